@@ -9,7 +9,10 @@ cross-entropy -> backward -> [all-reduce of the flat adapter-gradient buffer ove
 on a synthetic CIFAR100-shaped batch (B=128 per GPU, 3x224x224, C=100) that is resident in HBM
 before the timed region.  Weak scaling: every rank processes its own 128-image shard.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
+Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").  A plain run only sets up, warms up, times the
+K steps and prints the line (`ms_per_step` = wall time of one timed step); `--full` adds the measurements the headline does not
+need (roofline event passes, vendor-GEMM ceiling, concurrent runs, harness rate, CPU baseline); `--dump-outputs DIR` writes
+what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -276,6 +279,29 @@ def pin_rank_to_cores(local_rank, local_world):
         return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(eng, logits, loss):
+    """What a caller of the step holds after its last call, copied to the host: the logits and loss it returned and the state it
+    updated in place (trainable parameters, BatchNorm running statistics)."""
+    out = {"logits": logits, "loss": loss, "params": eng.params, "bn_running_mean": eng.running_mean,
+           "bn_running_var": eng.running_var}
+    return {k: v.detach().to("cpu", torch.float32, copy=True) for k, v in out.items()}
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy in float32, DUMP_MAX_BYTES in all: an array larger than its equal share of the budget is replaced by the
+    same seeded sample of its elements on every run (in index order), so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        if t.numel() > share:
+            t = t.flatten()[torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values]
+        np.save(os.path.join(dirname, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def _flush_c_stdio():
     try:
         import ctypes
@@ -294,7 +320,15 @@ def main():
     ap.add_argument("--arch", default="ViT-B/32")
     ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "fp8-act"],
                     help="frozen block weights: bf16, or e4m3 codes + per-channel scales (BASELINE config 5 with --arch ViT-L/14)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure what it does not need: the per-launch GEMM / HBM-kernel event "
+                         "passes and the roofline object, the vendor-GEMM ceiling and, at N = 1 on the headline configuration, "
+                         "concurrent_runs, the train_one harness rate and the CPU baseline.  Without it a run sets up, warms up, "
+                         "times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): the returned logits and loss, and "
+                         "the trainable parameters and BatchNorm running statistics the step updated in place")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--dp-exchange", choices=["auto", "single", "staged", "pipelined"], default="auto",
                     help="(N > 1) auto (default): time BOTH single and staged, W warm-up + K timed steps each, report the faster one "
                          "as `value` and both under config.exchange_schedules -- which of the two wins on N real GPUs has never been "
@@ -305,7 +339,7 @@ def main():
     ap.add_argument("--dp-route", action="store_true",
                     help="(N = 1) also time the DP step on a 1-rank RCCL group in its three exchange schedules (single / pipelined / "
                          "staged) and report them beside the fused step (dp_route)")
-    ap.add_argument("--no-harness", action="store_true", help="skip the reference-API (train_one) throughput measurement")
+    ap.add_argument("--no-harness", action="store_true", help="(--full) skip the reference-API (train_one) throughput measurement")
     ap.add_argument("--graph", action="store_true",
                     help="(N = 1, measurement) time the step as ONE captured HIP graph replay (engine.capture_train_step) instead of the "
                          "~200 launches of the C call; the line then carries step_launch = 'hip-graph'")
@@ -319,13 +353,14 @@ def main():
                                                             "gloo carries device tensors")
     ap.add_argument("--share-device", action="store_true", help="(tests only) every rank uses cuda:0")
     ap.add_argument("--strict-traffic", action="store_true",
-                    help="exit with status 3 when the committed PMC pass (profiles/hbm_traffic.json) was not taken with this "
-                         "build's kernel sources, instead of printing the line with traffic null and traffic_stale true "
+                    help="(implies --full) exit with status 3 when the committed PMC pass (profiles/hbm_traffic.json) was not taken "
+                         "with this build's kernel sources, instead of printing the line with traffic null and traffic_stale true "
                          "(tests/test_zz_profiles_current.py enforces the same on the committed tree)")
     ap.add_argument("--pmc-calib", action="store_true",
                     help="(profiling runs only) first move a known byte count through HBM so that the FETCH_SIZE / "
                          "WRITE_SIZE counters of the same rocprofv3 pass can be calibrated (scripts/pmc_traffic.py)")
     args = ap.parse_args()
+    args.full = args.full or args.strict_traffic       # the traffic check belongs to the roofline object
 
     if args.cpu_sweep:
         for n in (8, 16, 32, 64, 128):
@@ -445,14 +480,15 @@ def main():
         med = v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
         xus = sorted(eng.exchange_times_us()) if world > 1 else []
         eng.time_exchange(False)
-        return dt, med, loss, (xus[len(xus) // 2] if xus else None)
+        outputs = step_outputs(eng, logits, loss) if args.dump_outputs else None
+        return dt, med, loss, (xus[len(xus) // 2] if xus else None), outputs
 
     per_schedule = {}
     for sch in schedules:
-        dt, median_ms, loss, x_us = timed_region(sch)
+        dt, median_ms, loss, x_us, outputs = timed_region(sch)
         print(f"[bench rank {rank}/{world}] {sch if world > 1 else 'step'}: {dt / args.steps * 1e3:.3f} ms/step (median {median_ms:.3f})"
               + (f", exchange {x_us:.1f} us" if x_us is not None else ""), file=sys.stderr, flush=True)   # stragglers show here
-        rec = {"dt": dt, "median_ms": median_ms, "loss": float(loss)}
+        rec = {"dt": dt, "median_ms": median_ms, "loss": float(loss), "outputs": outputs}
         if world > 1:
             # every rank's own clock: the whole-job time is the MAX (a straggler shows as one large entry), and the exchange time per
             # rank says whether a slow step is the collective or the rank's kernels
@@ -475,19 +511,22 @@ def main():
     args.dp_exchange = best
     final_loss = per_schedule[best]["loss"]
     eng.check_streamk()          # a stream-K hand-off that timed out would make the timed steps invalid: fail loudly
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, per_schedule[best]["outputs"])
 
-    # ---- dominant kernel (MFMA GEMM family): HIP events around every GEMM launch, measured over
-    # extra steps right after the timed region so that event recording does not perturb `value`.
-    prof_steps = max(1, min(args.steps, 10))
     step = eager_step                                  # the per-launch event passes below bracket individual launches: eager
-    gemm_ms, gemm_flops, gemm_launches = eng.profile_gemms(lambda: [step() for _ in range(prof_steps)])
-    gemm_by_shape = dict(eng.last_profile_by_shape)
-    algo_bytes_total = eng.last_profile_bytes
-    # ... and a second pass that also brackets the HBM-bound kernels (their own pass: more events between the kernels)
-    eng.profile_gemms(lambda: [step() for _ in range(prof_steps)], all_kernels=True)
-    hbm_kernels = {k: {"launches_per_step": c / prof_steps, "avg_us": m * 1e3 / max(c, 1), "algorithmic_bytes_per_launch": b / max(c, 1),
-                       "achieved_TBps": b / max(m * 1e-3, 1e-12) / 1e12, "frac_of_hbm_peak": b / max(m * 1e-3, 1e-12) / 1e12 / PEAK_HBM_TBS}
-                   for k, (c, m, b) in sorted(eng.last_profile_hbm.items(), key=lambda kv: -kv[1][1])}
+    if args.full:
+        # ---- dominant kernel (MFMA GEMM family): HIP events around every GEMM launch, measured over
+        # extra steps right after the timed region so that event recording does not perturb `value`.
+        prof_steps = max(1, min(args.steps, 10))
+        gemm_ms, gemm_flops, gemm_launches = eng.profile_gemms(lambda: [step() for _ in range(prof_steps)])
+        gemm_by_shape = dict(eng.last_profile_by_shape)
+        algo_bytes_total = eng.last_profile_bytes
+        # ... and a second pass that also brackets the HBM-bound kernels (their own pass: more events between the kernels)
+        eng.profile_gemms(lambda: [step() for _ in range(prof_steps)], all_kernels=True)
+        hbm_kernels = {k: {"launches_per_step": c / prof_steps, "avg_us": m * 1e3 / max(c, 1), "algorithmic_bytes_per_launch": b / max(c, 1),
+                           "achieved_TBps": b / max(m * 1e-3, 1e-12) / 1e12, "frac_of_hbm_peak": b / max(m * 1e-3, 1e-12) / 1e12 / PEAK_HBM_TBS}
+                       for k, (c, m, b) in sorted(eng.last_profile_hbm.items(), key=lambda kv: -kv[1][1])}
 
     dp_route = None
     if args.dp_route and world == 1:
@@ -538,6 +577,42 @@ def main():
         site = args.method in ("kadaptation", "lora")
         r = 32 if args.method == "kadaptation" else 8
         gflop = train_gflop_per_image(arch.width, arch.layers, arch.patch, arch.resolution, arch.embed_dim, classes, r, site)
+        headline = (args.arch, args.method, args.batch, args.weights) == ("ViT-B/32", "kadaptation", 128, "bf16")
+        metric = "images/sec fine-tune, CLIP ViT-B/32 + KAdaptation, bs=128, 1/2/4/8 GPU" if headline else \
+            f"images/sec fine-tune, CLIP {args.arch} + {args.method}, bs={args.batch}/GPU, {args.weights} weights"
+        out = {
+            "metric": metric,
+            "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms, "median_ms_per_step": median_ms, "value_at_median": args.batch * world / (median_ms * 1e-3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            # the arithmetic type of the path: bf16 operands on the bf16 MFMA, f32 accumulate; with --weights fp8 the frozen
+            # weights are e4m3 codes converted to bf16 in the GEMM (the activation side stays bf16)
+            "dtype": {"bf16": "bf16", "fp8": "bf16 x fp8-e4m3 weights", "fp8-act": "fp8-e4m3 x fp8-e4m3 (forward frozen products), bf16 x fp8 (backward)"}[args.weights], "data": "synthetic",
+            "config": {"workload": f"CLIP {args.arch} + {args.method} fine-tune step (fwd+CE+bwd+SGD), "
+                                   f"{args.batch} images/GPU 3x{arch.resolution}x{arch.resolution}, C={classes}, "
+                                   f"synthetic OpenAI-layout checkpoint, adapters at reference init, frozen block "
+                                   f"weights {args.weights}" + (" (e4m3 codes + per-channel scales, bf16 activations, f32 accumulate)"
+                                                                 if args.weights == "fp8" else ""),
+                       "global_batch": args.batch * world, "parallelism": f"dp{world}",
+                       "step_launch": "hip-graph replay" if (args.graph and world == 1) else "eager (one C call, ~200 kernel launches)",
+                       "gradient_exchange": ("none" if world == 1 else args.exchange), "rccl_ranks": world if (world > 1 and args.dist_backend == "nccl") else 0,
+                       "gradient_buckets": 0 if world == 1 else (3 if args.dp_exchange == "staged" else 1),
+                       "exchange_us_per_step": per_schedule[best].get("exchange_us_per_step"),
+                       "per_rank_ms_per_step": per_schedule[best].get("per_rank_ms_per_step"),
+                       "exchange_schedules": None if world == 1 else {
+                           k: {"images_per_sec": args.batch * world * args.steps / v["dt"], "ms_per_step": v["dt"] / args.steps * 1e3,
+                               "median_ms_per_step": v["median_ms"], "exchange_us_per_step": v.get("exchange_us_per_step"),
+                               "per_rank_ms_per_step": v.get("per_rank_ms_per_step"), "per_rank_exchange_us": v.get("per_rank_exchange_us"),
+                               "overlapped_with_backward": k == "staged"}
+                           for k, v in per_schedule.items()},
+                       "exchange_schedule_chosen": None if world == 1 else ("the faster of " + " / ".join(per_schedule) + f" in THIS run: {best}" if len(per_schedule) > 1 else best),
+                       "exchange_us_how": None if world == 1 else "median over the timed steps of an event pair on the stream the exchange is enqueued on, max over ranks (single: around the in-stream all-reduce; staged: around the waits behind the backward = what the overlap did not hide; pipelined: on the second stream)",
+                       "gradient_exchange_schedule": "none" if world == 1 else {"single": "one all-reduce of the flat buffer behind the fused forward/backward call", "pipelined": "one all-reduce of the flat buffer + SGD on a second stream under the next step's stem", "staged": "three buckets overlapped with the staged backward"}[args.dp_exchange], "exchanged_floats_per_step": 0 if world == 1 else int(eng.n_params),
+                       "train_gflop_per_image": gflop, "final_loss": final_loss},
+        }
+        if dp_route is not None:
+            out["dp_route"] = dp_route
+    if rank == 0 and args.full:
         step_tflops = value / world * gflop / 1e3      # whole-step algorithmic TFLOP/s per GPU
         gemm_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
         algo_bytes = algo_bytes_total / max(gemm_launches, 1)
@@ -573,79 +648,44 @@ def main():
             for (epi, M, N, K), (cnt, ms_k, fl_k, by_k) in sorted(gemm_by_shape.items(), key=lambda kv: -kv[1][1]):
                 print(f"[shape] epi={EPI_NAMES.get(epi, epi)} M={M} N={N} K={K} n/step={cnt / prof_steps:.1f} avg_us={ms_k * 1e3 / cnt:.1f}",
                       file=sys.stderr)
-        headline = (args.arch, args.method, args.batch, args.weights) == ("ViT-B/32", "kadaptation", 128, "bf16")
-        metric = "images/sec fine-tune, CLIP ViT-B/32 + KAdaptation, bs=128, 1/2/4/8 GPU" if headline else \
-            f"images/sec fine-tune, CLIP {args.arch} + {args.method}, bs={args.batch}/GPU, {args.weights} weights"
-        out = {
-            "metric": metric,
-            "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "median_ms_per_step": median_ms, "value_at_median": args.batch * world / (median_ms * 1e-3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            # the arithmetic type of the path: bf16 operands on the bf16 MFMA, f32 accumulate; with --weights fp8 the frozen
-            # weights are e4m3 codes converted to bf16 in the GEMM (the activation side stays bf16)
-            "dtype": {"bf16": "bf16", "fp8": "bf16 x fp8-e4m3 weights", "fp8-act": "fp8-e4m3 x fp8-e4m3 (forward frozen products), bf16 x fp8 (backward)"}[args.weights], "data": "synthetic",
-            "config": {"workload": f"CLIP {args.arch} + {args.method} fine-tune step (fwd+CE+bwd+SGD), "
-                                   f"{args.batch} images/GPU 3x{arch.resolution}x{arch.resolution}, C={classes}, "
-                                   f"synthetic OpenAI-layout checkpoint, adapters at reference init, frozen block "
-                                   f"weights {args.weights}" + (" (e4m3 codes + per-channel scales, bf16 activations, f32 accumulate)"
-                                                                 if args.weights == "fp8" else ""),
-                       "global_batch": args.batch * world, "parallelism": f"dp{world}",
-                       "step_launch": "hip-graph replay" if (args.graph and world == 1) else "eager (one C call, ~200 kernel launches)",
-                       "gradient_exchange": ("none" if world == 1 else args.exchange), "rccl_ranks": world if (world > 1 and args.dist_backend == "nccl") else 0,
-                       "gradient_buckets": 0 if world == 1 else (3 if args.dp_exchange == "staged" else 1),
-                       "exchange_us_per_step": per_schedule[best].get("exchange_us_per_step"),
-                       "per_rank_ms_per_step": per_schedule[best].get("per_rank_ms_per_step"),
-                       "exchange_schedules": None if world == 1 else {
-                           k: {"images_per_sec": args.batch * world * args.steps / v["dt"], "ms_per_step": v["dt"] / args.steps * 1e3,
-                               "median_ms_per_step": v["median_ms"], "exchange_us_per_step": v.get("exchange_us_per_step"),
-                               "per_rank_ms_per_step": v.get("per_rank_ms_per_step"), "per_rank_exchange_us": v.get("per_rank_exchange_us"),
-                               "overlapped_with_backward": k == "staged"}
-                           for k, v in per_schedule.items()},
-                       "exchange_schedule_chosen": None if world == 1 else ("the faster of " + " / ".join(per_schedule) + f" in THIS run: {best}" if len(per_schedule) > 1 else best),
-                       "exchange_us_how": None if world == 1 else "median over the timed steps of an event pair on the stream the exchange is enqueued on, max over ranks (single: around the in-stream all-reduce; staged: around the waits behind the backward = what the overlap did not hide; pipelined: on the second stream)",
-                       "gradient_exchange_schedule": "none" if world == 1 else {"single": "one all-reduce of the flat buffer behind the fused forward/backward call", "pipelined": "one all-reduce of the flat buffer + SGD on a second stream under the next step's stem", "staged": "three buckets overlapped with the staged backward"}[args.dp_exchange], "exchanged_floats_per_step": 0 if world == 1 else int(eng.n_params),
-                       "train_gflop_per_image": gflop, "final_loss": final_loss},
-            "roofline": {"bound": "mfma", "kernel": "gemm8_kernel<...> + gemm_kphase_kernel<...> + gemm_kernel<...> + gemm_streamk_kernel<...> (pevit_amd/csrc/gemm.hip: all epilogues / tile shapes)",
-                         "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s",
-                         "frac": gemm_tflops / peak, "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_stale": traffic_stale,
-                         # the whole step against the same peak: images/s x algorithmic GFLOP/image, and the matrix-core work
-                         # actually executed (class-token pruning of the last block) over the step time
-                         "whole_step_frac": step_tflops / peak,
-                         # round 5: BOTH floors of the step.  Its arithmetic intensity (flop per algorithmic byte of every launch)
-                         # lies below the ridge, so the step as a whole is HBM-side; `bound` above names the roof of the dominant
-                         # KERNEL FAMILY (the GEMMs, each well above the ridge), per_kernel[*].bound that of every product
-                         "mfma_floor_ms": mfma_floor_ms, "hbm_floor_ms": hbm_floor_ms,
-                         "algorithmic_bytes_per_step": hbm_bytes_step,
-                         "whole_step_flop_per_byte": gflop * args.batch * 1e9 / max(hbm_bytes_step, 1.0), "ridge_flop_per_byte": ridge,
-                         "whole_step_bound": "hbm" if gflop * args.batch * 1e9 / max(hbm_bytes_step, 1.0) < ridge else "mfma",
-                         "whole_step_hbm_frac": hbm_bytes_step / (ms * 1e-3) / (PEAK_HBM_TBS * 1e12),
-                         # HBM-side bytes of EVERY dispatch of a step from the same two PMC passes as `traffic` (per step)
-                         "traffic_all": traffic_all, "traffic_all_unit": "bytes/step",
-                         "traffic_all_over_algorithmic": (traffic_all / hbm_bytes_step) if traffic_all else None,
-                         "executed_gemm_frac_of_peak": gemm_flops / prof_steps / 1e12 / (ms * 1e-3) / peak,
-                         "non_gemm_ms_per_step": ms - gemm_ms / prof_steps,
-                         "hbm_kernels": hbm_kernels,
-                         "peak_attainable_measured": {"value": attainable, "unit": "TFLOP/s",
-                                                      "how": "vendor-library bf16 GEMM 4096^3 (torch.matmul), measured in this run "
-                                                             "after the timed region; not used by the product path"},
-                         "kernels_hash": kernels_hash(),
-                         "traffic_how": traffic_how, "algorithmic_bytes_per_launch": algo_bytes,
-                         "launches_per_step": gemm_launches / prof_steps,
-                         "per_kernel": per_kernel,
-                         "avg_launch_us": gemm_ms * 1e3 / max(gemm_launches, 1),
-                         "gemm_ms_per_step": gemm_ms / prof_steps,
-                         "flops_per_launch": gemm_flops / max(gemm_launches, 1),
-                         "how": "2*M*N*K of every GEMM launch / HIP-event duration of that launch (events on the "
-                                "launch stream), summed over %d steps" % prof_steps,
-                         "whole_step": {"achieved": step_tflops, "frac": step_tflops / peak,
-                                        "how": "images/s x algorithmic GFLOP/image (SURVEY 8d) / peak",
-                                        # the last block runs its post-attention products on the class-token rows only
-                                        # (identical results): the matrix-core work actually executed per step is lower
-                                        "executed_gemm_tflop_per_step": gemm_flops / prof_steps / 1e12,
-                                        "executed_gemm_frac_of_peak": gemm_flops / prof_steps / 1e12 / (ms * 1e-3) / peak}},
-        }
-        if dp_route is not None:
-            out["dp_route"] = dp_route
+        out["roofline"] = {"bound": "mfma", "kernel": "gemm8_kernel<...> + gemm_kphase_kernel<...> + gemm_kernel<...> + gemm_streamk_kernel<...> (pevit_amd/csrc/gemm.hip: all epilogues / tile shapes)",
+                           "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s",
+                           "frac": gemm_tflops / peak, "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_stale": traffic_stale,
+                           # the whole step against the same peak: images/s x algorithmic GFLOP/image, and the matrix-core work
+                           # actually executed (class-token pruning of the last block) over the step time
+                           "whole_step_frac": step_tflops / peak,
+                           # round 5: BOTH floors of the step.  Its arithmetic intensity (flop per algorithmic byte of every launch)
+                           # lies below the ridge, so the step as a whole is HBM-side; `bound` above names the roof of the dominant
+                           # KERNEL FAMILY (the GEMMs, each well above the ridge), per_kernel[*].bound that of every product
+                           "mfma_floor_ms": mfma_floor_ms, "hbm_floor_ms": hbm_floor_ms,
+                           "algorithmic_bytes_per_step": hbm_bytes_step,
+                           "whole_step_flop_per_byte": gflop * args.batch * 1e9 / max(hbm_bytes_step, 1.0), "ridge_flop_per_byte": ridge,
+                           "whole_step_bound": "hbm" if gflop * args.batch * 1e9 / max(hbm_bytes_step, 1.0) < ridge else "mfma",
+                           "whole_step_hbm_frac": hbm_bytes_step / (ms * 1e-3) / (PEAK_HBM_TBS * 1e12),
+                           # HBM-side bytes of EVERY dispatch of a step from the same two PMC passes as `traffic` (per step)
+                           "traffic_all": traffic_all, "traffic_all_unit": "bytes/step",
+                           "traffic_all_over_algorithmic": (traffic_all / hbm_bytes_step) if traffic_all else None,
+                           "executed_gemm_frac_of_peak": gemm_flops / prof_steps / 1e12 / (ms * 1e-3) / peak,
+                           "non_gemm_ms_per_step": ms - gemm_ms / prof_steps,
+                           "hbm_kernels": hbm_kernels,
+                           "peak_attainable_measured": {"value": attainable, "unit": "TFLOP/s",
+                                                        "how": "vendor-library bf16 GEMM 4096^3 (torch.matmul), measured in this run "
+                                                               "after the timed region; not used by the product path"},
+                           "kernels_hash": kernels_hash(),
+                           "traffic_how": traffic_how, "algorithmic_bytes_per_launch": algo_bytes,
+                           "launches_per_step": gemm_launches / prof_steps,
+                           "per_kernel": per_kernel,
+                           "avg_launch_us": gemm_ms * 1e3 / max(gemm_launches, 1),
+                           "gemm_ms_per_step": gemm_ms / prof_steps,
+                           "flops_per_launch": gemm_flops / max(gemm_launches, 1),
+                           "how": "2*M*N*K of every GEMM launch / HIP-event duration of that launch (events on the "
+                                  "launch stream), summed over %d steps" % prof_steps,
+                           "whole_step": {"achieved": step_tflops, "frac": step_tflops / peak,
+                                          "how": "images/s x algorithmic GFLOP/image (SURVEY 8d) / peak",
+                                          # the last block runs its post-attention products on the class-token rows only
+                                          # (identical results): the matrix-core work actually executed per step is lower
+                                          "executed_gemm_tflop_per_step": gemm_flops / prof_steps / 1e12,
+                                          "executed_gemm_frac_of_peak": gemm_flops / prof_steps / 1e12 / (ms * 1e-3) / peak}}
         if world == 1 and not args.no_harness and headline:
             del eng, images, labels
             torch.cuda.empty_cache()

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 R=${1:-r06}; export R
 O=gpurun_out/${R}_other_configs.jsonl; : > $O
-run() { timeout 400 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --no-harness "$@" 2>/dev/null | tail -1 >> $O; }
+run() { timeout 400 python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --no-harness "$@" 2>/dev/null | tail -1 >> $O; }
 run
 run --batch 64
 run --method lora

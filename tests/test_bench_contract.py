@@ -103,6 +103,60 @@ def test_flush_helper_and_the_dp_schedule_option(monkeypatch, capsys):
     assert "--dp-exchange" in seen["cmd"] and "staged" in seen["cmd"]
 
 
+def test_dump_outputs_are_float32_npy_within_the_budget_and_sampled_the_same_way_every_run(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: one DIR/<name>.npy per array, float32, DUMP_MAX_BYTES in all; an array over its share of the budget
+    becomes a seeded sample of its elements that is the same on every run, so that two builds compare element for element."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    g = torch.Generator().manual_seed(1)
+    arrays = {"logits": torch.randn(4, 10, generator=g), "loss": torch.tensor([2.5], dtype=torch.float64),
+              "params": torch.randn(5000, generator=g)}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["logits.npy", "loss.npy", "params.npy"]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 4096
+    assert np.array_equal(a["logits"], arrays["logits"].numpy()) and float(a["loss"][0]) == 2.5    # small arrays whole
+    assert a["params"].size == 4096 // (4 * 3) and np.isin(a["params"], arrays["params"].numpy()).all()
+    for n in arrays:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """A plain run is lean: the headline line (ms_per_step = the wall time of one of the K timed steps) and nothing that needs runs
+    of its own; --dump-outputs writes the last timed step's results, identical from run to run on the same arguments; --full
+    brings the roofline object back."""
+    import json
+    import subprocess
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--arch", "tiny-256",
+            "--batch", "16"]
+
+    def run(*extra):
+        out = subprocess.run(base + list(extra), capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.splitlines()[-1])
+    lines = [run("--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    for d in lines:
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "images/sec" and d["higher_is_better"] is True
+        assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"] and d["dtype"] == "bf16"
+        assert not {"roofline", "cpu_baseline", "concurrent_runs", "harness_images_per_sec"} & set(d)
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    assert set(a) == {"logits", "loss", "params", "bn_running_mean", "bn_running_var"}
+    assert a["logits"].shape == (16, 100) and a["logits"].dtype == np.float32 and np.isfinite(a["logits"]).all()
+    assert abs(float(a["loss"][0]) - lines[0]["config"]["final_loss"]) < 1e-6
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
+    full = run("--full", "--no-cpu-baseline")
+    assert full["roofline"]["achieved"] > 0 and full["roofline"]["launches_per_step"] > 0
+
+
 @pytest.mark.gpu
 def test_concurrent_runs_side_measurement_is_bit_identical_to_solo_runs():
     """bench.py's `concurrent_runs` object (round 6): K engine contexts on K streams at batch 64 (K = 1, 2, 3) and 128 (K = 1, 2);

@@ -46,7 +46,7 @@ def test_loaders_from_tensor_archive(tmp_path):
     assert xf.dtype == torch.float32 and torch.equal(yf, y)
     assert float(xf.max()) < 3.0 and float(xf.min()) > -2.5          # uint8 -> CLIP mean/std normalisation
     mean, std = torch.tensor(cfg.INPUT.MEAN).view(1, 3, 1, 1), torch.tensor(cfg.INPUT.STD).view(1, 3, 1, 1)
-    assert torch.equal(xf, (x.float() / 255.0 - mean) / std)
+    assert torch.equal(xf.cpu(), (x.cpu().float() / 255.0 - mean) / std)     # normalised on the host; resident where the set lives
     cfg.DATASET.NORMALIZE_ON_HOST = False
     merged = _harness.merge_trainval_loader(train, val)
     assert len(merged.dataset) == 20

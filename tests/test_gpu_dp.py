@@ -102,7 +102,8 @@ def test_two_rank_hip_step_equals_mean_of_shard_steps(case, mode, tmp_path):
 def test_bench_multi_rank_launch_contract(tmp_path, exchange):
     """bench.py exactly as the driver launches it for N > 1 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 ... bench.py --gpus N --steps K --warmup W), two ranks on the one GPU of the test box (gloo
-    instead of RCCL, both ranks on cuda:0): rank 0 prints ONE JSON line whose value is the whole-job aggregate."""
+    instead of RCCL, both ranks on cuda:0; --full for the roofline object): rank 0 prints ONE JSON line whose value is the whole-job
+    aggregate."""
     import json
     import subprocess
     if not torch.cuda.is_available():
@@ -110,7 +111,7 @@ def test_bench_multi_rank_launch_contract(tmp_path, exchange):
     port = 29700 + (os.getpid() % 2000) + (7 if exchange == "flat" else 0)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--arch", "tiny-256", "--batch", "16", "--dist-backend", "gloo", "--share-device", "--exchange", exchange]
+           "--arch", "tiny-256", "--batch", "16", "--dist-backend", "gloo", "--share-device", "--exchange", exchange, "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

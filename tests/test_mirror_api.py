@@ -128,7 +128,7 @@ def test_init_head_with_text_encoder(ckpt):
     cfg.TRAIN.INIT_HEAD_WITH_TEXT_ENCODER = True
     cfg.DATASET.CLASS_NAMES = [torch.from_numpy(z["tokens"][c]) for c in range(10)]
     clf = Classifier(cfg, 0)
-    np.testing.assert_allclose(clf.layers[0].weight.detach().numpy(), z["zeroshot_weights"].T, atol=1e-6)
+    np.testing.assert_allclose(clf.layers[0].weight.detach().cpu().numpy(), z["zeroshot_weights"].T, atol=1e-6)
     assert float(clf.layers[0].bias.abs().max()) == 0.0
 
 
@@ -220,7 +220,8 @@ def test_head_merge_folds_the_projection_into_the_head(ckpt):
     E = proj.shape[0]
     assert merged.layers[0].weight.shape == (w.shape[0], E) and merged.channel_bn.num_features == E
     assert torch.allclose(merged.layers[0].weight.data, w @ proj.T) and torch.equal(merged.layers[0].bias.data, b)
-    assert torch.equal(merged.backbone.visual.proj.data, torch.eye(E)) and merged.backbone.visual.arch.embed_dim == E
+    proj_m = merged.backbone.visual.proj.data
+    assert torch.equal(proj_m, torch.eye(E, device=proj_m.device)) and merged.backbone.visual.arch.embed_dim == E
     del merged                                  # a merged tower is never recycled: the next Classifier gets the file's projection
     import gc; gc.collect()
     cfg.TRAIN.MERGE_ENCODER_AND_HEAD_PROJ = False
