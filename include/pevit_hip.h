@@ -11,6 +11,9 @@
  *                                           incl. MultiheadAttention.multi_head_attention_forward
  *                                           (model.py:612-834) and adapter_forward (model.py:563-584;
  *                                           lora_model.py:490-514), and their autograd backward
+ *   pevit_attention_forward / _backward     MultiheadAttention.forward(x, x, x, need_weights, attn_mask=None,
+ *                                           average_attn_weights)  model.py:837-944 (-> 612-834) of one block
+ *                                           (resblocks[i].attn), incl. the head-averaged / per-head weights
  *   pevit_visual_forward / _backward        VisionTransformer.forward      model.py:1034-1051
  *                                           (= CLIP.encode_image, model.py:1151-1152)
  *   pevit_head_forward_backward             Classifier.forward tail + CrossEntropyLoss
@@ -135,6 +138,19 @@ int pevit_blocks_forward(pevit_ctx* ctx, void* stream, const float* x_nbe, float
                          int l_lo, int l_hi);
 int pevit_blocks_backward(pevit_ctx* ctx, void* stream, const float* dy_nbe, float* dx_nbe_or_null, int batch, int l_lo,
                           int l_hi);
+/* MultiheadAttention.forward(x, x, x, need_weights, attn_mask=None, average_attn_weights) of block `layer`
+ * (model.py:837-944): x_nbe (N,B,E) f32 is the attention INPUT (ln_1's output inside the block); y_nbe (N,B,E) f32 is
+ * out_proj(attention) WITHOUT the residual.  weights_or_null: (B,N,N) (average_weights = 1) or (B,H,N,N) (0) f32
+ * softmax probabilities; NULL means need_weights = False.  The activations live in the layer's saved slots: a later
+ * pevit_blocks_backward is refused, and so is a pevit_attention_backward after any other forward.  Weight formats bf16,
+ * fp8 and f32-verify (fp8-act is refused). */
+int pevit_attention_forward(pevit_ctx* ctx, void* stream, int layer, const float* x_nbe, float* y_nbe, int batch,
+                            int save_for_backward, float* weights_or_null, int average_weights);
+/* dy -> dx (may be NULL); accumulates the adapter gradients of `layer` into the flat gradient buffer, including
+ * its share of the shared phm_rule factors, exactly as pevit_blocks_backward over [layer, layer+1) does.  Adapter,
+ * Compacter and the frozen tower: stock attention with frozen weights, dx only (no gradient is written). */
+int pevit_attention_backward(pevit_ctx* ctx, void* stream, int layer, const float* dy_nbe, float* dx_nbe_or_null,
+                             int batch);
 int pevit_visual_forward(pevit_ctx* ctx, void* stream, const float* images, float* feat, int batch,
                          int save_for_backward);
 int pevit_visual_backward(pevit_ctx* ctx, void* stream, const float* dfeat, int batch);
@@ -236,6 +252,9 @@ int pevit_op_delta_add(void* stream, void* qbuf, void* vbuf, const float* t, con
 int pevit_op_attn_fwd_delta(void* stream, void* q, const void* k, void* v, const float* t, const void* q16_bf16, const float* bias,
                             float ascale, void* out, int ldo, float* lse, int B, int H, int N);
 int pevit_op_attn_delta_hpw(int B, int H, int N);
+/* softmax probabilities P = exp(q k^T - lse) (attn_probs.hip): q, k (B*H, N, 64) bf16 as pevit_op_attn_fwd takes them, lse as it
+ * wrote it; average = 1: out (B, N, N) f32, the mean over the H heads; 0: out (B, H, N, N) f32.  N <= 384. */
+int pevit_op_attn_probs(void* stream, const void* q, const void* k, const float* lse, float* out, int B, int H, int N, int average);
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
  * stamps at their phase boundaries (NULL switches it off) */
 int pevit_debug_timeline(void* buf);

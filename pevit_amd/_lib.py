@@ -47,6 +47,8 @@ SIGNATURES = {
     "pevit_transformer_backward": (c_int, [P, P, P, P, c_int]),
     "pevit_blocks_forward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int]),
     "pevit_blocks_backward": (c_int, [P, P, P, P, c_int, c_int, c_int]),
+    "pevit_attention_forward": (c_int, [P, P, c_int, P, P, c_int, c_int, P, c_int]),
+    "pevit_attention_backward": (c_int, [P, P, c_int, P, P, c_int]),
     "pevit_visual_forward": (c_int, [P, P, P, P, c_int, c_int]),
     "pevit_visual_backward": (c_int, [P, P, P, c_int]),
     "pevit_visual_backward_part": (c_int, [P, P, P, c_int, c_int, c_int]),
@@ -81,6 +83,7 @@ SIGNATURES = {
     "pevit_op_delta_add": (c_int, [P, P, P, P, P, P, c_float, c_int, c_int, c_int]),
     "pevit_op_attn_fwd_delta": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int, P, c_int, c_int, c_int]),
     "pevit_op_attn_delta_hpw": (c_int, [c_int, c_int, c_int]),
+    "pevit_op_attn_probs": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int]),
     "pevit_debug_timeline": (c_int, [P]),
     "pevit_debug_occupy": (c_int, [P, c_int, c_int, C.c_double]),
     "pevit_op_lowrank_u": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int]),

@@ -93,7 +93,9 @@ struct pevit_ctx {
     float img_mean[3] = {0.f, 0.f, 0.f}, img_std[3] = {1.f, 1.f, 1.f};   // pevit_set_input_norm: preprocessing of uint8 pixels
     bool img_norm_set = false;
     int saved_batch = 0;
-    int saved_kind = 0;       // which forward the saved activations belong to: 1 = transformer seam, 2 = visual (class-token pruned)
+    int saved_kind = 0;       // which forward the saved activations belong to: 1 = transformer seam, 2 = visual (class-token pruned),
+                              // 3 = attention seam of layer saved_layer
+    int saved_layer = -1;
     // optional per-GEMM timing (HIP events on the caller's stream), see pevit_profile_begin
     bool prof_on = false;
     int prof_all = 0;         // also bracket the HBM-bound kernels (pevit_tune "profile_all")
@@ -472,6 +474,16 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
 // ------------------------------------------------------------------------------------
 namespace {
 
+// the forward the saved activations belong to, for error messages
+const char* saved_name(const pevit_ctx* c) {
+    switch (c->saved_kind) {
+        case 1: return "transformer_forward";
+        case 2: return "visual_forward";
+        case 3: return "attention_forward";
+        default: return "none";
+    }
+}
+
 int check_ready(pevit_ctx* c, int B, const char* who) {
     if (!c || !c->arena || !c->ws) { pevit_set_error("%s: context not bound", who); return -1; }
     if (B <= 0 || B > c->max_batch) { pevit_set_error("%s: batch %d outside [1,%d]", who, B, c->max_batch); return -1; }
@@ -582,72 +594,57 @@ GemmParams gpw(const pevit_ctx* c, const bf16* A, int lda, size_t w_off, int ldb
     return p;
 }
 
-// forward of the L residual blocks on internal (batch-major) rows.  x0 -> sav[0].x_in must
-// already hold the input; the output lands in ws + w_xfinal.
-// cls_only: the caller consumes only the class token of the last block (VisionTransformer.forward,
-// model.py:1046) -- everything of the last block that sits after the attention core is then
-// evaluated on the B class-token rows only (identical results, ~6 % fewer FLOPs per step).
-int blocks_forward(pevit_ctx* c, hipStream_t s, int B, bool cls_only, int l_lo = 0, int l_hi = -1) {
-    if (l_hi < 0) l_hi = c->L;
+// The attention half of block l between ln_1 and out_proj (MultiheadAttention.forward, model.py:612-812): the QKV product with the
+// adapter columns t of the attention-site methods, delta-add and the attention core.  Reads the layer's xn1 (or its e4m3 copy a8),
+// leaves q / k / v in the head layout, lse and attn_out in the layer's saved slots.  Shared by the block walk and the attention seam.
+int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, int l, unsigned char* a8, unsigned char* attn8) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
-    cls_only = cls_only && !post_mlp(c);
     char* W = c->ws; char* A = c->arena;
     const bool site = attention_site(c);
-    if (site || post_mlp(c)) CHECK(prep_adapters(c, s));
-    for (int l = l_lo; l < l_hi; ++l) {
-        const BlockArena& b = c->blk[l];
-        const LayerSaved& v = c->sav[l];
-        float* x_in = at<float>(W, v.x_in);
-        float* x_mid = at<float>(W, v.x_mid);
-        float* x_out = (l + 1 < c->L) ? at<float>(W, c->sav[l + 1].x_in) : at<float>(W, c->w_xfinal);
-        bf16* qkv = at<bf16>(W, v.qkv);
-        const size_t plane = (size_t)T * E;
-        // x = x + attn(ln_1(x))                                         model.py:973
-        unsigned char* a8 = c->fp8act ? at<unsigned char>(W, c->w_a8) : nullptr;
-        unsigned char* attn8 = c->fp8act ? at<unsigned char>(W, c->w_attn8) : nullptr;
-        PROF(c, s, PEVIT_PROF_LN_FWD, T, (double)T * E * (4 + c->es),
-             pevit_launch_ln_fwd(x_in, at<float>(A, b.ln1w), at<float>(A, b.ln1b), T, E, at<bf16>(W, v.xn1), nullptr,
-                                 at<float>(W, v.mean1), at<float>(W, v.rstd1), s, 0, c->f32, a8));
-        if (!c->fp8) {
-            GemmParams p = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wqkv), E, c->NQpad, T, site ? c->NQ : 3 * E, E);
-            p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.outf = at<float>(W, v.t); p.ldo = 64;
-            p.E = E; p.H = H; p.Ntok = N;
-            CHECK(gemm(c, EPI_QKV_HEADS, p, s));
-        } else {
-            // fp8 codes for the 3E frozen rows; the 64 trainable adapter rows stay bf16: as the bf16 tail of the same launch where the
-            // product runs on the staggered 8-wave kernel (round 4: the separate t = xn P product was the whole 1-2 % by which
-            // the fp8 format trailed bf16), as a small product of their own otherwise
-            GemmParams p = gpw(c, at<bf16>(W, v.xn1), E, b.wqkv, E, 3 * E, T, 3 * E, E, b.sqkv);
-            if (a8) { p.A = reinterpret_cast<const bf16*>(a8); p.a_fp8 = 1; }
-            p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.E = E; p.H = H; p.Ntok = N;
-            bool tail = false;
-            if (site && !a8 && c->fp8_tail) {
-                GemmParams m = p;
-                m.N = c->NQ; m.B2 = at<bf16>(A, b.wpan); m.ldb2 = E; m.Nb2 = 128; m.n_fp8 = 3 * E; m.outf = at<float>(W, v.t); m.ldo = 64;
-                if (pevit_gemm_mixed_ok(m, c->tune)) { p = m; tail = true; }
-            }
-            CHECK(gemm(c, EPI_QKV_HEADS, p, s));
-            if (site && !tail) {
-                GemmParams q = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wpan), E, 128, T, 64, E);
-                q.outf = at<float>(W, v.t); q.ldo = 64;
-                CHECK(gemm(c, EPI_F32, q, s));
-            }
+    const BlockArena& b = c->blk[l];
+    const LayerSaved& v = c->sav[l];
+    bf16* qkv = at<bf16>(W, v.qkv);
+    const size_t plane = (size_t)T * E;
+    if (!c->fp8) {
+        GemmParams p = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wqkv), E, c->NQpad, T, site ? c->NQ : 3 * E, E);
+        p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.outf = at<float>(W, v.t); p.ldo = 64;
+        p.E = E; p.H = H; p.Ntok = N;
+        CHECK(gemm(c, EPI_QKV_HEADS, p, s));
+    } else {
+        // fp8 codes for the 3E frozen rows; the 64 trainable adapter rows stay bf16: as the bf16 tail of the same launch where the
+        // product runs on the staggered 8-wave kernel (round 4: the separate t = xn P product was the whole 1-2 % by which
+        // the fp8 format trailed bf16), as a small product of their own otherwise
+        GemmParams p = gpw(c, at<bf16>(W, v.xn1), E, b.wqkv, E, 3 * E, T, 3 * E, E, b.sqkv);
+        if (a8) { p.A = reinterpret_cast<const bf16*>(a8); p.a_fp8 = 1; }
+        p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.E = E; p.H = H; p.Ntok = N;
+        bool tail = false;
+        if (site && !a8 && c->fp8_tail) {
+            GemmParams m = p;
+            m.N = c->NQ; m.B2 = at<bf16>(A, b.wpan); m.ldb2 = E; m.Nb2 = 128; m.n_fp8 = 3 * E; m.outf = at<float>(W, v.t); m.ldo = 64;
+            if (pevit_gemm_mixed_ok(m, c->tune)) { p = m; tail = true; }
         }
-        const float* dbias = nullptr;
-        if (c->d.method == PEVIT_KADAPTATION) dbias = c->params + c->p_layer0 + c->p_layer_stride * l + 4 * (size_t)E;
-        // delta-add and the attention core as ONE launch where a run of heads owns whole reference rows of the raw reshape
-        // (attn_delta.hip: N <= 64; ViT-B/32), otherwise delta_add + attn_fwd
-        // ... unless its one-workgroup-per-CU runs leave between a quarter and three quarters of the chip empty (measured at batch
-        // 64: 128 runs for 256 CUs, the two kernels are 0.6 % of the step faster; fused_attn_delta = 2 forces the fused form)
-        const int ad_hpw = pevit_attn_delta_hpw(B, H, N);
-        const int ad_runs = ad_hpw > 0 ? (B * H + ad_hpw - 1) / ad_hpw : 0;
-        const bool ad_fill = ad_hpw > 0 && (c->fused_attn_delta > 1 || 4 * ad_runs >= 3 * pevit_num_cus() || 4 * ad_runs <= pevit_num_cus());
-        const bool fused_ad = site && c->fused_attn_delta && !c->f32 && !attn8 && ad_fill;
-        if (fused_ad) {
-            PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T, (double)T * E * (3 + 2 + 1) * 2 + (double)T * 64 * 4 + (double)B * H * N * 4,   // q, k, v in; q', v', out
-                 pevit_launch_attn_fwd_delta(qkv, qkv + plane, qkv + 2 * plane, at<float>(W, v.t), at<bf16>(A, b.q16), dbias, c->ascale,
-                                             at<bf16>(W, v.attn_out), E, at<float>(W, v.lse), B, H, N, s));
-        } else {
+        CHECK(gemm(c, EPI_QKV_HEADS, p, s));
+        if (site && !tail) {
+            GemmParams q = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wpan), E, 128, T, 64, E);
+            q.outf = at<float>(W, v.t); q.ldo = 64;
+            CHECK(gemm(c, EPI_F32, q, s));
+        }
+    }
+    const float* dbias = nullptr;
+    if (c->d.method == PEVIT_KADAPTATION) dbias = c->params + c->p_layer0 + c->p_layer_stride * l + 4 * (size_t)E;
+    // delta-add and the attention core as ONE launch where a run of heads owns whole reference rows of the raw reshape
+    // (attn_delta.hip: N <= 64; ViT-B/32), otherwise delta_add + attn_fwd
+    // ... unless its one-workgroup-per-CU runs leave between a quarter and three quarters of the chip empty (measured at batch
+    // 64: 128 runs for 256 CUs, the two kernels are 0.6 % of the step faster; fused_attn_delta = 2 forces the fused form)
+    const int ad_hpw = pevit_attn_delta_hpw(B, H, N);
+    const int ad_runs = ad_hpw > 0 ? (B * H + ad_hpw - 1) / ad_hpw : 0;
+    const bool ad_fill = ad_hpw > 0 && (c->fused_attn_delta > 1 || 4 * ad_runs >= 3 * pevit_num_cus() || 4 * ad_runs <= pevit_num_cus());
+    const bool fused_ad = site && c->fused_attn_delta && !c->f32 && !attn8 && ad_fill;
+    if (fused_ad) {
+        PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T, (double)T * E * (3 + 2 + 1) * 2 + (double)T * 64 * 4 + (double)B * H * N * 4,   // q, k, v in; q', v', out
+             pevit_launch_attn_fwd_delta(qkv, qkv + plane, qkv + 2 * plane, at<float>(W, v.t), at<bf16>(A, b.q16), dbias, c->ascale,
+                                         at<bf16>(W, v.attn_out), E, at<float>(W, v.lse), B, H, N, s));
+    } else {
         if (site) {
             PROF(c, s, PEVIT_PROF_DELTA_ADD, T, (double)T * E * 4 * c->es + (double)T * 64 * 4,     // q and v read + written, t read
                  pevit_launch_delta_add(qkv, eadv(c, qkv, 2 * plane), at<float>(W, v.t), at<float>(A, b.q32), at<bf16>(A, b.q16), dbias,
@@ -660,7 +657,34 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, bool cls_only, int l_lo =
             PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2 + (double)B * H * N * 4,
                  pevit_launch_attn_fwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<float>(W, v.lse), B,
                                        H, N, s, attn8));
-        }
+    }
+    return 0;
+}
+
+// forward of the L residual blocks on internal (batch-major) rows.  x0 -> sav[0].x_in must
+// already hold the input; the output lands in ws + w_xfinal.
+// cls_only: the caller consumes only the class token of the last block (VisionTransformer.forward,
+// model.py:1046) -- everything of the last block that sits after the attention core is then
+// evaluated on the B class-token rows only (identical results, ~6 % fewer FLOPs per step).
+int blocks_forward(pevit_ctx* c, hipStream_t s, int B, bool cls_only, int l_lo = 0, int l_hi = -1) {
+    if (l_hi < 0) l_hi = c->L;
+    const int E = c->E, T = B * c->N, N = c->N;
+    cls_only = cls_only && !post_mlp(c);
+    char* W = c->ws; char* A = c->arena;
+    if (attention_site(c) || post_mlp(c)) CHECK(prep_adapters(c, s));
+    for (int l = l_lo; l < l_hi; ++l) {
+        const BlockArena& b = c->blk[l];
+        const LayerSaved& v = c->sav[l];
+        float* x_in = at<float>(W, v.x_in);
+        float* x_mid = at<float>(W, v.x_mid);
+        float* x_out = (l + 1 < c->L) ? at<float>(W, c->sav[l + 1].x_in) : at<float>(W, c->w_xfinal);
+        // x = x + attn(ln_1(x))                                         model.py:973
+        unsigned char* a8 = c->fp8act ? at<unsigned char>(W, c->w_a8) : nullptr;
+        unsigned char* attn8 = c->fp8act ? at<unsigned char>(W, c->w_attn8) : nullptr;
+        PROF(c, s, PEVIT_PROF_LN_FWD, T, (double)T * E * (4 + c->es),
+             pevit_launch_ln_fwd(x_in, at<float>(A, b.ln1w), at<float>(A, b.ln1b), T, E, at<bf16>(W, v.xn1), nullptr,
+                                 at<float>(W, v.mean1), at<float>(W, v.rstd1), s, 0, c->f32, a8));
+        CHECK(attn_core_fwd(c, s, B, l, a8, attn8));
         // rows of the tail of this block: all T, or (last block, cls_only) the B class-token rows, which
         // sit N*E elements apart in every [T][E] buffer
         const bool cls = cls_only && l == c->L - 1;
@@ -748,6 +772,122 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, bool cls_only, int l_lo =
     return 0;
 }
 
+// Cross-layer state of the attention-site adapter gradients over one backward walk (block walk or attention seam): the optional
+// side stream of the token-contracted products, and the dP of the previously processed layer that lowrank_combo defers by one launch.
+struct AttnGradWalk {
+    bool use_side = false, combo = false, side_pending = false;
+    int prev_layer = -1, u_par = 0;
+    float* u_last = nullptr;
+};
+
+int attn_walk_begin(pevit_ctx* c, AttnGradWalk& w) {
+    const bool site = attention_site(c);
+    w.use_side = c->side_stream && site;
+    w.combo = c->lowrank_combo && site && !c->f32 && !w.use_side;
+    if (w.use_side && !c->side) {
+        HIP_OK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+        HIP_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        HIP_OK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    return 0;
+}
+
+// The attention half of block l's backward (the autograd of model.py:612-812 without the QKV dX product): ws+w_dyb (bf16, fp8: with
+// out_proj's channel scales folded in) -> out_proj dX -> attention backward into dqkv -> the low-rank adapter gradient partials of
+// the attention-site methods.  cls: class-token pruning of the last block (only the B class-token rows of dyb are defined).
+int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, int l, bool cls, AttnGradWalk& w) {
+    const int E = c->E, T = B * c->N, H = c->H, N = c->N;
+    char* W = c->ws; char* A = c->arena;
+    const bool site = attention_site(c);
+    const int chunks = pevit_lowrank_chunks(T);
+    const BlockArena& b = c->blk[l];
+    const LayerSaved& v = c->sav[l];
+    bf16* qkv = at<bf16>(W, v.qkv);
+    bf16* dqkv = at<bf16>(W, c->w_dqkv);
+    bf16* dyb = at<bf16>(W, c->w_dyb);
+    const size_t plane = (size_t)T * E;
+    const int R = cls ? B : T;
+    const int rs = cls ? N * E : E;            // row stride of [T][E] buffers
+    {
+        GemmParams p = gpw(c, dyb, rs, b.woT, E, E, R, E, E, 0);
+        p.outb = at<bf16>(W, c->w_dO); p.ldob = rs;
+        CHECK(gemm(c, EPI_BF16, p, s));
+    }
+    // dqkv / u32 are about to be overwritten: the previous layer's gradient contraction must have read them
+    if (w.side_pending) { HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0)); w.side_pending = false; }
+    if (c->f32)
+        CHECK(pevit_launch_attn_bwd_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), (const float*)eadv(c, qkv, 2 * plane),
+                                        at<float>(W, v.attn_out), E, at<float>(W, c->w_dO), E, at<float>(W, v.lse), (float*)dqkv,
+                                        c->NQ, B, H, N, s));
+    else
+        PROF(c, s, PEVIT_PROF_ATTN_BWD, T, (double)T * E * (N <= 64 ? 7 : 8) * 2 + (double)B * H * N * 4,     // q, k, v, (out: N > 64 only), dout in; dq, dk, dv out
+             pevit_launch_attn_bwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<bf16>(W, c->w_dO), E,
+                                   at<float>(W, v.lse), dqkv, c->NQ, B, H, N, s, (cls && N <= 64) ? 1 : 0));
+    if (site && w.combo) {
+        // u, dQ_q, dQ_v, d bias of this layer and the dP of the layer before it in ONE launch (lowrank.hip lowrank_combo_kernel)
+        float* u_cur = at<float>(W, w.u_par ? c->w_u32b : c->w_u32);
+        const LayerSaved* pv = w.prev_layer >= 0 ? &c->sav[w.prev_layer] : nullptr;
+        PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 3 * 2 + (double)T * 64 * 14 + (double)chunks * 4 * E * 32 * 4,
+             pevit_launch_lowrank_combo(1, pv ? 1 : 0, dqkv, c->NQ, at<bf16>(A, b.qT), u_cur, dqkv + 3 * E, at<float>(W, v.t),
+                                        at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
+                                        at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer),
+                                        pv ? at<bf16>(W, pv->xn1) : nullptr, E, w.u_last,
+                                        pv ? at<float>(W, c->w_partial + (size_t)w.prev_layer * c->partial_layer) : nullptr, B, H, N, E, s));
+        w.u_last = u_cur; w.prev_layer = l; w.u_par ^= 1;
+    } else if (site) {
+        if (c->f32)
+            CHECK(pevit_launch_lowrank_u_f32((const float*)dqkv, c->NQ, at<float>(A, b.q32), at<float>(W, c->w_u32),
+                                             (float*)eadv(c, dqkv, 3 * (size_t)E), B, H, N, E, s));
+        else
+            PROF(c, s, PEVIT_PROF_LOWRANK_U, T, (double)T * E * 2 * 2 + (double)T * 64 * 6,
+                 pevit_launch_lowrank_u(dqkv, c->NQ, at<bf16>(A, b.qT), at<float>(W, c->w_u32), dqkv + 3 * E, B, H, N, E, s));
+        // the token-contracted adapter gradients feed nothing before the end of the step: run them beside
+        // the QKV-backward GEMM / LayerNorm backward / next layer's MLP GEMMs on the second stream
+        hipStream_t gs = s;
+        if (w.use_side) {
+            HIP_OK(hipEventRecord(c->ev_fork, s));
+            HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+            gs = c->side;
+        }
+        if (c->f32)
+            CHECK(pevit_launch_lowrank_grad_f32(at<float>(W, v.xn1), E, at<float>(W, c->w_u32), (const float*)dqkv, c->NQ,
+                                                at<float>(W, v.t), at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
+                                                at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer), chunks, B, H, N, E, gs));
+        else
+            PROF(c, gs, PEVIT_PROF_LOWRANK_GRAD, T, (double)T * E * 3 * 2 + (double)T * 64 * 8 + (double)chunks * 4 * E * 32 * 4,
+                 pevit_launch_lowrank_grad(at<bf16>(W, v.xn1), E, at<float>(W, c->w_u32), dqkv, c->NQ, at<float>(W, v.t),
+                                           at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
+                                           at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer), chunks, B, H, N, E, gs, c->lowrank_xcd));
+        if (w.use_side) { HIP_OK(hipEventRecord(c->ev_join, c->side)); w.side_pending = true; }
+    }
+    return 0;
+}
+
+// QKV dX of block l: dqkv (incl. the 64 adapter columns u of the attention-site methods) -> the gradient of the attention input.
+// dx_f32 == nullptr: into ws+w_dxn in the block walk's hand-over type (bf16 with dx_stored, for LayerNorm backward); else f32 [T][E].
+int attn_qkv_dx(pevit_ctx* c, hipStream_t s, int B, int l, float* dx_f32) {
+    const int E = c->E, T = B * c->N;
+    float* dxn = at<float>(c->ws, c->w_dxn);
+    GemmParams p = gp(at<bf16>(c->ws, c->w_dqkv), c->NQ, at<bf16>(c->arena, c->blk[l].wqkvT), c->NQ, E, T, E,
+                      attention_site(c) ? c->NQ : 3 * E);
+    if (dx_f32) { p.outf = dx_f32; p.ldo = E; CHECK(gemm(c, EPI_F32, p, s)); }
+    else if (c->dx_stored) { p.outb = reinterpret_cast<bf16*>(dxn); p.ldob = E; CHECK(gemm(c, EPI_BF16, p, s)); }
+    else { p.outf = dxn; p.ldo = E; CHECK(gemm(c, EPI_F32, p, s)); }
+    return 0;
+}
+
+// end of a walk: join the side stream, and the deferred dP of the last layer walked
+int attn_walk_end(pevit_ctx* c, hipStream_t s, int B, AttnGradWalk& w) {
+    const int E = c->E, T = B * c->N, H = c->H, N = c->N;
+    if (w.side_pending) { HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0)); w.side_pending = false; }
+    if (w.combo && w.prev_layer >= 0)       // the dP of the last layer walked
+        PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 2 + (double)T * 64 * 4,
+             pevit_launch_lowrank_combo(0, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at<bf16>(c->ws, c->sav[w.prev_layer].xn1), E,
+                                        w.u_last, at<float>(c->ws, c->w_partial + (size_t)w.prev_layer * c->partial_layer), B, H, N, E, s));
+    w.prev_layer = -1;
+    return 0;
+}
+
 // backward of the blocks.  On entry ws+w_dxa holds dL/dx_final (f32) and ws+w_dyb its bf16 copy.
 // On exit ws+w_dxa holds dL/dx_0 if need_dx0.
 // cls_only mirrors blocks_forward: on entry only the class-token rows of dxa / dyb are defined (and
@@ -763,35 +903,24 @@ bool gstream16_on(const pevit_ctx* c) {
     return post_mlp(c) && c->adapter_fused && !c->fused_bn && pevit_adapter_fused_ok(c->E);
 }
 
+int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, int l_lo, int l_hi);
+
 int blocks_backward(pevit_ctx* c, hipStream_t s, int B, bool need_dx0, bool cls_only, int l_hi, int l_lo) {
-    const int E = c->E, T = B * c->N, H = c->H, N = c->N;
+    const int E = c->E, T = B * c->N, N = c->N;
     cls_only = cls_only && !post_mlp(c);
     char* W = c->ws; char* A = c->arena;
-    const bool site = attention_site(c);
-    const int chunks = pevit_lowrank_chunks(T);
     float* dxa = at<float>(W, c->w_dxa);
     float* dxb = at<float>(W, c->w_dxb);
     bf16* dyb = at<bf16>(W, c->w_dyb);
     float* dxn = at<float>(W, c->w_dxn);
-    bf16* dqkv = at<bf16>(W, c->w_dqkv);
-    const bool use_side = c->side_stream && site;
-    bool side_pending = false;
-    const bool combo = c->lowrank_combo && site && !c->f32 && !use_side;
     const bool gs16 = gstream16_on(c);
-    int prev_layer = -1, u_par = 0;
-    float* u_last = nullptr;
+    AttnGradWalk walk;
+    CHECK(attn_walk_begin(c, walk));
     int tn_pend = -1, tn_par = 0;          // post-MLP adapters: layer whose d W_down product is still owed, and the d pre buffer in turn
     const bf16* tn_pend_dpre = nullptr;
-    if (use_side && !c->side) {
-        HIP_OK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
     for (int l = l_hi - 1; l >= l_lo; --l) {
         const BlockArena& b = c->blk[l];
         const LayerSaved& v = c->sav[l];
-        bf16* qkv = at<bf16>(W, v.qkv);
-        const size_t plane = (size_t)T * E;
         const bf16* mlp_dy = dyb;          // upstream gradient of the MLP output (bf16)
         if (post_mlp(c)) {
             // out = x_mid + h + up(act(down(LN_a(h)))) :  dx_out (dxa, dyb) flows to x_mid, to h, and into the adapter
@@ -886,62 +1015,9 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, bool need_dx0, bool cls_
                                  at<float>(A, b.ln2w), dxa, dxb, dyb, R, E, s, (size_t)rs,
                                  c->fp8 ? at<float>(A, b.so) : nullptr, c->f32, c->dx_stored));
         // ---- attention branch
-        {
-            GemmParams p = gpw(c, dyb, rs, b.woT, E, E, R, E, E, 0);
-            p.outb = at<bf16>(W, c->w_dO); p.ldob = rs;
-            CHECK(gemm(c, EPI_BF16, p, s));
-        }
-        // dqkv / u32 are about to be overwritten: the previous layer's gradient contraction must have read them
-        if (side_pending) { HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0)); side_pending = false; }
-        if (c->f32)
-            CHECK(pevit_launch_attn_bwd_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), (const float*)eadv(c, qkv, 2 * plane),
-                                            at<float>(W, v.attn_out), E, at<float>(W, c->w_dO), E, at<float>(W, v.lse), (float*)dqkv,
-                                            c->NQ, B, H, N, s));
-        else
-            PROF(c, s, PEVIT_PROF_ATTN_BWD, T, (double)T * E * (N <= 64 ? 7 : 8) * 2 + (double)B * H * N * 4,     // q, k, v, (out: N > 64 only), dout in; dq, dk, dv out
-                 pevit_launch_attn_bwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<bf16>(W, c->w_dO), E,
-                                       at<float>(W, v.lse), dqkv, c->NQ, B, H, N, s, (cls && N <= 64) ? 1 : 0));
-        if (site && combo) {
-            // u, dQ_q, dQ_v, d bias of this layer and the dP of the layer before it in ONE launch (lowrank.hip lowrank_combo_kernel)
-            float* u_cur = at<float>(W, u_par ? c->w_u32b : c->w_u32);
-            const LayerSaved* pv = prev_layer >= 0 ? &c->sav[prev_layer] : nullptr;
-            PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 3 * 2 + (double)T * 64 * 14 + (double)chunks * 4 * E * 32 * 4,
-                 pevit_launch_lowrank_combo(1, pv ? 1 : 0, dqkv, c->NQ, at<bf16>(A, b.qT), u_cur, dqkv + 3 * E, at<float>(W, v.t),
-                                            at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
-                                            at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer),
-                                            pv ? at<bf16>(W, pv->xn1) : nullptr, E, u_last,
-                                            pv ? at<float>(W, c->w_partial + (size_t)prev_layer * c->partial_layer) : nullptr, B, H, N, E, s));
-            u_last = u_cur; prev_layer = l; u_par ^= 1;
-        } else if (site) {
-            if (c->f32)
-                CHECK(pevit_launch_lowrank_u_f32((const float*)dqkv, c->NQ, at<float>(A, b.q32), at<float>(W, c->w_u32),
-                                                 (float*)eadv(c, dqkv, 3 * (size_t)E), B, H, N, E, s));
-            else
-                PROF(c, s, PEVIT_PROF_LOWRANK_U, T, (double)T * E * 2 * 2 + (double)T * 64 * 6,
-                     pevit_launch_lowrank_u(dqkv, c->NQ, at<bf16>(A, b.qT), at<float>(W, c->w_u32), dqkv + 3 * E, B, H, N, E, s));
-            // the token-contracted adapter gradients feed nothing before the end of the step: run them beside
-            // the QKV-backward GEMM / LayerNorm backward / next layer's MLP GEMMs on the second stream
-            hipStream_t gs = s;
-            if (use_side) {
-                HIP_OK(hipEventRecord(c->ev_fork, s));
-                HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                gs = c->side;
-            }
-            if (c->f32)
-                CHECK(pevit_launch_lowrank_grad_f32(at<float>(W, v.xn1), E, at<float>(W, c->w_u32), (const float*)dqkv, c->NQ,
-                                                    at<float>(W, v.t), at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
-                                                    at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer), chunks, B, H, N, E, gs));
-            else
-                PROF(c, gs, PEVIT_PROF_LOWRANK_GRAD, T, (double)T * E * 3 * 2 + (double)T * 64 * 8 + (double)chunks * 4 * E * 32 * 4,
-                     pevit_launch_lowrank_grad(at<bf16>(W, v.xn1), E, at<float>(W, c->w_u32), dqkv, c->NQ, at<float>(W, v.t),
-                                               at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
-                                               at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer), chunks, B, H, N, E, gs, c->lowrank_xcd));
-            if (use_side) { HIP_OK(hipEventRecord(c->ev_join, c->side)); side_pending = true; }
-        }
+        CHECK(attn_core_bwd(c, s, B, l, cls, walk));
         if (l > 0 || need_dx0) {
-            GemmParams p = gp(dqkv, c->NQ, at<bf16>(A, b.wqkvT), c->NQ, E, T, E, site ? c->NQ : 3 * E);
-            if (c->dx_stored) { p.outb = reinterpret_cast<bf16*>(dxn); p.ldob = E; CHECK(gemm(c, EPI_BF16, p, s)); }
-            else { p.outf = dxn; p.ldo = E; CHECK(gemm(c, EPI_F32, p, s)); }
+            CHECK(attn_qkv_dx(c, s, B, l, nullptr));
             // fp8: this bf16 copy is the upstream gradient of layer l-1's c_proj backward
             if (gs16)      // the f32 copy only where the caller asked for dx (the lowest block walked)
                 PROF(c, s, PEVIT_PROF_LN_BWD, T, (double)T * E * (c->es + 4 + c->es + c->es),
@@ -957,15 +1033,21 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, bool need_dx0, bool cls_
                                      cls ? N : 0));        // last block, class-token pruning: dxb carries a gradient on the class rows only
         }
     }
-    if (side_pending) HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0));
+    // (the side stream / deferred dP belong to the attention-site methods, the owed d W_down product to the post-MLP ones: at most
+    // one of the two below has work)
+    CHECK(attn_walk_end(c, s, B, walk));
     if (tn_pend >= 0)                   // the d W_down product of the last adapter walked
         CHECK(pevit_launch_tn_gemm64(at<bf16>(W, c->sav[tn_pend].z), E, tn_pend_dpre, 64, at<float>(W, c->w_tnD + (size_t)tn_pend * c->tn_layer),
                                      nullptr, at<float>(W, c->w_csy + (size_t)tn_pend * c->csy_layer), T, E, s));
-    if (combo && prev_layer >= 0)       // the dP of the last layer walked
-        PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 2 + (double)T * 64 * 4,
-             pevit_launch_lowrank_combo(0, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at<bf16>(W, c->sav[prev_layer].xn1), E,
-                                        u_last, at<float>(W, c->w_partial + (size_t)prev_layer * c->partial_layer), B, H, N, E, s));
-    // adapter gradients of layers [l_lo, l_hi): reduce the partials and chain onto the reference's tensors
+    return reduce_adapter_grads(c, s, B, l_lo, l_hi);
+}
+
+// adapter gradients of layers [l_lo, l_hi): reduce the per-layer partials and chain onto the reference's tensors (flat gradient
+// buffer, accumulating)
+int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, int l_lo, int l_hi) {
+    const int E = c->E, T = B * c->N;
+    char* W = c->ws;
+    const int chunks = pevit_lowrank_chunks(T);
     const int nl = l_hi - l_lo;
     const size_t pl0 = c->p_layer0 + c->p_layer_stride * l_lo;          // first float of layer l_lo's parameters
     if (nl <= 0) return 0;
@@ -1039,7 +1121,7 @@ extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("blocks_backward: bad block range [%d, %d)", l_lo, l_hi); return -1; }
     if (c->saved_batch != B || c->saved_kind != 1) {
         pevit_set_error("blocks_backward: the saved activations are not those of a blocks/transformer forward with batch %d "
-                        "(saved: batch %d, %s)", B, c->saved_batch, c->saved_kind == 2 ? "visual_forward" : "none");
+                        "(saved: batch %d, %s)", B, c->saved_batch, saved_name(c));
         return -1;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1052,6 +1134,85 @@ extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy
         CHECK(pevit_launch_cast_bf16(at<float>(c->ws, c->w_dxa), at<bf16>(c->ws, c->w_dyb), n, 1.0f, s, c->f32));
     CHECK(blocks_backward(c, s, B, dx_nbe != nullptr, false, l_hi, l_lo));
     if (dx_nbe) CHECK(pevit_launch_permute_rows(at<float>(c->ws, c->w_dxa), dx_nbe, c->N, B, c->E, 0, s));
+    return 0;
+}
+
+// MultiheadAttention.forward(x, x, x, need_weights, attn_mask=None, average_attn_weights) of block `layer` (model.py:837-944 ->
+// 612-834) on (N,B,E) activations: the attention half of the block walk (the same QKV / delta / attention launches) between a cast of
+// the caller's input into the layer's xn1 slot and out_proj + bias into f32, without the residual.  The layer's saved slots hold
+// the activations; the softmax probabilities are recomputed from q, k and lse (attn_probs.hip) when asked for.
+extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, const float* x_nbe, float* y_nbe, int B,
+                                       int save_for_backward, float* weights, int average_weights) {
+    CHECK(check_ready(c, B, "attention_forward"));
+    if (layer < 0 || layer >= c->L) { pevit_set_error("attention_forward: layer %d outside [0, %d)", layer, c->L); return -1; }
+    if (c->fp8act) {
+        pevit_set_error("attention_forward: weight format fp8-act is not supported by the attention seam (its e4m3 activation codes "
+                        "come out of the LayerNorm kernel, which the seam does not run): use bf16, fp8 or f32-verify");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    size_t total; layout_workspace(c, B, c->sav, &total, c);
+    const int E = c->E, N = c->N, T = B * N;
+    char* W = c->ws; char* A = c->arena;
+    const BlockArena& b = c->blk[layer];
+    const LayerSaved& v = c->sav[layer];
+    float* xin = at<float>(W, c->w_dxn);          // [T][E] f32 scratch (free in a forward pass)
+    float* yout = at<float>(W, c->w_dxa);
+    CHECK(pevit_launch_permute_rows(x_nbe, xin, N, B, E, 1, s));
+    CHECK(pevit_launch_cast_bf16(xin, at<bf16>(W, v.xn1), (size_t)T * E, 1.0f, s, c->f32));
+    if (attention_site(c)) CHECK(prep_adapters(c, s));
+    CHECK(attn_core_fwd(c, s, B, layer, nullptr, nullptr));
+    if (weights) {
+        const bf16* qkv = at<bf16>(W, v.qkv);
+        const size_t plane = (size_t)T * E;
+        if (c->f32)
+            CHECK(pevit_launch_attn_probs_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), at<float>(W, v.lse), weights, B, c->H,
+                                              N, average_weights ? 1 : 0, s));
+        else
+            CHECK(pevit_launch_attn_probs(qkv, qkv + plane, at<float>(W, v.lse), weights, B, c->H, N, average_weights ? 1 : 0, s));
+    }
+    {
+        GemmParams p = gpw(c, at<bf16>(W, v.attn_out), E, b.wo, E, E, T, E, E, b.so);
+        p.bias = at<float>(A, b.bo); p.outf = yout; p.ldo = E;
+        CHECK(gemm(c, EPI_BIAS_F32, p, s));
+    }
+    CHECK(pevit_launch_permute_rows(yout, y_nbe, N, B, E, 0, s));
+    c->saved_batch = save_for_backward ? B : 0; c->saved_kind = 3; c->saved_layer = layer;
+    return 0;
+}
+
+// dy (gradient of out_proj's output) -> dx (gradient of the attention input, may be NULL); the adapter gradients of `layer` are
+// accumulated into the flat gradient buffer exactly as pevit_blocks_backward over [layer, layer + 1) does (incl. its share of the
+// shared phm_rule factors).  Adapter / Compacter / the frozen tower: stock attention with frozen weights, dx only.
+extern "C" int pevit_attention_backward(pevit_ctx* c, void* stream, int layer, const float* dy_nbe, float* dx_nbe, int B) {
+    CHECK(check_ready(c, B, "attention_backward"));
+    if (layer < 0 || layer >= c->L) { pevit_set_error("attention_backward: layer %d outside [0, %d)", layer, c->L); return -1; }
+    if (c->saved_batch != B || c->saved_kind != 3 || c->saved_layer != layer) {
+        char what[64];
+        if (c->saved_kind == 3) snprintf(what, sizeof(what), "attention_forward of layer %d", c->saved_layer);
+        else snprintf(what, sizeof(what), "%s", saved_name(c));
+        pevit_set_error("attention_backward: the saved activations are not those of an attention_forward of layer %d with batch %d "
+                        "(saved: batch %d, %s)", layer, B, c->saved_batch, what);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int E = c->E, N = c->N, T = B * N;
+    char* W = c->ws;
+    float* dy = at<float>(W, c->w_dxa);
+    CHECK(pevit_launch_permute_rows(dy_nbe, dy, N, B, E, 1, s));
+    // fp8: out_proj's channel scales ride on the A operand of its dX product (as LayerNorm backward leaves them in the block walk)
+    if (c->fp8)
+        CHECK(pevit_launch_cast_bf16_cols(dy, at<bf16>(W, c->w_dyb), (size_t)T, E, at<float>(c->arena, c->blk[layer].so), s));
+    else
+        CHECK(pevit_launch_cast_bf16(dy, at<bf16>(W, c->w_dyb), (size_t)T * E, 1.0f, s, c->f32));
+    AttnGradWalk walk;
+    CHECK(attn_walk_begin(c, walk));
+    CHECK(attn_core_bwd(c, s, B, layer, false, walk));
+    float* dx = at<float>(W, c->w_dxb);
+    if (dx_nbe) CHECK(attn_qkv_dx(c, s, B, layer, dx));
+    CHECK(attn_walk_end(c, s, B, walk));
+    if (attention_site(c)) CHECK(reduce_adapter_grads(c, s, B, layer, layer + 1));
+    if (dx_nbe) CHECK(pevit_launch_permute_rows(dx, dx_nbe, N, B, E, 0, s));
     return 0;
 }
 
@@ -1196,7 +1357,7 @@ extern "C" int pevit_visual_backward_part(pevit_ctx* c, void* stream, const floa
     CHECK(check_ready(c, B, "visual_backward"));
     if (c->saved_batch != B || c->saved_kind != 2) {
         pevit_set_error("visual_backward: the saved activations are not those of a visual_forward with batch %d (saved: batch %d, %s)",
-                        B, c->saved_batch, c->saved_kind == 1 ? "transformer_forward" : "none");
+                        B, c->saved_batch, saved_name(c));
         return -1;
     }
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("visual_backward: bad layer range [%d, %d)", l_lo, l_hi); return -1; }
@@ -1479,6 +1640,10 @@ extern "C" int pevit_debug_occupy(void* stream, int workgroups, int lds_bytes, d
 }
 extern "C" int pevit_debug_timeline(void* buf) { pevit_attn_delta_set_timeline(buf); return 0; }
 extern "C" int pevit_op_attn_delta_hpw(int B, int H, int N) { return pevit_attn_delta_hpw(B, H, N); }
+extern "C" int pevit_op_attn_probs(void* stream, const void* q, const void* k, const float* lse, float* out, int B, int H, int N,
+                                   int average) {
+    return pevit_launch_attn_probs((const bf16*)q, (const bf16*)k, lse, out, B, H, N, average, (hipStream_t)stream);
+}
 extern "C" int pevit_op_lowrank_u(void* stream, const void* dqkv, int ld, const void* qT, float* u32, void* u_cols, int B,
                                   int H, int N, int E) {
     return pevit_launch_lowrank_u((const bf16*)dqkv, ld, (const bf16*)qT, u32, (bf16*)u_cols, B, H, N, E,

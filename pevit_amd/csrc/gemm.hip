@@ -1970,6 +1970,7 @@ int pevit_launch_gemm(int epi, const GemmParams& p_in, const GemmTune& t, hipStr
             case EPI_DGELU_BF16: return launch_epi<EPI_DGELU_BF16, true>(p, t, stream);
             case EPI_F32: return launch_epi<EPI_F32, true>(p, t, stream);
             case EPI_BF16: return launch_epi<EPI_BF16, true>(p, t, stream);
+            case EPI_BIAS_F32: return launch_epi<EPI_BIAS_F32, true>(p, t, stream);
         }
         pevit_set_error("gemm: epilogue %d has no fp8-weight form", epi);
         return -1;
@@ -1988,6 +1989,7 @@ int pevit_launch_gemm(int epi, const GemmParams& p_in, const GemmTune& t, hipStr
         case EPI_BIAS_GELUNEW: return launch_epi<EPI_BIAS_GELUNEW, false>(p, t, stream);
         case EPI_DRELU_BF16: return launch_epi<EPI_DRELU_BF16, false>(p, t, stream);
         case EPI_DGELUNEW_BF16: return launch_epi<EPI_DGELUNEW_BF16, false>(p, t, stream);
+        case EPI_BIAS_F32: return launch_epi<EPI_BIAS_F32, false>(p, t, stream);
     }
     pevit_set_error("gemm: unknown epilogue %d", epi);
     return -1;

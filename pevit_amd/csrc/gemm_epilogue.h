@@ -187,6 +187,9 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int row, int
         epilogue_store_aux<EPI, ST>(p, row, col, v, h);
     } else if constexpr (EPI == EPI_F32) {
         store8f(p.outf + (size_t)row * p.ldo + col, v);
+    } else if constexpr (EPI == EPI_BIAS_F32) {
+        add8(v, p.bias + col);
+        store8f(p.outf + (size_t)row * p.ldo + col, v);
     } else if constexpr (EPI == EPI_BF16) {
         store8s<ST>(p.outb, (size_t)row * p.ldob + col, v);
     } else if constexpr (EPI == EPI_BIAS_BF16) {
@@ -230,7 +233,8 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int row, int
 // in vmcnt, in order.  On these tiles that was one store latency per 16-row pass.)
 template <int EPI> constexpr bool epi_reads_resid = (EPI == EPI_BIAS_RESID_F32 || EPI == EPI_BIAS_RESID_KEEP || EPI == EPI_PATCH_EMBED);
 template <int EPI> constexpr bool epi_has_bias = (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID_F32 || EPI == EPI_BIAS_RESID_KEEP ||
-                                                  EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_GELUNEW || EPI == EPI_BIAS_RELU_BF16);
+                                                  EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_GELUNEW || EPI == EPI_BIAS_RELU_BF16 ||
+                                                  EPI == EPI_BIAS_F32);
 struct EpiOperand { float4 r0, r1; bf16x8 a; };
 
 // column constants of columns col..col+7 (col < N): bias where the epilogue has one, the dGELU channel scale, else unused
@@ -286,6 +290,10 @@ __device__ __forceinline__ void epilogue_store_full(const GemmParams& p, int row
         v[0] += o.r0.x; v[1] += o.r0.y; v[2] += o.r0.z; v[3] += o.r0.w; v[4] += o.r1.x; v[5] += o.r1.y; v[6] += o.r1.z; v[7] += o.r1.w;
         store8f(p.outf + ((size_t)b * p.Ntok + 1 + g) * p.ldo + col, v);
     } else if constexpr (EPI == EPI_F32) {
+        store8f(p.outf + (size_t)row * p.ldo + col, v);
+    } else if constexpr (EPI == EPI_BIAS_F32) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] += c[i];
         store8f(p.outf + (size_t)row * p.ldo + col, v);
     } else if constexpr (EPI == EPI_BF16) {
         store8s<ST>(p.outb, (size_t)row * p.ldob + col, v);

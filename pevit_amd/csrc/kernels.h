@@ -16,6 +16,7 @@ enum GemmEpilogue {
     EPI_BIAS_GELUNEW = 10,   // a = acc + bias (bf16, saved) ; g = gelu_new(a) (bf16)
     EPI_DRELU_BF16 = 11,     // out_bf16 = acc * (aux > 0)
     EPI_DGELUNEW_BF16 = 12,  // out_bf16 = acc * gelu_new'(aux)
+    EPI_BIAS_F32 = 13,       // out_f32 = acc + bias   (MultiheadAttention.forward: out_proj without the block's residual)
 };
 
 struct GemmParams {
@@ -103,6 +104,11 @@ int pevit_launch_attn_bwd(const bf16* q, const bf16* k, const bf16* v, const bf1
                           const bf16* dout, int lddo, const float* lse, bf16* dqkv, int ld,
                           int B, int H, int N, hipStream_t s, int dout_cls_only = 0);   // dout_cls_only (N <= 64): dout is zero except on token 0 of every image; the other rows are not read
 
+// ---- attn_probs.hip ---------------------------------------------------------------
+// softmax probabilities P = exp(q k^T - lse) of the attention core (q, k: (B*H, N, 64) bf16 as attn_fwd takes them, lse as it
+// wrote it): average = 1 -> out (B, N, N) f32 = mean over the H heads; 0 -> out (B, H, N, N) f32
+int pevit_launch_attn_probs(const bf16* q, const bf16* k, const float* lse, float* out, int B, int H, int N, int average, hipStream_t s);
+
 // ---- attn_delta.hip (attention-site adapters fused with the attention core, N <= 64) --------------
 // heads per workgroup of the fused forms for this geometry, or 0 when there is none (the two-kernel path is used)
 int pevit_attn_delta_hpw(int B, int H, int N);
@@ -189,6 +195,8 @@ int pevit_launch_attn_fwd_f32(const float* q, const float* k, const float* v, fl
                               hipStream_t s);
 int pevit_launch_attn_bwd_f32(const float* q, const float* k, const float* v, const float* out, int ldo, const float* dout,
                               int lddo, const float* lse, float* dqkv, int ld, int B, int H, int N, hipStream_t s);
+int pevit_launch_attn_probs_f32(const float* q, const float* k, const float* lse, float* out, int B, int H, int N, int average,
+                                hipStream_t s);
 int pevit_launch_lowrank_u_f32(const float* dqkv, int ld, const float* q32, float* u32, float* ucols, int B, int H, int N, int E,
                                hipStream_t s);
 // G[e][j] = sum_r X[r][e] Y[r][j], partial / column-sum layout of tn_gemm64 (adapter.hip)

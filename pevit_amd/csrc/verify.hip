@@ -110,6 +110,29 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
     }
 }
 
+// attention probabilities (attn_probs.hip) in f32: one thread per (image, query, key), S = q . k over d = 64, P = exp(S - lse),
+// summed over the heads in order and divided by H (average), or stored per head
+__global__ __launch_bounds__(256) void attn_probs_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                             const float* __restrict__ lse, float* __restrict__ out, int B, int H, int N,
+                                                             int average) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)B * N * N) return;
+    const int col = (int)(idx % N), row = (int)((idx / N) % N), b = (int)(idx / ((size_t)N * N));
+    float sum = 0.f;
+    for (int h = 0; h < H; ++h) {
+        const size_t bh = (size_t)b * H + h;
+        const float* qi = q + (bh * N + row) * 64;
+        const float* kj = k + (bh * N + col) * 64;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < 64; ++d) s = fmaf(qi[d], kj[d], s);
+        const float p = expf(s - lse[bh * N + row]);
+        if (average) sum += p;
+        else out[(bh * N + row) * N + col] = p;
+    }
+    if (average) out[idx] = sum / (float)H;
+}
+
 __global__ __launch_bounds__(256) void attn_bwd_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v, const float* __restrict__ out, int ldo,
                                                            const float* __restrict__ dout, int lddo,
@@ -285,6 +308,7 @@ int pevit_launch_gemm_f32(int epi, const GemmParams& p, hipStream_t s) {
         case EPI_BIAS_GELUNEW: return launch_f32<EPI_BIAS_GELUNEW>(p, s);
         case EPI_DRELU_BF16: return launch_f32<EPI_DRELU_BF16>(p, s);
         case EPI_DGELUNEW_BF16: return launch_f32<EPI_DGELUNEW_BF16>(p, s);
+        case EPI_BIAS_F32: return launch_f32<EPI_BIAS_F32>(p, s);
     }
     pevit_set_error("gemm (f32 verification): unknown epilogue %d", epi);
     return -1;
@@ -303,6 +327,15 @@ int pevit_launch_attn_bwd_f32(const float* q, const float* k, const float* v, co
     if (N < 1 || N > 320) { pevit_set_error("attn_bwd (f32 verification): N=%d outside [1,320]", N); return -1; }
     hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(B * H), dim3(256), 0, s, q, k, v, out, ldo, dout, lddo, lse, dqkv, ld, H, N);
     LAUNCH_OK("attn_bwd_f32_kernel");
+    return 0;
+}
+
+int pevit_launch_attn_probs_f32(const float* q, const float* k, const float* lse, float* out, int B, int H, int N, int average,
+                                hipStream_t s) {
+    if (N < 1 || N > 384) { pevit_set_error("attn_probs (f32 verification): N=%d outside [1,384]", N); return -1; }
+    const size_t n = (size_t)B * N * N;
+    hipLaunchKernelGGL(attn_probs_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, k, lse, out, B, H, N, average);
+    LAUNCH_OK("attn_probs_f32_kernel");
     return 0;
 }
 

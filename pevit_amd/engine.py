@@ -117,6 +117,7 @@ class HipEngine:
         self._steps = 0
         self.forward_generation = 0      # bumped by EVERY forward: each one overwrites the single activation workspace
         self.block_generation = {}       # per block: bumped by every forward THROUGH that block (blocks keep their own activations)
+        self.attention_generation = {}   # per block: the block_generation its last attention_forward left (attention seam)
         self._logits = torch.empty((max_batch, num_classes), dtype=torch.float32, device=self.device)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
 
@@ -272,6 +273,45 @@ class HipEngine:
         dx = torch.empty_like(dy) if need_dx else None
         _lib.check(self.lib.pevit_blocks_backward(self._ctx, _lib.stream_ptr(), _lib.ptr(dy), _lib.ptr(dx), B, l_lo, l_hi),
                    "pevit_blocks_backward")
+        return dx
+
+    def attention_forward(self, x_nbe: torch.Tensor, layer: int, save: bool = True, weights: str | None = None):
+        """MultiheadAttention.forward(x, x, x) of block ``layer`` (the reference's resblocks[layer].attn, model.py:837-944) on the
+        attention INPUT x (N,B,E): returns (out_proj output without the residual, weights or None).  ``weights``: None
+        (need_weights=False), "mean" ((B,N,N) head average) or "heads" ((B,H,N,N))."""
+        self.dp_flush()
+        N, B, E = x_nbe.shape
+        if (N, E) != (self.arch.tokens, self.arch.width) or x_nbe.device != self.device:
+            raise _lib.PevitError(f"attention_forward expects ({self.arch.tokens}, B, {self.arch.width}) on {self.device}, "
+                                  f"got {tuple(x_nbe.shape)} on {x_nbe.device}")
+        if not 0 <= layer < self.arch.layers:
+            raise _lib.PevitError(f"attention_forward: layer {layer} outside [0, {self.arch.layers})")
+        if weights not in (None, "mean", "heads"):
+            raise ValueError(f"weights={weights!r}: expected None, 'mean' or 'heads'")
+        # the seam's activations live in the layer's saved slots: a pending backward through the tower or through this block is
+        # no longer possible
+        self.forward_generation += 1
+        self.block_generation[layer] = self.block_generation.get(layer, 0) + 1
+        self.attention_generation[layer] = self.block_generation[layer]
+        x = x_nbe.contiguous().float()
+        y = torch.empty_like(x)
+        w = None
+        if weights == "mean":
+            w = torch.empty((B, N, N), dtype=torch.float32, device=self.device)
+        elif weights == "heads":
+            w = torch.empty((B, self.arch.heads, N, N), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pevit_attention_forward(self._ctx, _lib.stream_ptr(), layer, _lib.ptr(x), _lib.ptr(y), B, int(save),
+                                                    _lib.ptr(w), int(weights != "heads")), "pevit_attention_forward")
+        return y, w
+
+    def attention_backward(self, dy_nbe: torch.Tensor, layer: int, need_dx: bool = True):
+        """dy (N,B,E) of the attention output -> dx of its input; accumulates the adapter gradients of ``layer`` into ``grads``."""
+        self.dp_flush()
+        N, B, E = dy_nbe.shape
+        dy = dy_nbe.contiguous().float()
+        dx = torch.empty_like(dy) if need_dx else None
+        _lib.check(self.lib.pevit_attention_backward(self._ctx, _lib.stream_ptr(), layer, _lib.ptr(dy), _lib.ptr(dx), B),
+                   "pevit_attention_backward")
         return dx
 
     def transformer_backward(self, dy_nbe: torch.Tensor, need_dx: bool = True):

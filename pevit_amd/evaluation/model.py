@@ -73,11 +73,13 @@ class _TextTransformer(nn.Module):
 class _Params(nn.Module):
     """Named container: holds parameters / sub-containers under the reference's attribute names."""
 
+    _children = {}        # attribute name -> container class of that child (default: _Params)
+
     def add(self, name, tensor, trainable=False):
         head, _, rest = name.partition(".")
         if rest:
             if head not in self._modules:
-                self.add_module(head, _Params())
+                self.add_module(head, self._children.get(head, _Params)())
             self._modules[head].add(rest, tensor, trainable)
         else:
             self.register_parameter(head, nn.Parameter(tensor, requires_grad=trainable))
@@ -197,9 +199,79 @@ class _BlockFn(torch.autograd.Function):
         return (dx, None, None, None, *grads)
 
 
+class _AttentionFn(torch.autograd.Function):
+    """MultiheadAttention.forward(x, x, x) of block ``index`` (model.py:837-944) on the engine (pevit_attention_forward / _backward):
+    the attention output (without the block's residual) and, when asked for, the softmax weights.  The weights carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, visual, index, save, weights, *params):
+        eng = visual._engine
+        y, w = eng.attention_forward(x, index, save=save, weights=weights)
+        ctx.set_materialize_grads(False)
+        ctx.visual, ctx.index, ctx.generation, ctx.need_dx = visual, index, eng.block_generation[index], x.requires_grad
+        ctx.shape = tuple(x.shape)
+        if w is None:
+            w = x.new_empty(0)
+            ctx.mark_non_differentiable(w)
+        return y, w
+
+    @staticmethod
+    def backward(ctx, dy, dw):
+        if dw is not None:
+            raise _lib.PevitError("no gradient through attention weights: the HIP engine returns the softmax weights of "
+                                  "resblocks[i].attn for inspection only (detach them before they enter a loss)")
+        eng = ctx.visual._engine
+        if eng.block_generation.get(ctx.index) != ctx.generation or eng.attention_generation.get(ctx.index) != ctx.generation:
+            raise _lib.PevitError(f"backward through resblocks[{ctx.index}].attn whose activations the engine no longer holds: another "
+                                  "forward through this block ran in between")
+        if dy is None:
+            dy = torch.zeros(ctx.shape, dtype=torch.float32, device=eng.device)
+        eng.grads[:eng.n_tower].zero_()
+        dx = eng.attention_backward(dy, ctx.index, need_dx=ctx.need_dx)
+        views = eng.param_views(eng.grads.clone())
+        mask = ctx.visual._has_grad
+        grads = [views["visual." + n] if mask[n] else None for n in ctx.visual._trainable_names]
+        return (dx, None, None, None, None, *grads)
+
+
+class _Attention(_Params):
+    """visual.transformer.resblocks[i].attn: the reference's MultiheadAttention (model.py:612-944) -- its parameters under the
+    reference's names, callable as ``attn(x, x, x)`` for self-attention on (N, B, E) activations of this tower.  Returns
+    ``(out_proj output, weights)`` like the reference: weights (B, N, N) averaged over the heads, (B, H, N, N) with
+    ``average_attn_weights=False``, None with ``need_weights=False``.  Cross-attention, masks and a gradient through the weights
+    are not supported and raise; there is no PyTorch fallback."""
+    batch_first = False
+
+    def forward(self, query, key, value, key_padding_mask=None, need_weights=True, attn_mask=None, average_attn_weights=True):
+        def same(a, b):
+            return a is b or (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.device == b.device and
+                              a.dtype == b.dtype and a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride())
+        if not (same(query, key) and same(key, value)):
+            raise _lib.PevitError("resblocks[i].attn: query, key and value must be the same tensor (self-attention); the HIP "
+                                  "engine has no cross-attention")
+        if attn_mask is not None:
+            raise _lib.PevitError("resblocks[i].attn: attn_mask must be None (the vision tower has no attention mask; the HIP engine "
+                                  "does not implement one)")
+        if key_padding_mask is not None:
+            raise _lib.PevitError("resblocks[i].attn: key_padding_mask must be None (the HIP engine does not implement one)")
+        visual = self._owner()
+        N = visual.arch.tokens
+        if query.dim() != 3 or query.shape[0] != N or query.shape[2] != self.embed_dim:
+            raise _lib.PevitError(f"resblocks[i].attn: the input must be 3-D (N, B, E) = ({N}, B, {self.embed_dim}) "
+                                  f"(sequence first, batch_first=False), got {tuple(query.shape)}")
+        eng = visual.engine()
+        eng.ensure_batch(query.shape[1])
+        params = visual._trainable_params()
+        save = torch.is_grad_enabled() and (query.requires_grad or any(p.requires_grad for p in params))
+        mode = ("mean" if average_attn_weights else "heads") if need_weights else None
+        y, w = _AttentionFn.apply(query.contiguous().float(), visual, self._index, save, mode, *params)
+        return y, (w if need_weights else None)
+
+
 class _Block(_Params):
     """visual.transformer.resblocks[i]: parameters under the reference's names, callable like the reference's
     ResidualAttentionBlock (reference-side code that walks ``resblocks`` keeps working; the whole-tower call is one engine op)."""
+    _children = {"attn": _Attention}
 
     def forward(self, x):
         visual = self._owner()
@@ -312,6 +384,9 @@ class VisionTransformer(nn.Module):
                 else:
                     s, tr = shapes[pre + n]
                     blk.add(n, torch.zeros(s), tr)
+            object.__setattr__(blk.attn, "_owner", weakref.ref(self))
+            object.__setattr__(blk.attn, "_index", i)
+            blk.attn.embed_dim, blk.attn.num_heads = E, arch.heads
             self.transformer.resblocks.add_module(str(i), blk)
         self.ln_post = _Params(); self.ln_post.add("weight", torch.ones(E)); self.ln_post.add("bias", torch.zeros(E))
         self._has_grad = {n: True for n in self._trainable_names}

@@ -2,8 +2,9 @@
 # rocprofv3 passes behind bench.py's roofline object: kernel trace + stats, HBM-side traffic (FETCH_SIZE and WRITE_SIZE in
 # separate passes, each self-calibrated on a known 1 GiB stream), and matrix-core utilisation (SQ_VALU_MFMA_BUSY_CYCLES).
 # PMC passes carry --kernel-trace only (gpurun refuses PMC combined with the API trace domains).
-# usage (on the GPU box, from the repo root):  bash scripts/run_pmc_passes.sh [tag]
-set -x
+# usage (on the GPU box, from the repo root, under an outer time limit):  timeout 3000 bash scripts/run_pmc_passes.sh [tag]
+# Stops at the first failing step: a failed or timed-out pass leaves no half-refreshed profile behind and starts nothing more.
+set -ex
 export TMPDIR=/tmp
 R=$PWD
 TAG=${1:-r06}
