@@ -1702,41 +1702,28 @@ extern "C" int pevit_op_im2col(void* stream, const float* images, void* patches_
     return pevit_launch_im2col(images, (bf16*)patches_bf16, B, R, P, Kpad, (hipStream_t)stream);
 }
 extern "C" int pevit_tune(pevit_ctx* c, const char* key, int value) {
+    static const struct { const char* key; int GemmTune::*field; } gemm_keys[] = {
+        {"gemm_config", &GemmTune::config}, {"gemm_persistent", &GemmTune::persistent}, {"gemm_ablate", &GemmTune::ablate},
+        {"gemm_kswitch", &GemmTune::kswitch}, {"gemm_big", &GemmTune::big}, {"gemm_cfg_longk", &GemmTune::cfg_longk},
+        {"gemm_cfg_shortk", &GemmTune::cfg_shortk}, {"gemm_big_bias", &GemmTune::big_bias}, {"gemm_streamk", &GemmTune::streamk},
+        {"gemm_sk_share", &GemmTune::sk_share}, {"gemm_sk_band", &GemmTune::sk_band}, {"gemm_ksplit", &GemmTune::ksplit},
+        {"gemm_ksplit_small", &GemmTune::ksplit_small}, {"gemm_ksplit_stagger", &GemmTune::ksplit_stagger},
+        {"gemm_ksplit_mink", &GemmTune::ksplit_mink}, {"gemm_kphase_nl", &GemmTune::kphase_nl}, {"gemm_kz2", &GemmTune::kz2},
+        {"gemm_skinny", &GemmTune::skinny}, {"gemm_skinny_maxm", &GemmTune::skinny_maxm}, {"gemm_skinny_mink", &GemmTune::skinny_mink},
+        {"gemm_skinny_slices", &GemmTune::skinny_slices}, {"gemm_band", &GemmTune::band}, {"gemm_stagger", &GemmTune::stagger},
+    };
+    // these need a context
+    static const struct { const char* key; int pevit_ctx::*field; } ctx_keys[] = {
+        {"side_stream", &pevit_ctx::side_stream}, {"fused_bottleneck", &pevit_ctx::fused_bn}, {"dx_stored", &pevit_ctx::dx_stored},
+        {"gstream_bf16", &pevit_ctx::gstream16}, {"profile_all", &pevit_ctx::prof_all}, {"fused_attn_delta", &pevit_ctx::fused_attn_delta},
+        {"fp8_tail", &pevit_ctx::fp8_tail}, {"adapter_fused", &pevit_ctx::adapter_fused}, {"adapter_tn_fold", &pevit_ctx::adapter_tn_fold},
+        {"lowrank_combo", &pevit_ctx::lowrank_combo}, {"lowrank_xcd", &pevit_ctx::lowrank_xcd},
+    };
     GemmTune& t = c ? c->tune : g_default_tune;
-    if (key && !strcmp(key, "gemm_config")) { t.config = value; return 0; }
-    if (key && !strcmp(key, "gemm_persistent")) { t.persistent = value; return 0; }
-    if (key && !strcmp(key, "gemm_ablate")) { t.ablate = value; return 0; }
-    if (key && !strcmp(key, "gemm_kswitch")) { t.kswitch = value; return 0; }
-    if (key && !strcmp(key, "gemm_big")) { t.big = value; return 0; }
-    if (key && !strcmp(key, "gemm_cfg_longk")) { t.cfg_longk = value; return 0; }
-    if (key && !strcmp(key, "gemm_cfg_shortk")) { t.cfg_shortk = value; return 0; }
-    if (key && !strcmp(key, "gemm_big_bias")) { t.big_bias = value; return 0; }
-    if (key && c && !strcmp(key, "side_stream")) { c->side_stream = value; return 0; }
-    if (key && c && !strcmp(key, "fused_bottleneck")) { c->fused_bn = value; return 0; }
-    if (key && !strcmp(key, "gemm_streamk")) { t.streamk = value; return 0; }
-    if (key && !strcmp(key, "gemm_sk_share")) { t.sk_share = value; return 0; }
-    if (key && !strcmp(key, "gemm_sk_band")) { t.sk_band = value; return 0; }
-    if (key && !strcmp(key, "gemm_ksplit")) { t.ksplit = value; return 0; }
-    if (key && !strcmp(key, "gemm_ksplit_small")) { t.ksplit_small = value; return 0; }
-    if (key && !strcmp(key, "gemm_ksplit_stagger")) { t.ksplit_stagger = value; return 0; }
-    if (key && !strcmp(key, "gemm_ksplit_mink")) { t.ksplit_mink = value; return 0; }
-    if (key && !strcmp(key, "gemm_kphase_nl")) { t.kphase_nl = value; return 0; }
-    if (key && !strcmp(key, "gemm_kz2")) { t.kz2 = value; return 0; }
-    if (key && !strcmp(key, "gemm_skinny")) { t.skinny = value; return 0; }
-    if (key && !strcmp(key, "gemm_skinny_maxm")) { t.skinny_maxm = value; return 0; }
-    if (key && !strcmp(key, "gemm_skinny_mink")) { t.skinny_mink = value; return 0; }
-    if (key && !strcmp(key, "gemm_skinny_slices")) { t.skinny_slices = value; return 0; }
-    if (key && !strcmp(key, "gemm_band")) { t.band = value; return 0; }
-    if (key && !strcmp(key, "gemm_stagger")) { t.stagger = value; return 0; }
-    if (key && c && !strcmp(key, "dx_stored")) { c->dx_stored = value; return 0; }
-    if (key && c && !strcmp(key, "gstream_bf16")) { c->gstream16 = value; return 0; }
-    if (key && c && !strcmp(key, "profile_all")) { c->prof_all = value; return 0; }
-    if (key && c && !strcmp(key, "fused_attn_delta")) { c->fused_attn_delta = value; return 0; }
-    if (key && c && !strcmp(key, "fp8_tail")) { c->fp8_tail = value; return 0; }
-    if (key && c && !strcmp(key, "adapter_fused")) { c->adapter_fused = value; return 0; }
-    if (key && c && !strcmp(key, "adapter_tn_fold")) { c->adapter_tn_fold = value; return 0; }
-    if (key && c && !strcmp(key, "lowrank_combo")) { c->lowrank_combo = value; return 0; }
-    if (key && c && !strcmp(key, "lowrank_xcd")) { c->lowrank_xcd = value; return 0; }
+    for (const auto& k : gemm_keys)
+        if (key && !strcmp(key, k.key)) { t.*k.field = value; return 0; }
+    for (const auto& k : ctx_keys)
+        if (key && c && !strcmp(key, k.key)) { c->*k.field = value; return 0; }
     pevit_set_error("tune: unknown key %s", key ? key : "(null)");
     return -1;
 }

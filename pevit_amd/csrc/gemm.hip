@@ -33,7 +33,10 @@
 //
 // Epilogue: accumulators are transposed through LDS, one 32x32 fragment per wave at a time, so
 // that global accesses are 16/32-byte-per-lane row segments.
+#include <cstdarg>
+#include <cstdio>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "kernels.h"
@@ -1558,6 +1561,9 @@ __global__ __launch_bounds__(512, 2) void gemm_kphase_kernel(GemmParams p, int n
   }
 }
 
+
+// ---- host: plan_gemm decides which kernel runs and how; the launchers below it map a plan onto its kernel instantiation
+
 // band height (m-tiles) that hands every XCD whole bands: tiles / 8 consecutive tile indices per XCD (xcd_remap) = k bands of
 // tiles_n * band tiles.  0 = keep TILE_BAND (several rounds, or no even split).
 int xcd_band(int tiles, int tiles_n, int grid, const GemmTune& t) {
@@ -1569,61 +1575,30 @@ int xcd_band(int tiles, int tiles_n, int grid, const GemmTune& t) {
     return 0;
 }
 
-template <int EPI, int WGM, int WGN, int WM, int WN, bool STAG>
-int launch_ksplit(const GemmParams& p, const GemmTune& t, hipStream_t stream) {
-    constexpr int bm = WGM * WM * 32, bn = WGN * WN * 32, stage = (bm + bn) * 128;
-    constexpr int scratch_end = 3 * stage + 2 * WGM * WGN * 4096;
-    constexpr int lds = 4 * stage > scratch_end ? 4 * stage : scratch_end;
-    auto kern = gemm_ksplit_kernel<EPI, WGM, WGN, WM, WN, STAG>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            pevit_set_error("hipFuncSetAttribute(k-split gemm epi %d) failed", EPI);
-            return -1;
-        }
-        attr_set = true;
-    }
-    const int tiles = ceil_div(p.M, bm) * ceil_div(p.N, bn);
-    const int grid = min(tiles, num_cus() & ~7);
-    GemmParams pb = p;
-    pb.band = xcd_band(tiles, ceil_div(p.N, bn), grid, t);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(2 * WGM * WGN * 64), lds, stream, pb, tiles);
-    LAUNCH_OK("gemm (k-split)");
-    g_last_path = 3;
-    return 0;
-}
-
 // floats of stream-K workspace a two-slice launch needs: two slabs per tile (ksplit_finish: 8 waves x ceil(WM / 2) fragments x 1024)
 constexpr long kz_slab_floats(int wm) { return 2L * 8 * ((wm + 1) / 2) * 1024; }
 
-template <int EPI, int WM, int NL, bool KZ = false>
-int launch_kphase(const GemmParams& p, const GemmTune& t, hipStream_t stream) {
-    constexpr int bm = WM * 32, bn = 128, stage = (bm + bn) * 128;
-    constexpr int scratch = 3 * stage > 4 * WM * 4096 ? 3 * stage : 4 * WM * 4096;
-    constexpr int lds = 4 * stage > scratch + 8 * 4096 ? 4 * stage : scratch + 8 * 4096;
-    auto kern = gemm_kphase_kernel<EPI, WM, NL, KZ>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            pevit_set_error("hipFuncSetAttribute(phased k-split gemm epi %d) failed", EPI);
-            return -1;
-        }
-        attr_set = true;
-    }
-    const long long a = ((long long)p.M * p.lda + p.K) * 2, b = ((long long)p.Nb * p.ldb + p.K) * 2;
-    if (a >= (1LL << 31) || b >= (1LL << 31)) return launch_ksplit<EPI, 1, 4, WM, 1, true>(p, t, stream);   // 31-bit buffer offsets
-    const int tiles = ceil_div(p.M, bm) * ceil_div(p.N, bn);
-    const int grid = min(KZ ? 2 * tiles : tiles, num_cus() & ~7);
-    GemmParams pb = p;
-    pb.band = xcd_band(tiles, ceil_div(p.N, bn), min(tiles, grid), t);
-    pb.kz = KZ ? 2 : 0;
-    if (KZ && (!p.sk_slab || !p.sk_flag || tiles > p.sk_slots || tiles * kz_slab_floats(WM) > (long)p.sk_slots * PEVIT_SK_SLAB_FLOATS)) {
-        pevit_set_error("gemm (two K slices per tile): the stream-K workspace is missing or too small for %d tiles", tiles); return -1;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, pb, tiles);
-    LAUNCH_OK("gemm (phased k-split)");
-    g_last_path = KZ ? 7 : 4;
-    return 0;
+int sk_slots(int cus) { return min(2 * cus, PEVIT_SK_MAX_SLOTS) & ~7; }
+
+// buffer descriptors address an operand with 31-bit byte offsets: bytes from its base to the end of its last row
+constexpr long long kMaxOffset = 1LL << 31;
+long long span_bytes(int rows, int ld, int K, int esize) { return ((long long)rows * ld + K) * esize; }
+bool fits_31bit(const GemmParams& p, int a_esize, int b_esize) {
+    return span_bytes(p.M, p.lda, p.K, a_esize) < kMaxOffset && span_bytes(p.Nb, p.ldb, p.K, b_esize) < kMaxOffset;
+}
+
+// which kernel families have an instantiation for an epilogue; the launchers instantiate exactly these
+struct EpiTraits {
+    bool fp8b;     // fp8 B: the frozen-weight products of the block and their dX forms
+    bool fp8a;     // fp8 x fp8: the forward frozen products (opt-in weight format "fp8-act")
+    bool skinny;   // the few-row kernel
+    bool ksplit;   // the k-split, phased k-split and stream-K kernels
+};
+constexpr EpiTraits epi_traits(int e) {
+    return {e == EPI_QKV_HEADS || e == EPI_BIAS_RESID_F32 || e == EPI_BIAS_GELU || e == EPI_DGELU_BF16 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_F32,
+            e == EPI_QKV_HEADS || e == EPI_BIAS_RESID_F32 || e == EPI_BIAS_GELU || e == EPI_F32,
+            e == EPI_BIAS_RESID_F32 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_RESID_KEEP || e == EPI_BIAS_GELU || e == EPI_DGELU_BF16,
+            e == EPI_BIAS_RESID_F32 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_RESID_KEEP || e == EPI_PATCH_EMBED};
 }
 
 // wgm x wgn waves of wm x wn fragments; wgs = workgroups per CU the LDS and registers are sized for
@@ -1650,54 +1625,28 @@ constexpr int kNumConfigs = sizeof(kConfigs) / sizeof(kConfigs[0]);
 constexpr int cfg_bm(int c) { return kConfigs[c].wgm * kConfigs[c].wm * 32; }
 constexpr int cfg_bn(int c) { return kConfigs[c].wgn * kConfigs[c].wn * 32; }
 
-template <int EPI, int CFG, bool BF8>
-int launch_cfg(const GemmParams& p, const GemmTune& t, hipStream_t stream) {
-    constexpr TileConfig c = kConfigs[CFG];
-    constexpr int nw = c.wgm * c.wgn, bm = cfg_bm(CFG), bn = cfg_bn(CFG);
-    constexpr int lds = 2 * (bm + bn) * 128;
-    constexpr int minw = c.wgs * nw / 4;
-    auto kern = gemm_kernel<EPI, c.wgm, c.wgn, c.wm, c.wn, minw, c.hoist, BF8, c.spread, c.pipe && !BF8>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-            hipSuccess) {
-            pevit_set_error("hipFuncSetAttribute(gemm epi %d cfg %d) failed", EPI, CFG);
-            return -1;
-        }
-        attr_set = true;
-    }
-    const int tiles = ceil_div(p.M, bm) * ceil_div(p.N, bn);
-    // persistent grid: one workgroup per residency slot (a multiple of 8 keeps XCD affinity), or one
-    // per tile when the tiles do not even fill the slots
-    int grid = tiles;
-    if (t.persistent) {
-        const int slots = num_cus() * c.wgs;
-        if (tiles > slots) grid = slots;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, p, tiles);
-    LAUNCH_OK("gemm");
-    g_last_path = 1;
-    return 0;
-}
+// configuration 9 = 160x256 on 1 x 8 waves: only the staggered kernel has it (gemm8_kernel; `allow9`).  It is what fills the
+// chip at the reference's own batch of 64 (M = 3200: 240 tiles for c_fc / dGELU where 320x256 has 120).
+constexpr int CFG_160x256 = 9;
+
+// the tiles of the 8-wave configurations: 3 (256x128), 4 (256x256), 5 (320x256), CFG_160x256
+constexpr int big_bm(int c) { return c == 5 ? 320 : c == CFG_160x256 ? 160 : 256; }
+constexpr int big_bn(int c) { return c == 3 ? 128 : 256; }
 
 // Tile shape per problem.  Measured on MI355X (scripts/bench_gemm.py, profiles/NOTES_gemm.md (r02_gemm_experiments)).
 // The 8-wave tiles win when their tiling still gives (almost) every CU one tile per round;
 // the N = 768 products of the ViT-B step (75 tiles of 256x256) stay on the 4-wave tiles.
-// configuration 9 = 160x256 on 1 x 8 waves: only the staggered kernel has it (gemm8_kernel; `allow9`).  It is what fills the
-// chip at the reference's own batch of 64 (M = 3200: 240 tiles for c_fc / dGELU where 320x256 has 120).
-constexpr int CFG_160x256 = 9;
-int pick_config(const GemmParams& p, const GemmTune& t, bool allow9) {
+int pick_config(const GemmParams& p, const GemmTune& t, bool allow9, int cus) {
     if (t.config >= 0 && t.config < kNumConfigs) return t.config;
     if (t.config == CFG_160x256 && allow9) return CFG_160x256;
     if (p.N <= 64) return 2;
-    const int cus = num_cus();
     if (t.big) {
         // rounds of the persistent loop and the fraction of the last round that is filled
         const int cand[4] = {5, 4, 3, CFG_160x256};
         int best = -1; double best_cost = 1e30;
         for (int i = 0; i < (allow9 ? 4 : 3); ++i) {
             const int c = cand[i];
-            const int bm = c == 5 ? 320 : c == CFG_160x256 ? 160 : 256, bn = c == 3 ? 128 : 256;
+            const int bm = big_bm(c), bn = big_bn(c);
             const long tiles = (long)ceil_div(p.M, bm) * ceil_div(p.N, bn);
             if (tiles * 10 < (long)cus * 7) continue;                 // fewer than 0.7 tiles per CU: leave to the small tiles
             const long rounds = (tiles + cus - 1) / cus;
@@ -1740,12 +1689,11 @@ SkPlan sk_plan(long tiles, int nk, int slots) {
 // stream-K applies where the heuristic takes the 128x128 tile for a long-K problem with fewer tiles than residency slots
 // (the N = E products of ViT-B/32), bf16 B, the five epilogues those products use (c_proj forward with and without the kept MLP output, the
 // dX products in f32 / bf16, the patch embedding)
-SkPlan streamk_plan(const GemmParams& p, const GemmTune& t, int cfg) {
+SkPlan streamk_plan(const GemmParams& p, const GemmTune& t, int cfg, int slots) {
     const SkPlan none{0, 0};
     if (!t.streamk || !p.sk_slab || !p.sk_flag || !t.persistent) return none;
     const int tiles_m = ceil_div(p.M, 128);
     const long tiles = (long)tiles_m * ceil_div(p.N, 128);
-    const int slots = min(pevit_gemm_sk_slots(), p.sk_slots);
     const int nk = p.K / 64;
     if (slots < 8) return none;
     if (t.streamk == 2)        // measurement only
@@ -1756,241 +1704,293 @@ SkPlan streamk_plan(const GemmParams& p, const GemmTune& t, int cfg) {
     return t.streamk == 3 ? SkPlan{nk, TILE_BAND} : none;     // 3: the whole-tile walk through this kernel (measurement)
 }
 
-template <int EPI>
-int launch_streamk(const GemmParams& p_in, SkPlan plan, hipStream_t stream) {
-    const int share = plan.share;
-    constexpr int lds = 2 * (128 + 128) * 128;
-    auto kern = gemm_streamk_kernel<EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            pevit_set_error("hipFuncSetAttribute(stream-K gemm epi %d) failed", EPI);
-            return -1;
-        }
-        attr_set = true;
-    }
-    GemmParams p = p_in;
-    p.sk_share = share; p.sk_band = plan.band;
-    const int tiles = ceil_div(p.M, 128) * ceil_div(p.N, 128);
-    // every workgroup must be resident: the grid never exceeds the 2-per-CU slots (streamk_share checked that)
-    const int grid = (int)(((long)tiles * (p.K / 64) + share - 1) / share + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p, tiles);
-    LAUNCH_OK("gemm (stream-K)");
-    g_last_path = 5;
-    return 0;
-}
-
-// few-row long-K products on gemm_skinny_kernel: 2-6 slices of ~12 k-tiles, tiles x slices within the slab slots
-struct SkinnyPlan { int nslices, ksl; };
-SkinnyPlan skinny_plan(const GemmParams& p, const GemmTune& t) {
-    const SkinnyPlan none{0, 0};
-    if (!t.skinny || t.config >= 0 || t.ablate || p.b_fp8 || p.a_fp8 || !p.sk_slab || !p.sk_flag) return none;
-    const int nk = p.K / 64;
-    if (p.M > t.skinny_maxm || p.N < 64 || nk < t.skinny_mink) return none;
-    const long tiles = (long)ceil_div(p.M, 128) * ceil_div(p.N, 64);
-    const int slots = min(pevit_gemm_sk_slots(), p.sk_slots);       // a slot holds 128x128 floats: two of these slabs
-    const int nslices = t.skinny_slices > 0 ? min(6, max(1, t.skinny_slices)) : nk < 24 ? 1 : min(6, max(2, (nk + 6) / 12));
-    if (tiles * nslices > 2L * slots || tiles > slots) return none;  // tickets: one word per tile
-    return SkinnyPlan{nslices, ceil_div(nk, nslices)};
-}
-
-template <int EPI>
-int launch_skinny(const GemmParams& p, SkinnyPlan plan, hipStream_t stream) {
-    constexpr int lds = 4 * (128 + 64) * 128;
-    auto kern = gemm_skinny_kernel<EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            pevit_set_error("hipFuncSetAttribute(few-row gemm epi %d) failed", EPI);
-            return -1;
-        }
-        attr_set = true;
-    }
-    const int tiles_n = ceil_div(p.N, 64), tiles = ceil_div(p.M, 128) * tiles_n;
-    hipLaunchKernelGGL(kern, dim3(tiles * plan.nslices), dim3(256), lds, stream, p, tiles_n, plan.nslices, plan.ksl);
-    LAUNCH_OK("gemm (few rows)");
-    g_last_path = 6;
-    return 0;
-}
-
 // the 160x128 two-group tile: where the heuristic takes a 4-wave tile for a long-K problem whose 160x128 tiling gives (almost)
 // every CU exactly one tile -- the N = E products of ViT-B/32 at B = 128 (240 tiles)
 // returns the tile height in fragments: 5 (160x128), 3 (96x128: M = 3200, the reference's own batch of 64, gives 204 tiles where
 // 160x128 gives 120), or 0 = not this kernel
-int use_ksplit(const GemmParams& p, const GemmTune& t, int cfg) {
+int use_ksplit(const GemmParams& p, const GemmTune& t, int cfg, int cus) {
     if (!t.ksplit || t.config >= 0 || (cfg != 0 && cfg != 1) || t.ablate || p.K < t.ksplit_mink) return 0;
-    const int cus = num_cus() & ~7;
+    const int chip = cus & ~7;
     const int cand[2] = {5, 3};
     for (int i = 0; i < (t.ksplit_small ? 2 : 1); ++i) {
         const long tiles = (long)ceil_div(p.M, cand[i] * 32) * ceil_div(p.N, 128);
-        const long rounds = (tiles + cus - 1) / cus;
+        const long rounds = (tiles + chip - 1) / chip;
         if (t.ksplit == 1 && rounds > 1) continue;          // 2: also problems of several rounds (measurement)
-        if (4 * tiles >= 3 * rounds * cus) return cand[i];  // the last round at least 3/4 full on average
+        if (4 * tiles >= 3 * rounds * chip) return cand[i];  // the last round at least 3/4 full on average
     }
     return 0;
 }
 
-// two workgroups per 160x128 tile, half of K each (gemm_kphase_kernel<..., KZ>): where those tiles fill at most half the chip and
-// each slice still walks >= 16 k-tiles (M = 3200, N = 768, K >= 2048: three products per layer at batch 64)
-bool use_kz2(const GemmParams& p, const GemmTune& t) {
-    if (!t.kz2 || !p.sk_slab || !p.sk_flag) return false;
-    const long tiles = (long)ceil_div(p.M, 160) * ceil_div(p.N, 128);
-    const long long a = ((long long)p.M * p.lda + p.K) * 2, b = ((long long)p.Nb * p.ldb + p.K) * 2;
-    return 2 * tiles <= (num_cus() & ~7) && 4 * tiles >= (num_cus() & ~7) && p.K / 64 >= 32 && tiles <= p.sk_slots &&
-           tiles * kz_slab_floats(5) <= (long)p.sk_slots * PEVIT_SK_SLAB_FLOATS && a < (1LL << 31) && b < (1LL << 31);
+// Everything one launch needs.  A non-empty err means there is no kernel for the problem.
+struct GemmPlan {
+    int path = 0;         // kernel family (pevit_gemm_last_path): 1 gemm_kernel, 2 gemm8_kernel, 3 gemm_ksplit_kernel,
+                          // 4 gemm_kphase_kernel, 5 gemm_streamk_kernel, 6 gemm_skinny_kernel, 7 gemm_kphase_kernel<..., KZ = true>
+    int ops = 0;          // operands: 0 bf16 x bf16, 1 bf16 x fp8 B (on gemm8_kernel with the bf16 tail B2, if set), 2 fp8 x fp8
+    int cfg = 0;          // path 1: kConfigs index; path 2: 4, 5, CFG_160x256, or 3 (256x128, two k-steps per phase: measurement)
+    int wm = 0;           // paths 3, 4, 7: tile height in 32-row fragments (5: 160x128, 3: 96x128)
+    int nl = 0;           // paths 4, 7: LDS-DMA pieces of a k-tile requested in the LOAD section (2 or 8)
+    bool stag = false;    // path 3: the two wave groups half an iteration apart
+    int tiles = 0, grid = 0, band = 0;   // band: GemmParams::band of paths 2, 3, 4, 7
+    SkPlan sk{0, 0};      // path 5: GemmParams::sk_share, sk_band
+    int tiles_n = 0, nslices = 0, ksl = 0;   // path 6: 64-column tiles per row of tiles, K slices per tile, k-tiles per slice
+    char err[160] = "";
+};
+
+__attribute__((format(printf, 1, 2))) GemmPlan plan_error(const char* fmt, ...) {
+    GemmPlan pl;
+    va_list ap; va_start(ap, fmt); vsnprintf(pl.err, sizeof(pl.err), fmt, ap); va_end(ap);
+    return pl;
 }
 
-// the staggered 8-wave kernel: 256x256 (configuration 4) and 320x256 (5), bf16 B, operands addressable with 31-bit byte offsets
-template <int EPI, int WGM, int WGN, int WM, int WN, int KSP, int OPS>
-int launch_big8(const GemmParams& p, const GemmTune& t, hipStream_t stream) {
-    constexpr int bm = WGM * WM * 32, bn = WGN * WN * 32, stage = (bm + bn) * 128, scratch = 8 * 32 * WN * 32 * 4;
-    constexpr int lds = stage + (stage > scratch ? stage : scratch);
-    auto kern = gemm8_kernel<EPI, WGM, WGN, WM, WN, KSP, OPS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            pevit_set_error("hipFuncSetAttribute(staggered gemm epi %d) failed", EPI);
-            return -1;
+GemmPlan plan_gemm8(const GemmParams& p, const GemmTune& t, int cus, int cfg, int ops) {
+    GemmPlan pl; pl.path = 2; pl.cfg = cfg; pl.ops = ops;
+    const int tiles_n = ceil_div(p.N, big_bn(cfg)); pl.tiles = ceil_div(p.M, big_bm(cfg)) * tiles_n;
+    pl.grid = t.persistent && pl.tiles > cus ? cus : pl.tiles;
+    pl.band = xcd_band(pl.tiles, tiles_n, pl.grid, t);
+    return pl;
+}
+
+// paths 3, 4, 7: (wm x 32) x 128 tiles, at most one workgroup per CU; path 7 has two workgroups per tile
+GemmPlan plan_split(const GemmParams& p, const GemmTune& t, int cus, int path, int wm) {
+    GemmPlan pl; pl.path = path; pl.wm = wm;
+    const int tiles_n = ceil_div(p.N, 128); pl.tiles = ceil_div(p.M, wm * 32) * tiles_n;
+    pl.grid = min(path == 7 ? 2 * pl.tiles : pl.tiles, cus & ~7);
+    pl.band = xcd_band(pl.tiles, tiles_n, min(pl.tiles, pl.grid), t);
+    return pl;
+}
+
+// the kernel for a checked problem with bf16 or fp8 B: the families in the order they are tried
+GemmPlan plan_tiles(const EpiTraits& tr, const GemmParams& p, const GemmTune& t, int cus) {
+    const bool bf8 = p.b_fp8;
+    const int nk = p.K / 64;
+    const int slots = min(sk_slots(cus), p.sk_slots);
+    // few-row long-K products on gemm_skinny_kernel: 2-6 slices of ~12 k-tiles, tiles x slices within the slab slots
+    if (tr.skinny && !bf8 && t.skinny && t.config < 0 && !t.ablate && p.sk_slab && p.sk_flag && p.M <= t.skinny_maxm && p.N >= 64 &&
+        nk >= t.skinny_mink) {
+        GemmPlan pl; pl.path = 6;
+        pl.tiles_n = ceil_div(p.N, 64); pl.tiles = ceil_div(p.M, 128) * pl.tiles_n;
+        pl.nslices = t.skinny_slices > 0 ? min(6, max(1, t.skinny_slices)) : nk < 24 ? 1 : min(6, max(2, (nk + 6) / 12));
+        // a slot holds 128x128 floats: two of these slabs; tickets: one word per tile
+        if ((long)pl.tiles * pl.nslices <= 2L * slots && pl.tiles <= slots) {
+            pl.ksl = ceil_div(nk, pl.nslices); pl.grid = pl.tiles * pl.nslices;
+            return pl;
         }
-        attr_set = true;
     }
-    const int tiles = ceil_div(p.M, bm) * ceil_div(p.N, bn);
-    int grid = tiles;
-    if (t.persistent && tiles > num_cus()) grid = num_cus();
-    GemmParams pb = p;
-    pb.band = xcd_band(tiles, ceil_div(p.N, bn), grid, t);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, pb, tiles);
-    LAUNCH_OK("gemm (staggered 8-wave)");
-    g_last_path = 2;
-    return 0;
-}
-bool big8_ok(const GemmParams& p, const GemmTune& t) {
-    if (!t.stagger || (t.ablate & 12)) return false;
-    const long long a = ((long long)p.M * p.lda + p.K) * 2, b = ((long long)p.Nb * p.ldb + p.K) * (p.b_fp8 ? 1 : 2);
-    return a < (1LL << 31) && b < (1LL << 31);
-}
-
-template <int EPI, bool BF8>
-int launch_epi(const GemmParams& p, const GemmTune& t, hipStream_t stream) {
-    if constexpr (!BF8 && (EPI == EPI_BIAS_RESID_F32 || EPI == EPI_F32 || EPI == EPI_BF16 || EPI == EPI_BIAS_RESID_KEEP ||
-                           EPI == EPI_BIAS_GELU || EPI == EPI_DGELU_BF16)) {
-        const SkinnyPlan sp = skinny_plan(p, t);
-        if (sp.nslices) return launch_skinny<EPI>(p, sp, stream);
-    }
-    const bool stag = big8_ok(p, t);
-    const int cfg = pick_config(p, t, stag);
-    if (stag) {
-        if (cfg == 5) return launch_big8<EPI, 2, 4, 5, 2, 1, BF8 ? 1 : 0>(p, t, stream);
-        if (cfg == 4) return launch_big8<EPI, 2, 4, 4, 2, 1, BF8 ? 1 : 0>(p, t, stream);
-        if (cfg == CFG_160x256) return launch_big8<EPI, 1, 8, 5, 1, 1, BF8 ? 1 : 0>(p, t, stream);
-        if (cfg == 3 && t.stagger >= 2) return launch_big8<EPI, 4, 2, 2, 2, 2, BF8 ? 1 : 0>(p, t, stream);   // 256x128, two k-steps per phase (measurement)
-    }
-    if constexpr (!BF8 && (EPI == EPI_BIAS_RESID_F32 || EPI == EPI_F32 || EPI == EPI_BF16 || EPI == EPI_BIAS_RESID_KEEP || EPI == EPI_PATCH_EMBED)) {
-        const int kwm = use_ksplit(p, t, cfg);
-        if (kwm && t.ksplit_stagger == 2 && use_kz2(p, t)) return launch_kphase<EPI, 5, 8, true>(p, t, stream);
+    // the staggered 8-wave kernel, where the operands are addressable with 31-bit byte offsets
+    const bool stag = t.stagger && !(t.ablate & 12) && fits_31bit(p, 2, bf8 ? 1 : 2);
+    const int cfg = pick_config(p, t, stag, cus);
+    if (stag && (cfg == 5 || cfg == 4 || cfg == CFG_160x256 || (cfg == 3 && t.stagger >= 2)))
+        return plan_gemm8(p, t, cus, cfg, bf8 ? 1 : 0);
+    if (tr.ksplit && !bf8) {
+        const int kwm = use_ksplit(p, t, cfg, cus);
         if (kwm && t.ksplit_stagger == 2) {
-            // requests between the MFMAs (kphase_nl = 2: two in LOAD, the rest behind every second MFMA) win 3 % back to back and
-            // lose 0.9 % in the step (28.14 k vs 27.89 k images/s, two pairs; profiles/NOTES_gemm.md (r03_gemm_experiments) section 8)
-            if (kwm == 5) return t.kphase_nl <= 2 ? launch_kphase<EPI, 5, 2>(p, t, stream) : launch_kphase<EPI, 5, 8>(p, t, stream);
-            return t.kphase_nl <= 2 ? launch_kphase<EPI, 3, 2>(p, t, stream) : launch_kphase<EPI, 3, 8>(p, t, stream);
+            // two workgroups per 160x128 tile, half of K each (opt-in): where those tiles fill at most half the chip and each slice still
+            // walks >= 16 k-tiles (M = 3200, N = 768, K >= 2048: three products per layer at batch 64), one ticket + two slabs per tile
+            const long t160 = (long)ceil_div(p.M, 160) * ceil_div(p.N, 128);
+            const int chip = cus & ~7;
+            if (t.kz2 && p.sk_slab && p.sk_flag && 2 * t160 <= chip && 4 * t160 >= chip && nk >= 32 && t160 <= p.sk_slots &&
+                t160 * kz_slab_floats(5) <= (long)p.sk_slots * PEVIT_SK_SLAB_FLOATS && fits_31bit(p, 2, 2)) {
+                GemmPlan pl = plan_split(p, t, cus, 7, 5); pl.nl = 8;
+                return pl;
+            }
+            // the phased kernel; beyond 31-bit offsets the alternate-k-tile one.  Requests between the MFMAs (kphase_nl = 2: two in
+            // LOAD, the rest behind every second MFMA) win 3 % back to back and lose 0.9 % in the step (28.14 k vs 27.89 k
+            // images/s, two pairs; profiles/NOTES_gemm.md (r03_gemm_experiments) section 8)
+            GemmPlan pl = plan_split(p, t, cus, fits_31bit(p, 2, 2) ? 4 : 3, kwm);
+            pl.nl = t.kphase_nl <= 2 ? 2 : 8; pl.stag = true;
+            return pl;
         }
-        if (kwm == 5) return t.ksplit_stagger ? launch_ksplit<EPI, 1, 4, 5, 1, true>(p, t, stream) : launch_ksplit<EPI, 1, 4, 5, 1, false>(p, t, stream);
-        if (kwm == 3) return launch_ksplit<EPI, 1, 4, 3, 1, true>(p, t, stream);
-        const SkPlan plan = streamk_plan(p, t, cfg);
-        if (plan.share) return launch_streamk<EPI>(p, plan, stream);
+        if (kwm) {
+            GemmPlan pl = plan_split(p, t, cus, 3, kwm); pl.stag = kwm == 3 || t.ksplit_stagger;
+            return pl;
+        }
+        const SkPlan sk = streamk_plan(p, t, cfg, slots);
+        if (sk.share) {
+            GemmPlan pl; pl.path = 5; pl.sk = sk; pl.tiles = ceil_div(p.M, 128) * ceil_div(p.N, 128);
+            // every workgroup must be resident: the grid never exceeds the 2-per-CU slots (streamk_plan checked that)
+            pl.grid = (int)(((long)pl.tiles * nk + sk.share - 1) / sk.share + 7) & ~7;
+            return pl;
+        }
     }
-    switch (cfg) {
-        case 0: return launch_cfg<EPI, 0, BF8>(p, t, stream);
-        case 1: return launch_cfg<EPI, 1, BF8>(p, t, stream);
-        case 2: return launch_cfg<EPI, 2, BF8>(p, t, stream);
-        case 3: return launch_cfg<EPI, 3, BF8>(p, t, stream);
-        case 4: return launch_cfg<EPI, 4, BF8>(p, t, stream);
-        case 6: return launch_cfg<EPI, 6, BF8>(p, t, stream);
-        case 7: return launch_cfg<EPI, 7, BF8>(p, t, stream);
-        case 8: return launch_cfg<EPI, 8, BF8>(p, t, stream);
-        default: return launch_cfg<EPI, 5, BF8>(p, t, stream);
-    }
+    GemmPlan pl; pl.path = 1; pl.ops = bf8 ? 1 : 0; pl.cfg = cfg >= 0 && cfg < kNumConfigs ? cfg : 5;
+    const int wgs = kConfigs[pl.cfg].wgs; pl.tiles = ceil_div(p.M, cfg_bm(pl.cfg)) * ceil_div(p.N, cfg_bn(pl.cfg));
+    // persistent grid: one workgroup per residency slot (a multiple of 8 keeps XCD affinity), or one
+    // per tile when the tiles do not even fill the slots
+    pl.grid = t.persistent && pl.tiles > cus * wgs ? cus * wgs : pl.tiles;
+    return pl;
 }
 
-// fp8 x fp8 (GemmParams::a_fp8): always on the staggered kernel; the 8-wave tile whose rounds x bytes-per-k-tile is smallest
+// The one place that decides how a product runs: argument checks, then the operand form, then the kernel family and its grid.
+// Pure: no HIP calls, no globals (cus = compute units of the device).
+GemmPlan plan_gemm(int epi, const GemmParams& p, const GemmTune& t, int cus) {
+    if (p.K % 64 != 0 || p.K <= 0) return plan_error("gemm: K=%d must be a positive multiple of 64", p.K);
+    if (p.N % 8 != 0) return plan_error("gemm: N=%d must be a multiple of 8", p.N);
+    if (p.M <= 0 || p.N <= 0) return plan_error("gemm: empty problem M=%d N=%d", p.M, p.N);
+    if ((!p.a_fp8 && (p.lda % 8)) || (p.ldb % (p.b_fp8 ? 16 : 8))) return plan_error("gemm: lda/ldb must be multiples of 8 (16 for fp8 B)");
+    // the bf16 tail of an fp8-B problem (B2) is written by gemm8_kernel<.., OPS = 1> only, on its 256-column tiles: the tail starts
+    // on a tile boundary and is addressed through B's buffer descriptor, so it lies behind B, within 31 bits of it
+    const char* no_tail = "gemm: this problem has no kernel with a bf16 tail (ask pevit_gemm_mixed_ok first)";
+    if (p.B2) {
+        const long long off = reinterpret_cast<const char*>(p.B2) - reinterpret_cast<const char*>(p.B);
+        if (epi != EPI_QKV_HEADS || !p.b_fp8 || p.a_fp8 || p.n_fp8 % 256 || p.K % 128 || off <= 0 ||
+            off + span_bytes(p.Nb2, p.ldb2, p.K, 2) >= kMaxOffset)
+            return plan_error("%s", no_tail);
+    }
+    const EpiTraits tr = epi_traits(epi);
+    if (p.a_fp8) {
+        if (!p.b_fp8 || p.K % 128 != 0 || (p.lda % 16)) return plan_error("gemm: fp8 A needs fp8 B, K %% 128 == 0 and lda %% 16 == 0");
+        if (!tr.fp8a) return plan_error("gemm: epilogue %d has no fp8 x fp8 form", epi);
+        if (!fits_31bit(p, 1, 1)) return plan_error("gemm (fp8 x fp8): operands beyond 2 GiB");
+        // always the staggered kernel's 160x256 tile on 1 x 8 waves: a fragment of the 64-deep instruction is 8 registers per lane,
+        // and with two fragment columns per wave (320x256 / 256x256: 160 / 128 accumulator registers + 56 / 48 of fragments)
+        // hipcc spills 166 / 26 registers
+        return plan_gemm8(p, t, cus, CFG_160x256, 2);
+    }
+    if (p.b_fp8 && p.K % 128 != 0) return plan_error("gemm: fp8 B needs K=%d to be a multiple of 128", p.K);
+    if (p.b_fp8 && !tr.fp8b) return plan_error("gemm: epilogue %d has no fp8-weight form", epi);
+    if (epi < EPI_QKV_HEADS || epi > EPI_BIAS_F32) return plan_error("gemm: unknown epilogue %d", epi);
+    const GemmPlan pl = plan_tiles(tr, p, t, cus);
+    if (p.B2 && (pl.path != 2 || big_bn(pl.cfg) != 256)) return plan_error("%s", no_tail);
+    return pl;
+}
+
+// ---- launchers: a plan onto its kernel instantiation
+const char* const kFamily[] = {"", "tile", "staggered 8-wave", "k-split", "phased k-split", "stream-K", "few rows", "two K slices per tile"};
+
+// The one launch of every family.  The dynamic-LDS limit of an instantiation is raised by its first launch, through a
+// function-local static (thread-safe; a failure stays a failure for every later call).
+template <auto KERN, int LDS, typename... Args>
+int launch_kernel(int epi, const GemmPlan& pl, int block, hipStream_t stream, Args... args) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (attr == hipSuccess) hipLaunchKernelGGL(KERN, dim3(pl.grid), dim3(block), LDS, stream, args...);
+    const hipError_t e = attr != hipSuccess ? attr : hipGetLastError();
+    if (e != hipSuccess) {
+        pevit_set_error("gemm (%s, epi %d): %s failed: %s", kFamily[pl.path], epi, attr ? "raising the dynamic LDS limit" : "kernel launch",
+                        hipGetErrorString(e));
+        return -1;
+    }
+    g_last_path = pl.path;
+    return 0;
+}
+
+template <int EPI, int CFG, bool BF8>
+int launch_cfg(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    constexpr TileConfig c = kConfigs[CFG];
+    constexpr int nw = c.wgm * c.wgn, lds = 2 * (cfg_bm(CFG) + cfg_bn(CFG)) * 128;
+    return launch_kernel<gemm_kernel<EPI, c.wgm, c.wgn, c.wm, c.wn, c.wgs * nw / 4, c.hoist, BF8, c.spread, c.pipe && !BF8>, lds>(
+        EPI, pl, nw * 64, s, p, pl.tiles);
+}
+
+template <int EPI, int WGM, int WGN, int WM, int WN, int KSP, int OPS>
+int launch_big8(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    constexpr int stage = (WGM * WM + WGN * WN) * 32 * 128, scratch = 8 * 32 * WN * 32 * 4;
+    constexpr int lds = stage + (stage > scratch ? stage : scratch);
+    GemmParams pb = p; pb.band = pl.band;
+    return launch_kernel<gemm8_kernel<EPI, WGM, WGN, WM, WN, KSP, OPS>, lds>(EPI, pl, 512, s, pb, pl.tiles);
+}
+
+template <int EPI, int WM, bool STAG>
+int launch_ksplit(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    constexpr int stage = (WM * 32 + 128) * 128, scratch_end = 3 * stage + 8 * 4096;
+    constexpr int lds = 4 * stage > scratch_end ? 4 * stage : scratch_end;
+    GemmParams pb = p; pb.band = pl.band;
+    return launch_kernel<gemm_ksplit_kernel<EPI, 1, 4, WM, 1, STAG>, lds>(EPI, pl, 512, s, pb, pl.tiles);
+}
+
+template <int EPI, int WM, int NL, bool KZ = false>
+int launch_kphase(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    constexpr int stage = (WM * 32 + 128) * 128;
+    constexpr int scratch = 3 * stage > 4 * WM * 4096 ? 3 * stage : 4 * WM * 4096;
+    constexpr int lds = 4 * stage > scratch + 8 * 4096 ? 4 * stage : scratch + 8 * 4096;
+    GemmParams pb = p; pb.band = pl.band; pb.kz = KZ ? 2 : 0;
+    return launch_kernel<gemm_kphase_kernel<EPI, WM, NL, KZ>, lds>(EPI, pl, 512, s, pb, pl.tiles);
+}
+
 template <int EPI>
-int launch_f8a(const GemmParams& p, const GemmTune& t, hipStream_t stream) {
-    const long long a = (long long)p.M * p.lda + p.K, b = (long long)p.Nb * p.ldb + p.K;
-    if (a >= (1LL << 31) || b >= (1LL << 31)) { pevit_set_error("gemm (fp8 x fp8): operands beyond 2 GiB"); return -1; }
-    // 160x256 on 1 x 8 waves only: a fragment of the 64-deep instruction is 8 registers per lane, and with two fragment columns
-    // per wave (320x256 / 256x256: 160 / 128 accumulator registers + 56 / 48 of fragments) hipcc spills 166 / 26 registers
-    return launch_big8<EPI, 1, 8, 5, 1, 1, 2>(p, t, stream);
+int launch_streamk(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    GemmParams pb = p;
+    pb.sk_share = pl.sk.share; pb.sk_band = pl.sk.band;
+    return launch_kernel<gemm_streamk_kernel<EPI>, 2 * (128 + 128) * 128>(EPI, pl, 256, s, pb, pl.tiles);
+}
+
+template <int EPI>
+int launch_skinny(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    return launch_kernel<gemm_skinny_kernel<EPI>, 4 * (128 + 64) * 128>(EPI, pl, 256, s, p, pl.tiles_n, pl.nslices, pl.ksl);
+}
+
+// the kernel instantiation of a plan for operand form OPS (GemmPlan::ops); the epilogue's traits keep out the kernels it has no form
+// of.  The order in which the kernels are named here (and OPS 2, 1, 0 below) is the order hipcc emits them in.
+template <int EPI, int OPS>
+int launch_plan(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
+    constexpr EpiTraits tr = epi_traits(EPI);
+    if constexpr (OPS == 2 && tr.fp8a) {
+        if (pl.path == 2 && pl.cfg == CFG_160x256) return launch_big8<EPI, 1, 8, 5, 1, 1, 2>(p, pl, s);
+    } else if constexpr (OPS == 0 || (OPS == 1 && tr.fp8b)) {
+        constexpr bool BF8 = OPS == 1;
+        if constexpr (!BF8 && tr.skinny) {
+            if (pl.path == 6) return launch_skinny<EPI>(p, pl, s);
+        }
+        if (pl.path == 2) {
+            switch (pl.cfg) {
+                case 5: return launch_big8<EPI, 2, 4, 5, 2, 1, OPS>(p, pl, s);
+                case 4: return launch_big8<EPI, 2, 4, 4, 2, 1, OPS>(p, pl, s);
+                case CFG_160x256: return launch_big8<EPI, 1, 8, 5, 1, 1, OPS>(p, pl, s);
+                case 3: return launch_big8<EPI, 4, 2, 2, 2, 2, OPS>(p, pl, s);
+            }
+        }
+        if constexpr (!BF8 && tr.ksplit) {
+            if (pl.path == 7) return launch_kphase<EPI, 5, 8, true>(p, pl, s);
+            if (pl.path == 4 && pl.wm == 5) return pl.nl == 2 ? launch_kphase<EPI, 5, 2>(p, pl, s) : launch_kphase<EPI, 5, 8>(p, pl, s);
+            if (pl.path == 4) return pl.nl == 2 ? launch_kphase<EPI, 3, 2>(p, pl, s) : launch_kphase<EPI, 3, 8>(p, pl, s);
+            if (pl.path == 3 && pl.wm == 5) return pl.stag ? launch_ksplit<EPI, 5, true>(p, pl, s) : launch_ksplit<EPI, 5, false>(p, pl, s);
+            if (pl.path == 3) return launch_ksplit<EPI, 3, true>(p, pl, s);
+            if (pl.path == 5) return launch_streamk<EPI>(p, pl, s);
+        }
+        if (pl.path == 1) {
+            switch (pl.cfg) {
+                case 0: return launch_cfg<EPI, 0, BF8>(p, pl, s);
+                case 1: return launch_cfg<EPI, 1, BF8>(p, pl, s);
+                case 2: return launch_cfg<EPI, 2, BF8>(p, pl, s);
+                case 3: return launch_cfg<EPI, 3, BF8>(p, pl, s);
+                case 4: return launch_cfg<EPI, 4, BF8>(p, pl, s);
+                case 6: return launch_cfg<EPI, 6, BF8>(p, pl, s);
+                case 7: return launch_cfg<EPI, 7, BF8>(p, pl, s);
+                case 8: return launch_cfg<EPI, 8, BF8>(p, pl, s);
+                default: return launch_cfg<EPI, 5, BF8>(p, pl, s);
+            }
+        }
+    }
+    pevit_set_error("gemm: no kernel for path %d, epilogue %d, operand form %d", pl.path, EPI, OPS);   // plan_gemm reads the same traits
+    return -1;
+}
+
+// launch_plan<EPI, OPS> by epilogue, EPI_QKV_HEADS (0) .. EPI_BIAS_F32
+template <int OPS, int... E>
+int launch_epi(int epi, const GemmParams& p, const GemmPlan& pl, hipStream_t s, std::integer_sequence<int, E...>) {
+    constexpr int (*table[])(const GemmParams&, const GemmPlan&, hipStream_t) = {launch_plan<E, OPS>...};
+    return table[epi](p, pl, s);
 }
 
 }  // namespace
 
-// the bf16 tail of an fp8-B problem (GemmParams::B2) is implemented by gemm8_kernel<.., OPS = 1> only: true when launch_epi would
-// take one of its 256-column tiles for this problem and the tail starts on a tile boundary
+// a bf16 tail (B2) is only accepted where the plan puts the problem on a gemm8_kernel tile that writes it
 bool pevit_gemm_mixed_ok(const GemmParams& p, const GemmTune& t) {
-    if (!p.b_fp8 || p.a_fp8 || !p.B2 || p.n_fp8 % 256 || p.K % 128) return false;       // (EPI_QKV_HEADS only: pevit_launch_gemm checks)
-    if (!big8_ok(p, t)) return false;
-    // the tail is addressed through B's buffer descriptor: it must lie behind B, within 31 bits of it
-    const long long off = reinterpret_cast<const char*>(p.B2) - reinterpret_cast<const char*>(p.B);
-    if (off <= 0 || off + ((long long)p.Nb2 * p.ldb2 + p.K) * 2 >= (1LL << 31)) return false;
-    const int cfg = pick_config(p, t, true);
-    return cfg == 5 || cfg == 4 || cfg == CFG_160x256;
+    return p.B2 && !plan_gemm(EPI_QKV_HEADS, p, t, num_cus()).err[0];
 }
 
 int pevit_num_cus() { return num_cus(); }
-int pevit_gemm_sk_slots() { return min(2 * num_cus(), PEVIT_SK_MAX_SLOTS) & ~7; }
+int pevit_gemm_sk_slots() { return sk_slots(num_cus()); }
 int pevit_gemm_last_path() { return g_last_path; }
 
 int pevit_launch_gemm(int epi, const GemmParams& p_in, const GemmTune& t, hipStream_t stream) {
     GemmParams p = p_in;
     p.dbg = t.ablate;
-    if (p.K % 64 != 0 || p.K <= 0) { pevit_set_error("gemm: K=%d must be a positive multiple of 64", p.K); return -1; }
-    if (p.N % 8 != 0) { pevit_set_error("gemm: N=%d must be a multiple of 8", p.N); return -1; }
-    if (p.M <= 0 || p.N <= 0) { pevit_set_error("gemm: empty problem M=%d N=%d", p.M, p.N); return -1; }
-    if ((!p.a_fp8 && (p.lda % 8)) || (p.ldb % (p.b_fp8 ? 16 : 8))) { pevit_set_error("gemm: lda/ldb must be multiples of 8 (16 for fp8 B)"); return -1; }
-    if (p.a_fp8) {
-        if (!p.b_fp8 || p.K % 128 != 0 || (p.lda % 16)) { pevit_set_error("gemm: fp8 A needs fp8 B, K %% 128 == 0 and lda %% 16 == 0"); return -1; }
-        // the forward frozen products of the block (opt-in weight format "fp8-act")
-        switch (epi) {
-            case EPI_QKV_HEADS: return launch_f8a<EPI_QKV_HEADS>(p, t, stream);
-            case EPI_BIAS_RESID_F32: return launch_f8a<EPI_BIAS_RESID_F32>(p, t, stream);
-            case EPI_BIAS_GELU: return launch_f8a<EPI_BIAS_GELU>(p, t, stream);
-            case EPI_F32: return launch_f8a<EPI_F32>(p, t, stream);
-        }
-        pevit_set_error("gemm: epilogue %d has no fp8 x fp8 form", epi);
-        return -1;
+    const GemmPlan pl = plan_gemm(epi, p, t, num_cus());
+    if (pl.err[0]) { pevit_set_error("%s", pl.err); return -1; }
+    constexpr auto epis = std::make_integer_sequence<int, EPI_BIAS_F32 + 1>{};   // plan_gemm refused any other epilogue
+    switch (pl.ops) {
+        case 2: return launch_epi<2>(epi, p, pl, stream, epis);
+        case 1: return launch_epi<1>(epi, p, pl, stream, epis);
+        default: return launch_epi<0>(epi, p, pl, stream, epis);
     }
-    if (p.B2 && (epi != EPI_QKV_HEADS || !pevit_gemm_mixed_ok(p, t))) { pevit_set_error("gemm: this problem has no kernel with a bf16 tail (ask pevit_gemm_mixed_ok first)"); return -1; }
-    if (p.b_fp8) {
-        if (p.K % 128 != 0) { pevit_set_error("gemm: fp8 B needs K=%d to be a multiple of 128", p.K); return -1; }
-        // the frozen-weight products of the block and their dX forms
-        switch (epi) {
-            case EPI_QKV_HEADS: return launch_epi<EPI_QKV_HEADS, true>(p, t, stream);
-            case EPI_BIAS_RESID_F32: return launch_epi<EPI_BIAS_RESID_F32, true>(p, t, stream);
-            case EPI_BIAS_GELU: return launch_epi<EPI_BIAS_GELU, true>(p, t, stream);
-            case EPI_DGELU_BF16: return launch_epi<EPI_DGELU_BF16, true>(p, t, stream);
-            case EPI_F32: return launch_epi<EPI_F32, true>(p, t, stream);
-            case EPI_BF16: return launch_epi<EPI_BF16, true>(p, t, stream);
-            case EPI_BIAS_F32: return launch_epi<EPI_BIAS_F32, true>(p, t, stream);
-        }
-        pevit_set_error("gemm: epilogue %d has no fp8-weight form", epi);
-        return -1;
-    }
-    switch (epi) {
-        case EPI_QKV_HEADS: return launch_epi<EPI_QKV_HEADS, false>(p, t, stream);
-        case EPI_BIAS_RESID_F32: return launch_epi<EPI_BIAS_RESID_F32, false>(p, t, stream);
-        case EPI_BIAS_GELU: return launch_epi<EPI_BIAS_GELU, false>(p, t, stream);
-        case EPI_DGELU_BF16: return launch_epi<EPI_DGELU_BF16, false>(p, t, stream);
-        case EPI_F32: return launch_epi<EPI_F32, false>(p, t, stream);
-        case EPI_BF16: return launch_epi<EPI_BF16, false>(p, t, stream);
-        case EPI_BIAS_BF16: return launch_epi<EPI_BIAS_BF16, false>(p, t, stream);
-        case EPI_PATCH_EMBED: return launch_epi<EPI_PATCH_EMBED, false>(p, t, stream);
-        case EPI_BIAS_RELU_BF16: return launch_epi<EPI_BIAS_RELU_BF16, false>(p, t, stream);
-        case EPI_BIAS_RESID_KEEP: return launch_epi<EPI_BIAS_RESID_KEEP, false>(p, t, stream);
-        case EPI_BIAS_GELUNEW: return launch_epi<EPI_BIAS_GELUNEW, false>(p, t, stream);
-        case EPI_DRELU_BF16: return launch_epi<EPI_DRELU_BF16, false>(p, t, stream);
-        case EPI_DGELUNEW_BF16: return launch_epi<EPI_DGELUNEW_BF16, false>(p, t, stream);
-        case EPI_BIAS_F32: return launch_epi<EPI_BIAS_F32, false>(p, t, stream);
-    }
-    pevit_set_error("gemm: unknown epilogue %d", epi);
-    return -1;
 }

@@ -75,11 +75,12 @@ struct GemmTune {
 };
 constexpr int PEVIT_SK_SLAB_FLOATS = 128 * 128;   // one partial tile per residency slot
 constexpr int PEVIT_SK_MAX_SLOTS = 1024;
-int pevit_gemm_last_path();                        // 1 plain tile, 2 staggered 8-wave, 3 k-split (alternate k-tiles), 4 phased k-split, 5 stream-K, 6 few-row split-K
+int pevit_gemm_last_path();                        // 1 plain tile, 2 staggered 8-wave, 3 k-split (alternate k-tiles), 4 phased k-split, 5 stream-K, 6 few-row split-K,
+                                                   // 7 phased k-split with two K slices per tile
 int pevit_gemm_sk_slots();                         // residency slots of the stream-K kernel on this device (2 per CU, multiple of 8)
 
 int pevit_launch_gemm(int epi, const GemmParams& p, const GemmTune& t, hipStream_t stream);
-bool pevit_gemm_mixed_ok(const GemmParams& p, const GemmTune& t);   // would this fp8-B problem with a bf16 tail (B2) run on a kernel that supports it?
+bool pevit_gemm_mixed_ok(const GemmParams& p, const GemmTune& t);   // does pevit_launch_gemm(EPI_QKV_HEADS, p, t) have a kernel that writes the bf16 tail B2?
 
 // ---- norm.hip --------------------------------------------------------------------
 // y = LN(x) * gamma + beta over the last dim (eps 1e-5, f32 statistics: model.py:154-160)
