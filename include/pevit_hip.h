@@ -24,9 +24,8 @@
  *
  * Conventions: extern "C"; every function returns 0 on success and a negative value on error
  * (pevit_last_error() gives the message); nothing throws; no device-memory allocation by any context entry point
- * (the optional "side_stream" knob creates one stream + two events on first use, profiling its
- * events in pevit_profile_begin; the CONTEXT-FREE test entry point pevit_op_gemm allocates a stream-K workspace of its own
- * on first use, once per process).  One process drives one device: the kernel attributes and the CU count are cached
+ * (profiling creates its events in pevit_profile_begin; the CONTEXT-FREE test entry point pevit_op_gemm allocates a stream-K
+ * workspace of its own on first use, once per process).  One process drives one device: the kernel attributes and the CU count are cached
  * per process -- all device memory (weight arena, workspace, parameter and gradient
  * buffers) is owned by the caller and only borrowed; all work is enqueued asynchronously on
  * the caller's hipStream_t (passed as void*); contexts are independent of each other (no
@@ -294,7 +293,7 @@ int pevit_op_im2col_u8(void* stream, const uint8_t* images, const float* mean3, 
  * configuration: 128x128, 64x128, 64x64 with 4 waves; 256x128, 256x256, 320x256 with 8 waves; 6 = 128x64 with 4 waves),
  * "gemm_persistent", "gemm_big" (0 = never pick the 8-wave tiles), "gemm_big_bias", "gemm_kswitch", "gemm_cfg_longk" /
  * "gemm_cfg_shortk" (configuration of the few-tile problems above / below kswitch), "gemm_ablate" (bit 0 skips the
- * k-loop, bit 1 the epilogue stores, bit 2 the operand stream, bit 3 ds_read + MFMA), "side_stream" (ctx only),
+ * k-loop, bit 1 the epilogue stores, bit 2 the operand stream, bit 3 ds_read + MFMA),
  * "gemm_streamk" (0 = never use the stream-K decomposition of the few-tile long-K products), "gemm_ksplit" (0 = never
  * use the one-tile-per-CU 160x128 / 96x128 k-split tile of the N = E products; 2 = also on problems of several rounds),
  * "gemm_ksplit_stagger" (2 = phased kernel, default; 1 / 0 = the alternate-k-tile kernel with / without the half-iteration
@@ -302,9 +301,10 @@ int pevit_op_im2col_u8(void* stream, const uint8_t* images, const float* mean3, 
  * MFMAs: 2), "gemm_kz2" (1 = two workgroups per 160x128 tile, half of K each, where those tiles fill at most half the chip;
  * default 0: measured slower, profiles/r05_experiments.md), "gemm_stagger" (0 = legacy 8-wave kernel, 1 = staggered, 2 = also the 256x128 tile), "gemm_band",
  * "gemm_skinny" (0 = never use the few-row split-K kernel), "gemm_skinny_maxm" / "_mink" / "_slices", "gemm_sk_share" /
- * "gemm_sk_band" (with gemm_streamk = 2), "lowrank_xcd", "fused_bottleneck", "profile_all", "fused_attn_delta" (0 = delta_add + attn_fwd as two launches), "fp8_tail" (0 = t = xn P as a launch of its own with fp8 weights), "adapter_fused" (0 = the post-MLP adapter as separate
+ * "gemm_sk_band" (with gemm_streamk = 2), "lowrank_xcd", "profile_all", "fused_attn_delta" (0 = delta_add + attn_fwd as two launches), "fp8_tail" (0 = t = xn P as a launch of its own with fp8 weights), "adapter_fused" (0 = the post-MLP adapter as separate
  * LayerNorm / GEMM launches), "lowrank_combo" (0 = lowrank_u and lowrank_grad as two launches per layer) and
- * "dx_stored" (ctx only);
+ * "dx_stored" (ctx only).  A path knob takes effect at the next forward: a backward takes the paths of the forward whose
+ * activations it uses;
  * returns 0, or -1 for an unknown key */
 int pevit_tune(pevit_ctx* ctx, const char* key, int value);
 

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <new>
+#include <vector>
 
 #include "../../include/pevit_hip.h"
 #include "common.h"
@@ -52,6 +53,43 @@ struct LayerSaved {        // byte offsets inside the workspace, one per layer (
     size_t hf32, mean_a, rstd_a, z, apre, act;     // post-MLP adapters
 };
 
+struct WsLayout {          // byte offsets inside the workspace for one batch (layout_workspace)
+    std::vector<LayerSaved> sav;
+    size_t w_skflag, w_skslab;      // stream-K workspace (gemm.hip)
+    size_t w_a8, w_attn8;           // e4m3 copies of the LayerNorm output / the attention output (fp8act)
+    size_t w_xfinal, w_xn2, w_g, w_dqkv, w_u32, w_u32b, w_dO, w_dh, w_dxn, w_dxa, w_dxb, w_dyb, w_partial, w_dbias, w_G, w_rule;
+    size_t w_dpre, w_dpre2, w_dht, w_dhb, w_tnU, w_tnD, w_csx, w_csy, w_lnp, w_Gd, w_Gu;
+    size_t w_patches, w_xpost, w_feat, w_pmean, w_prstd, w_ybn, w_bnrstd, w_logits, w_dlogits, w_dybn, w_dfeat, w_dfeatb, w_dxpost;
+    size_t partial_layer, dbias_layer, tn_layer, csx_layer, csy_layer, lnp_layer;    // per-layer slab strides
+    size_t total;
+};
+
+// Every path choice of a step, made once by plan_step() when a forward starts and kept with its saved activations, so that a
+// backward walks the paths its forward took: a knob changed in between takes effect at the next forward.
+struct StepPlan {
+    bool site = false;           // attention-site adapters (KAdaptation, LoRA): 64 adapter columns ride on the QKV product
+    bool post_mlp = false;       // post-MLP adapters (Adapter, Compacter)
+    bool cls_prune = false;      // visual tower: the last block after its attention core on the class-token rows only
+    bool attn_delta = false;     // delta-add + attention forward as one launch (attn_delta.hip)
+    bool fp8_tail = false;       // fp8 weights: t = xn P as the bf16 tail of the QKV launch where pevit_gemm_mixed_ok allows it
+    bool adapter_fused = false;  // post-MLP adapter as one launch per direction (adapter_fused.hip)
+    bool tn_fold = false;        // ... and both token-contracted weight-gradient products inside its backward launch
+    int tn_fold_wgs = 0;         // ... on that many workgroups (0: the kernel's own count)
+    bool gstream16 = false;      // the residual GRADIENT stream of the backward in bf16 only
+    bool dx_stored = false;      // dX GEMMs hand the LN-input gradient to LayerNorm backward in the storage type
+    bool lowrank_combo = false;  // u + dQ + d bias of a layer and the dP of the layer before it as one launch
+    bool lowrank_xcd = false;    // lowrank_grad: XCD-contiguous workgroup order
+};
+
+// which forward the saved activations belong to
+enum class Saved { none, blocks, visual, attention };
+struct SavedForward {
+    Saved kind = Saved::none;
+    int batch = 0;               // 0: no backward may use them
+    int layer = -1;              // attention seam: its layer
+    StepPlan plan;               // the paths that forward took
+};
+
 }  // namespace
 
 static GemmTune g_default_tune;   // used by the context-free single-kernel entry points (pevit_op_*) only
@@ -62,7 +100,6 @@ struct pevit_ctx {
     int NQ, NQpad;            // 3E+64 and its multiple-of-128 padding
     bool fp8 = false;         // frozen block weights as e4m3 codes + per-channel scales (fp8.hip)
     bool fp8act = false;      // ... and fp8 A operands in the forward frozen products (PEVIT_W_FP8_ACT)
-    size_t w_a8 = 0, w_attn8 = 0;   // e4m3 copies of the LayerNorm output / the attention output (fp8act)
     bool f32 = false;         // f32-class verification mode: every bf16-declared buffer holds f32 (verify.hip)
     size_t es = 2;            // bytes per element of those buffers
     float ascale;             // 160 (model.py:564) or alpha/r (lora_model.py:491)
@@ -71,16 +108,11 @@ struct pevit_ctx {
     size_t a_conv, a_cls, a_pos, a_lnpre_w, a_lnpre_b, a_lnpost_w, a_lnpost_b, a_proj, a_projT, a_phm;
     size_t arena_bytes = 0;
     char* arena = nullptr;
-    // workspace
-    LayerSaved* sav = nullptr;
-    size_t w_skflag = 0, w_skslab = 0; int sk_slots = 0;   // stream-K workspace (gemm.hip), sk_slots = 0: disabled
-    size_t w_xfinal, w_xn2, w_g, w_dqkv, w_u32, w_u32b, w_dO, w_dh, w_dxn, w_dxa, w_dxb, w_dyb, w_partial, w_dbias;
-    size_t w_G, w_rule, partial_layer, dbias_layer;
-    size_t w_dpre, w_dpre2, w_dht, w_dhb, w_tnU, w_tnD, w_csx, w_csy, w_lnp, w_Gd, w_Gu, tn_layer, csx_layer, csy_layer, lnp_layer;
+    // workspace: the layout of the batch in flight
+    WsLayout lay;
+    int sk_slots = 0;         // stream-K slots (gemm.hip), 0: disabled
     // post-MLP adapter parameter offsets inside one layer's block of the flat buffer (floats)
     size_t o_nw, o_nb, o_dw, o_db, o_uw, o_ub, o_dWl, o_dWr, o_uWl, o_uWr;
-    size_t w_patches, w_xpost, w_feat, w_pmean, w_prstd, w_ybn, w_bnrstd, w_logits, w_dlogits, w_dybn, w_dfeat,
-        w_dfeatb, w_dxpost;
     size_t ws_bytes_for_max = 0;
     char* ws = nullptr;
     int max_batch = 0;
@@ -92,10 +124,7 @@ struct pevit_ctx {
     size_t p_head_w = 0, p_head_b = 0;
     float img_mean[3] = {0.f, 0.f, 0.f}, img_std[3] = {1.f, 1.f, 1.f};   // pevit_set_input_norm: preprocessing of uint8 pixels
     bool img_norm_set = false;
-    int saved_batch = 0;
-    int saved_kind = 0;       // which forward the saved activations belong to: 1 = transformer seam, 2 = visual (class-token pruned),
-                              // 3 = attention seam of layer saved_layer
-    int saved_layer = -1;
+    SavedForward saved;
     // optional per-GEMM timing (HIP events on the caller's stream), see pevit_profile_begin
     bool prof_on = false;
     int prof_all = 0;         // also bracket the HBM-bound kernels (pevit_tune "profile_all")
@@ -105,10 +134,6 @@ struct pevit_ctx {
     double* prof_bytes = nullptr;       // algorithmic operand + result bytes of each launch
     float* prof_ms = nullptr;           // filled by pevit_profile_end
     int* prof_shape = nullptr;          // epilogue, M, N, K of each launch
-    // second stream for work that is off the backward critical path (adapter-gradient contractions); created on
-    // first use, so that contexts can still be sized on machines without a GPU
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // A/B-measurement knobs (pevit_tune): per context, so that contexts stay independent of each other
     GemmTune tune;
     hipEvent_t step_gate = nullptr;         // pevit_set_step_gate: the fused step waits for it between the stem and the first block
@@ -117,18 +142,15 @@ struct pevit_ctx {
     bool in_fused_step = false;
     const float* dfeatb_of = nullptr;       // the dfeat buffer whose bf16 copy the head's BatchNorm backward has just left in w_dfeatb (consumed by the next visual backward)
     float* last_loss = nullptr;             // where the loss of the step in flight was written (NaN goes there when its update is withheld)
+    // path knobs (pevit_tune), read by plan_step() only
     int gstream16 = 1;        // attention-site adapters, bf16 weights: the residual GRADIENT stream is carried in bf16 only (the copy the dX GEMMs read), LayerNorm backward read-modify-writes it in place: 10 instead of 16 B per element (round 5)
     int dx_stored = 1;        // dX GEMMs hand the LN-input gradient to LayerNorm backward in the activation storage type (bf16)
-    int fused_bn = 0;         // post-MLP adapters: down -> activation -> up (and its backward) as one launch each (adapter.hip
-                              // bottleneck_pair_kernel): 24.4 + 22.1 us against 22.9 + 19.5 us for the four GEMM launches -- opt-in
     int lowrank_combo = 1;    // attention-site adapters: u + dQ + d bias of a layer and the dP of the layer before it as one launch
-    int adapter_tn_fold = 1;  // ... and the two token-contracted weight-gradient products ride in the backward launch (adapter_fused.hip: af_tn_range; > 1: that many workgroups for them)
     int adapter_fused = 1;    // post-MLP adapters: LayerNorm -> down -> activation -> up -> residual (and its backward) as one launch each
+    int adapter_tn_fold = 1;  // ... and the two token-contracted weight-gradient products ride in the backward launch (adapter_fused.hip: af_tn_range; > 1: that many workgroups for them)
     int fp8_tail = 1;         // fp8 weights: t = xn P as the bf16 tail of the QKV launch (0: a separate small product, as before round 4)
     int fused_attn_delta = 1; // delta-add + attention forward as one launch where the geometry allows (attn_delta.hip)
     int lowrank_xcd = 1;      // lowrank_grad: XCD-contiguous workgroup order (+0.2 % per step)
-    int side_stream = 0;      // adapter-gradient contractions on a second stream: +0.5 % step throughput, but it slows the GEMMs
-                              // it overlaps by 4 %, which blurs the per-kernel roofline measurement: off by default
 };
 
 namespace {
@@ -138,15 +160,43 @@ inline bool attention_site(const pevit_ctx* c) {
 }
 inline bool post_mlp(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER || c->d.method == PEVIT_COMPACTER; }
 
-void layout_workspace(pevit_ctx* c, int B, LayerSaved* sav, size_t* total, pevit_ctx* fill) {
+// the launch paths of a step of batch B: a pure function of the context's dims, weight format and knobs, the batch and the CU count
+StepPlan plan_step(const pevit_ctx* c, int B) {
+    StepPlan p;
+    p.site = attention_site(c);
+    p.post_mlp = post_mlp(c);
+    p.cls_prune = !p.post_mlp;
+    // delta-add and the attention core as ONE launch where a run of heads owns whole reference rows of the raw reshape
+    // (attn_delta.hip: N <= 64; ViT-B/32), otherwise delta_add + attn_fwd
+    // ... unless its one-workgroup-per-CU runs leave between a quarter and three quarters of the chip empty (measured at batch
+    // 64: 128 runs for 256 CUs, the two kernels are 0.6 % of the step faster; fused_attn_delta = 2 forces the fused form)
+    if (p.site && c->fused_attn_delta && !c->f32 && !c->fp8act) {
+        const int hpw = pevit_attn_delta_hpw(B, c->H, c->N);
+        const int runs = hpw > 0 ? (B * c->H + hpw - 1) / hpw : 0;
+        p.attn_delta = hpw > 0 && (c->fused_attn_delta > 1 || 4 * runs >= 3 * pevit_num_cus() || 4 * runs <= pevit_num_cus());
+    }
+    p.fp8_tail = p.site && c->fp8 && !c->fp8act && c->fp8_tail;
+    p.adapter_fused = p.post_mlp && c->adapter_fused && !c->f32 && pevit_adapter_fused_ok(c->E);
+    p.tn_fold = p.adapter_fused && c->adapter_tn_fold;
+    p.tn_fold_wgs = p.tn_fold && c->adapter_tn_fold > 1 ? c->adapter_tn_fold : 0;
+    p.dx_stored = c->dx_stored;
+    // attention-site adapters, and the post-MLP ones on their fused kernels; never the f32 verification mode
+    p.gstream16 = c->gstream16 && !c->f32 && p.dx_stored && (p.site || p.adapter_fused);
+    p.lowrank_combo = p.site && c->lowrank_combo && !c->f32;
+    p.lowrank_xcd = c->lowrank_xcd;
+    return p;
+}
+
+WsLayout layout_workspace(const pevit_ctx* c, int B) {
     Carver cv;
     const size_t T = (size_t)B * c->N, E = c->E, es = c->es;
-    size_t o;
+    WsLayout w{};
     // stream-K hand-off flags (+1 error word) and partial-tile slabs: first, so that their place does not depend on the batch
-    o = cv.take((size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4);                        if (fill) fill->w_skflag = o;   // + error word + skipped-update counter
-    o = cv.take((size_t)c->sk_slots * PEVIT_SK_SLAB_FLOATS * 4);              if (fill) fill->w_skslab = o;
-    for (int l = 0; l < c->L; ++l) {
-        LayerSaved s;
+    w.w_skflag = cv.take((size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4);     // + error word + skipped-update counter
+    w.w_skslab = cv.take((size_t)c->sk_slots * PEVIT_SK_SLAB_FLOATS * 4);
+    w.sav.resize(c->L);
+    for (LayerSaved& s : w.sav) {
+        s = LayerSaved{};
         s.x_in = cv.take(T * E * 4);
         s.x_mid = cv.take(T * E * 4);
         s.mean1 = cv.take(T * 4); s.rstd1 = cv.take(T * 4);
@@ -157,67 +207,67 @@ void layout_workspace(pevit_ctx* c, int B, LayerSaved* sav, size_t* total, pevit
         s.lse = cv.take((size_t)B * c->H * c->N * 4);
         s.attn_out = cv.take(T * E * es);
         s.h = cv.take(T * 4 * E * es);
-        s.hf32 = s.mean_a = s.rstd_a = s.z = s.apre = s.act = 0;
         if (post_mlp(c)) {
             s.hf32 = cv.take(T * E * 4); s.mean_a = cv.take(T * 4); s.rstd_a = cv.take(T * 4);
             s.z = cv.take(T * E * es); s.apre = cv.take(T * 64 * es); s.act = cv.take(T * 64 * es);
         }
-        if (sav) sav[l] = s;
     }
     const int chunks = pevit_lowrank_chunks((int)T);
-    o = cv.take(T * E * 4);                 if (fill) fill->w_xfinal = o;
-    o = cv.take(T * E * es);                 if (fill) fill->w_xn2 = o;
-    o = cv.take(T * 4 * E * es);             if (fill) fill->w_g = o;       // (fp8act: holds gelu(h) as e4m3 codes, half of it used)
+    w.w_xfinal = cv.take(T * E * 4);
+    w.w_xn2 = cv.take(T * E * es);
+    w.w_g = cv.take(T * 4 * E * es);            // (fp8act: holds gelu(h) as e4m3 codes, half of it used)
     if (c->fp8act) {
-        o = cv.take(T * E);                  if (fill) fill->w_a8 = o;
-        o = cv.take(T * E);                  if (fill) fill->w_attn8 = o;
+        w.w_a8 = cv.take(T * E);
+        w.w_attn8 = cv.take(T * E);
     }
-    o = cv.take(T * (size_t)c->NQ * es);     if (fill) fill->w_dqkv = o;
-    o = cv.take(T * 64 * 4);                if (fill) fill->w_u32 = o;
-    o = cv.take(T * 64 * 4);                if (fill) fill->w_u32b = o;      // second u buffer: dP of a layer is taken one launch later (lowrank_combo)
-    o = cv.take(T * E * es);                 if (fill) fill->w_dO = o;
-    o = cv.take(T * 4 * E * es);             if (fill) fill->w_dh = o;
-    o = cv.take(T * E * 4);                 if (fill) fill->w_dxn = o;
-    o = cv.take(T * E * 4);                 if (fill) fill->w_dxa = o;
-    o = cv.take(T * E * 4);                 if (fill) fill->w_dxb = o;
-    o = cv.take(T * E * es);                 if (fill) fill->w_dyb = o;
+    w.w_dqkv = cv.take(T * (size_t)c->NQ * es);
+    w.w_u32 = cv.take(T * 64 * 4);
+    w.w_u32b = cv.take(T * 64 * 4);             // second u buffer: dP of a layer is taken one launch later (lowrank_combo)
+    w.w_dO = cv.take(T * E * es);
+    w.w_dh = cv.take(T * 4 * E * es);
+    w.w_dxn = cv.take(T * E * 4);
+    w.w_dxa = cv.take(T * E * 4);
+    w.w_dxb = cv.take(T * E * 4);
+    w.w_dyb = cv.take(T * E * es);
     // adapter-gradient partials of every layer (reduced once per step, after the layer loop)
-    const size_t part_layer = align_up((size_t)chunks * 4 * E * 32 * 4, 256), db_layer = align_up((size_t)chunks * 2 * E * 4, 256);
-    o = cv.take(part_layer * c->L);                      if (fill) { fill->w_partial = o; fill->partial_layer = part_layer; }
-    o = cv.take(db_layer * c->L);                        if (fill) { fill->w_dbias = o; fill->dbias_layer = db_layer; }
-    o = cv.take((size_t)c->L * 4 * E * 32 * 4);          if (fill) fill->w_G = o;
-    o = cv.take((size_t)c->L * 4096 * 4);                if (fill) fill->w_rule = o;
+    w.partial_layer = align_up((size_t)chunks * 4 * E * 32 * 4, 256);
+    w.dbias_layer = align_up((size_t)chunks * 2 * E * 4, 256);
+    w.w_partial = cv.take(w.partial_layer * c->L);
+    w.w_dbias = cv.take(w.dbias_layer * c->L);
+    w.w_G = cv.take((size_t)c->L * 4 * E * 32 * 4);
+    w.w_rule = cv.take((size_t)c->L * 4096 * 4);
     if (post_mlp(c)) {
         const int tch = pevit_tn_chunks((int)T), lnb = std::max(pevit_lna_blocks((int)T), pevit_adapter_blocks((int)T));
-        const size_t tn_layer = (size_t)tch * E * 64 * 4, csx_layer = (size_t)tch * E * 4, csy_layer = (size_t)tch * 64 * 4,
-                     lnp_layer = (size_t)lnb * 3 * E * 4;
-        o = cv.take(T * 64 * es);            if (fill) fill->w_dpre = o;
-        o = cv.take(T * 64 * es);            if (fill) fill->w_dpre2 = o;     // d pre alternates: the deferred d W_down product reads the previous one
-        o = cv.take(T * E * 4);             if (fill) fill->w_dht = o;
-        o = cv.take(T * E * es);             if (fill) fill->w_dhb = o;
-        o = cv.take(tn_layer * c->L);       if (fill) { fill->w_tnU = o; fill->tn_layer = tn_layer; }
-        o = cv.take(tn_layer * c->L);       if (fill) fill->w_tnD = o;
-        o = cv.take(csx_layer * c->L);      if (fill) { fill->w_csx = o; fill->csx_layer = csx_layer; }
-        o = cv.take(csy_layer * c->L);      if (fill) { fill->w_csy = o; fill->csy_layer = csy_layer; }
-        o = cv.take(lnp_layer * c->L);      if (fill) { fill->w_lnp = o; fill->lnp_layer = lnp_layer; }
-        o = cv.take((size_t)c->L * E * 64 * 4);  if (fill) fill->w_Gd = o;
-        o = cv.take((size_t)c->L * E * 64 * 4);  if (fill) fill->w_Gu = o;
+        w.tn_layer = (size_t)tch * E * 64 * 4; w.csx_layer = (size_t)tch * E * 4; w.csy_layer = (size_t)tch * 64 * 4;
+        w.lnp_layer = (size_t)lnb * 3 * E * 4;
+        w.w_dpre = cv.take(T * 64 * es);
+        w.w_dpre2 = cv.take(T * 64 * es);       // d pre alternates: the deferred d W_down product reads the previous one
+        w.w_dht = cv.take(T * E * 4);
+        w.w_dhb = cv.take(T * E * es);
+        w.w_tnU = cv.take(w.tn_layer * c->L);
+        w.w_tnD = cv.take(w.tn_layer * c->L);
+        w.w_csx = cv.take(w.csx_layer * c->L);
+        w.w_csy = cv.take(w.csy_layer * c->L);
+        w.w_lnp = cv.take(w.lnp_layer * c->L);
+        w.w_Gd = cv.take((size_t)c->L * E * 64 * 4);
+        w.w_Gu = cv.take((size_t)c->L * E * 64 * 4);
     }
     const size_t Bz = (size_t)B, D = c->D, Cc = c->C;
-    o = cv.take(Bz * c->G2 * (size_t)c->Kpatch * es);      if (fill) fill->w_patches = o;
-    o = cv.take(Bz * E * es);      if (fill) fill->w_xpost = o;
-    o = cv.take(Bz * D * 4);      if (fill) fill->w_feat = o;
-    o = cv.take(Bz * 4);          if (fill) fill->w_pmean = o;
-    o = cv.take(Bz * 4);          if (fill) fill->w_prstd = o;
-    o = cv.take(Bz * D * 4);      if (fill) fill->w_ybn = o;
-    o = cv.take(D * 4);           if (fill) fill->w_bnrstd = o;
-    o = cv.take(Bz * Cc * 4);     if (fill) fill->w_logits = o;
-    o = cv.take(Bz * Cc * 4);     if (fill) fill->w_dlogits = o;
-    o = cv.take(Bz * D * 4);      if (fill) fill->w_dybn = o;
-    o = cv.take(Bz * D * 4);      if (fill) fill->w_dfeat = o;
-    o = cv.take(Bz * D * es);      if (fill) fill->w_dfeatb = o;
-    o = cv.take(Bz * E * 4);      if (fill) fill->w_dxpost = o;
-    *total = cv.off;
+    w.w_patches = cv.take(Bz * c->G2 * (size_t)c->Kpatch * es);
+    w.w_xpost = cv.take(Bz * E * es);
+    w.w_feat = cv.take(Bz * D * 4);
+    w.w_pmean = cv.take(Bz * 4);
+    w.w_prstd = cv.take(Bz * 4);
+    w.w_ybn = cv.take(Bz * D * 4);
+    w.w_bnrstd = cv.take(D * 4);
+    w.w_logits = cv.take(Bz * Cc * 4);
+    w.w_dlogits = cv.take(Bz * Cc * 4);
+    w.w_dybn = cv.take(Bz * D * 4);
+    w.w_dfeat = cv.take(Bz * D * 4);
+    w.w_dfeatb = cv.take(Bz * D * es);
+    w.w_dxpost = cv.take(Bz * E * 4);
+    w.total = cv.off;
+    return w;
 }
 
 template <typename T>
@@ -271,8 +321,7 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
 
     // ---- weight arena -------------------------------------------------------------
     c->blk = new (std::nothrow) BlockArena[c->L];
-    c->sav = new (std::nothrow) LayerSaved[c->L];
-    if (!c->blk || !c->sav) { pevit_set_error("ctx_create: out of host memory"); pevit_ctx_destroy(c); return -1; }
+    if (!c->blk) { pevit_set_error("ctx_create: out of host memory"); pevit_ctx_destroy(c); return -1; }
     Carver cv;
     const size_t E = c->E;
     for (int l = 0; l < c->L; ++l) {
@@ -346,20 +395,14 @@ extern "C" void pevit_ctx_destroy(pevit_ctx* c) {
     delete[] c->prof_bytes;
     delete[] c->prof_ms;
     delete[] c->prof_shape;
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->side) (void)hipStreamDestroy(c->side);
     delete[] c->blk;
-    delete[] c->sav;
     delete c;
 }
 
 extern "C" size_t pevit_arena_bytes(const pevit_ctx* c) { return c ? c->arena_bytes : 0; }
 extern "C" size_t pevit_workspace_bytes(const pevit_ctx* c, int batch) {
     if (!c || batch <= 0) return 0;
-    size_t total = 0;
-    layout_workspace(const_cast<pevit_ctx*>(c), batch, nullptr, &total, nullptr);
-    return total;
+    return layout_workspace(c, batch).total;
 }
 extern "C" size_t pevit_num_tower_params(const pevit_ctx* c) { return c ? c->n_tower : 0; }
 extern "C" size_t pevit_num_params(const pevit_ctx* c) { return c ? c->n_total : 0; }
@@ -434,10 +477,10 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
         HIP_OK(hipMemsetAsync(A + b.wqkvT, 0, E * (size_t)c->NQ * 2, s));
         const size_t skip = align_up((size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4, 256);    // the stream-K flags stay zero
         // 3E*E floats of the bound workspace serve as packing scratch: whatever activations a previous forward saved there
-        // are overwritten, so a backward through them is refused from here on (saved_batch = 0), and the load must be
+        // are overwritten, so a backward through them is refused from here on, and the load must be
         // issued on the stream the engine trains on (include/pevit_hip.h: one stream per context)
         float* tmp = at<float>(c->ws, skip);
-        c->saved_batch = 0; c->saved_kind = 0;
+        c->saved = SavedForward{};
         if (skip + (size_t)3 * E * E * 4 > c->ws_bytes_for_max) { pevit_set_error("load_block: workspace too small for the fp8 packing scratch"); return -1; }
         CHECK(pevit_launch_dequant_rows_fp8(at<u8>(A, b.wqkv), e, at<float>(A, b.sqkv), 3 * e, e, tmp, s));
         CHECK(pevit_launch_transpose_bf16(tmp, 3 * e, e, at<bf16>(A, b.wqkvT), c->NQ, 0, 1.0f, s));
@@ -474,14 +517,18 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
 // ------------------------------------------------------------------------------------
 namespace {
 
-// the forward the saved activations belong to, for error messages
-const char* saved_name(const pevit_ctx* c) {
-    switch (c->saved_kind) {
-        case 1: return "transformer_forward";
-        case 2: return "visual_forward";
-        case 3: return "attention_forward";
-        default: return "none";
-    }
+// a backward runs on the activations of the forward it asks for (kind, batch and, for the attention seam, layer) or is refused
+int check_saved(const pevit_ctx* c, Saved want, int B, int layer, const char* who) {
+    const SavedForward& f = c->saved;
+    if (f.kind == want && f.batch == B && (want != Saved::attention || f.layer == layer)) return 0;
+    static const char* const wanted[] = {"", "a blocks/transformer forward", "a visual_forward", "an attention_forward"};
+    static const char* const name[] = {"none", "transformer_forward", "visual_forward", "attention_forward"};
+    char want_l[32] = "", have_l[32] = "";
+    if (want == Saved::attention) snprintf(want_l, sizeof(want_l), " of layer %d", layer);
+    if (f.kind == Saved::attention) snprintf(have_l, sizeof(have_l), " of layer %d", f.layer);
+    pevit_set_error("%s: the saved activations are not those of %s%s with batch %d (saved: batch %d, %s%s)", who, wanted[(int)want],
+                    want_l, B, f.batch, name[(int)f.kind], have_l);
+    return -1;
 }
 
 int check_ready(pevit_ctx* c, int B, const char* who) {
@@ -561,7 +608,7 @@ void prof_close(pevit_ctx* c, hipStream_t s, int slot, double flops, double byte
 int gemm(pevit_ctx* c, int epi, const GemmParams& p_in, hipStream_t s) {
     GemmParams p = p_in;
     if (c->sk_slots && c->ws) {
-        p.sk_flag = at<unsigned>(c->ws, c->w_skflag); p.sk_slab = at<float>(c->ws, c->w_skslab); p.sk_slots = c->sk_slots;
+        p.sk_flag = at<unsigned>(c->ws, c->lay.w_skflag); p.sk_slab = at<float>(c->ws, c->lay.w_skslab); p.sk_slots = c->sk_slots;
     }
     const int slot = prof_open(c, s, true);
     const int rc = c->f32 ? pevit_launch_gemm_f32(epi, p, s) : pevit_launch_gemm(epi, p, c->tune, s);
@@ -597,12 +644,12 @@ GemmParams gpw(const pevit_ctx* c, const bf16* A, int lda, size_t w_off, int ldb
 // The attention half of block l between ln_1 and out_proj (MultiheadAttention.forward, model.py:612-812): the QKV product with the
 // adapter columns t of the attention-site methods, delta-add and the attention core.  Reads the layer's xn1 (or its e4m3 copy a8),
 // leaves q / k / v in the head layout, lse and attn_out in the layer's saved slots.  Shared by the block walk and the attention seam.
-int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, int l, unsigned char* a8, unsigned char* attn8) {
+int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, unsigned char* a8, unsigned char* attn8) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
     char* W = c->ws; char* A = c->arena;
-    const bool site = attention_site(c);
+    const bool site = pl.site;
     const BlockArena& b = c->blk[l];
-    const LayerSaved& v = c->sav[l];
+    const LayerSaved& v = c->lay.sav[l];
     bf16* qkv = at<bf16>(W, v.qkv);
     const size_t plane = (size_t)T * E;
     if (!c->fp8) {
@@ -618,7 +665,7 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, int l, unsigned char* a8, 
         if (a8) { p.A = reinterpret_cast<const bf16*>(a8); p.a_fp8 = 1; }
         p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.E = E; p.H = H; p.Ntok = N;
         bool tail = false;
-        if (site && !a8 && c->fp8_tail) {
+        if (pl.fp8_tail) {
             GemmParams m = p;
             m.N = c->NQ; m.B2 = at<bf16>(A, b.wpan); m.ldb2 = E; m.Nb2 = 128; m.n_fp8 = 3 * E; m.outf = at<float>(W, v.t); m.ldo = 64;
             if (pevit_gemm_mixed_ok(m, c->tune)) { p = m; tail = true; }
@@ -632,15 +679,7 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, int l, unsigned char* a8, 
     }
     const float* dbias = nullptr;
     if (c->d.method == PEVIT_KADAPTATION) dbias = c->params + c->p_layer0 + c->p_layer_stride * l + 4 * (size_t)E;
-    // delta-add and the attention core as ONE launch where a run of heads owns whole reference rows of the raw reshape
-    // (attn_delta.hip: N <= 64; ViT-B/32), otherwise delta_add + attn_fwd
-    // ... unless its one-workgroup-per-CU runs leave between a quarter and three quarters of the chip empty (measured at batch
-    // 64: 128 runs for 256 CUs, the two kernels are 0.6 % of the step faster; fused_attn_delta = 2 forces the fused form)
-    const int ad_hpw = pevit_attn_delta_hpw(B, H, N);
-    const int ad_runs = ad_hpw > 0 ? (B * H + ad_hpw - 1) / ad_hpw : 0;
-    const bool ad_fill = ad_hpw > 0 && (c->fused_attn_delta > 1 || 4 * ad_runs >= 3 * pevit_num_cus() || 4 * ad_runs <= pevit_num_cus());
-    const bool fused_ad = site && c->fused_attn_delta && !c->f32 && !attn8 && ad_fill;
-    if (fused_ad) {
+    if (pl.attn_delta) {
         PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T, (double)T * E * (3 + 2 + 1) * 2 + (double)T * 64 * 4 + (double)B * H * N * 4,   // q, k, v in; q', v', out
              pevit_launch_attn_fwd_delta(qkv, qkv + plane, qkv + 2 * plane, at<float>(W, v.t), at<bf16>(A, b.q16), dbias, c->ascale,
                                          at<bf16>(W, v.attn_out), E, at<float>(W, v.lse), B, H, N, s));
@@ -665,26 +704,26 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, int l, unsigned char* a8, 
 // already hold the input; the output lands in ws + w_xfinal.
 // cls_only: the caller consumes only the class token of the last block (VisionTransformer.forward,
 // model.py:1046) -- everything of the last block that sits after the attention core is then
-// evaluated on the B class-token rows only (identical results, ~6 % fewer FLOPs per step).
-int blocks_forward(pevit_ctx* c, hipStream_t s, int B, bool cls_only, int l_lo = 0, int l_hi = -1) {
+// evaluated on the B class-token rows only (identical results, ~6 % fewer FLOPs per step).  Never with post-MLP adapters
+// (StepPlan::cls_prune).
+int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool cls_only, int l_lo = 0, int l_hi = -1) {
     if (l_hi < 0) l_hi = c->L;
     const int E = c->E, T = B * c->N, N = c->N;
-    cls_only = cls_only && !post_mlp(c);
     char* W = c->ws; char* A = c->arena;
-    if (attention_site(c) || post_mlp(c)) CHECK(prep_adapters(c, s));
+    if (pl.site || pl.post_mlp) CHECK(prep_adapters(c, s));
     for (int l = l_lo; l < l_hi; ++l) {
         const BlockArena& b = c->blk[l];
-        const LayerSaved& v = c->sav[l];
+        const LayerSaved& v = c->lay.sav[l];
         float* x_in = at<float>(W, v.x_in);
         float* x_mid = at<float>(W, v.x_mid);
-        float* x_out = (l + 1 < c->L) ? at<float>(W, c->sav[l + 1].x_in) : at<float>(W, c->w_xfinal);
+        float* x_out = (l + 1 < c->L) ? at<float>(W, c->lay.sav[l + 1].x_in) : at<float>(W, c->lay.w_xfinal);
         // x = x + attn(ln_1(x))                                         model.py:973
-        unsigned char* a8 = c->fp8act ? at<unsigned char>(W, c->w_a8) : nullptr;
-        unsigned char* attn8 = c->fp8act ? at<unsigned char>(W, c->w_attn8) : nullptr;
+        unsigned char* a8 = c->fp8act ? at<unsigned char>(W, c->lay.w_a8) : nullptr;
+        unsigned char* attn8 = c->fp8act ? at<unsigned char>(W, c->lay.w_attn8) : nullptr;
         PROF(c, s, PEVIT_PROF_LN_FWD, T, (double)T * E * (4 + c->es),
              pevit_launch_ln_fwd(x_in, at<float>(A, b.ln1w), at<float>(A, b.ln1b), T, E, at<bf16>(W, v.xn1), nullptr,
                                  at<float>(W, v.mean1), at<float>(W, v.rstd1), s, 0, c->f32, a8));
-        CHECK(attn_core_fwd(c, s, B, l, a8, attn8));
+        CHECK(attn_core_fwd(c, s, B, pl, l, a8, attn8));
         // rows of the tail of this block: all T, or (last block, cls_only) the B class-token rows, which
         // sit N*E elements apart in every [T][E] buffer
         const bool cls = cls_only && l == c->L - 1;
@@ -698,290 +737,234 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, bool cls_only, int l_lo =
         }
         // x = x + mlp(ln_2(x))                                          model.py:974
         PROF(c, s, PEVIT_PROF_LN_FWD, R, (double)R * E * (4 + c->es),
-             pevit_launch_ln_fwd(x_mid, at<float>(A, b.ln2w), at<float>(A, b.ln2b), R, E, at<bf16>(W, c->w_xn2), nullptr,
+             pevit_launch_ln_fwd(x_mid, at<float>(A, b.ln2w), at<float>(A, b.ln2b), R, E, at<bf16>(W, c->lay.w_xn2), nullptr,
                                  at<float>(W, v.mean2), at<float>(W, v.rstd2), s, (size_t)rs, c->f32, a8));
         {
-            GemmParams p = gpw(c, at<bf16>(W, c->w_xn2), E, b.wfc, E, 4 * E, R, 4 * E, E, b.sfc);
+            GemmParams p = gpw(c, at<bf16>(W, c->lay.w_xn2), E, b.wfc, E, 4 * E, R, 4 * E, E, b.sfc);
             if (a8) { p.A = reinterpret_cast<const bf16*>(a8); p.a_fp8 = 1; p.out2_fp8 = 1; }     // gelu(h) leaves as e4m3 codes
-            p.bias = at<float>(A, b.bfc); p.outb = at<bf16>(W, v.h); p.ldob = 4 * E; p.outb2 = at<bf16>(W, c->w_g);
+            p.bias = at<float>(A, b.bfc); p.outb = at<bf16>(W, v.h); p.ldob = 4 * E; p.outb2 = at<bf16>(W, c->lay.w_g);
             p.ldob2 = 4 * E;
             CHECK(gemm(c, EPI_BIAS_GELU, p, s));
         }
-        if (cls) {
-            GemmParams p = gpw(c, at<bf16>(W, c->w_g), 4 * E, b.wpr, 4 * E, E, R, E, 4 * E, b.spr);
+        if (!pl.post_mlp) {
+            GemmParams p = gpw(c, at<bf16>(W, c->lay.w_g), 4 * E, b.wpr, 4 * E, E, R, E, 4 * E, b.spr);
             if (a8) p.a_fp8 = 1;
             p.bias = at<float>(A, b.bpr); p.resid = x_mid; p.ldr = rs; p.outf = x_out; p.ldo = rs;
             CHECK(gemm(c, EPI_BIAS_RESID_F32, p, s));
             continue;
         }
-        if (!post_mlp(c)) {
-            GemmParams p = gpw(c, at<bf16>(W, c->w_g), 4 * E, b.wpr, 4 * E, E, T, E, 4 * E, b.spr);
-            if (a8) p.a_fp8 = 1;
-            p.bias = at<float>(A, b.bpr); p.resid = x_mid; p.ldr = E; p.outf = x_out; p.ldo = E;
-            CHECK(gemm(c, EPI_BIAS_RESID_F32, p, s));
-        } else {
-            // x = x + [h + up(act(down(LN_a(h))))]         adapter_model.py:330-336 / compacter_model.py:497-503
-            const float* lp = c->params + c->p_layer0 + c->p_layer_stride * l;
-            if (c->adapter_fused && !c->f32 && !c->fused_bn && pevit_adapter_fused_ok(E)) {
-                // two launches (adapter_fused.hip): c_proj writes its accumulators once (the bias joins in the adapter kernel), then
-                // LayerNorm -> down -> activation -> up -> residual for 32 rows per workgroup
-                GemmParams p = gp(at<bf16>(W, c->w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
-                p.outf = at<float>(W, v.hf32); p.ldo = E;
-                CHECK(gemm(c, EPI_F32, p, s));
-                PROF(c, s, PEVIT_PROF_ADAPTER_FWD, T, (double)T * E * (4 + 4 + 4 + 2) + (double)T * 64 * 4,
-                     pevit_launch_adapter_fwd(c->d.method == PEVIT_ADAPTER ? 0 : 1, at<float>(W, v.hf32), at<float>(A, b.bpr), x_mid, lp + c->o_nw,
-                                              lp + c->o_nb, at<bf16>(A, b.wd), lp + c->o_db, at<bf16>(A, b.wu), lp + c->o_ub, at<bf16>(W, v.z),
-                                              at<float>(W, v.mean_a), at<float>(W, v.rstd_a), at<bf16>(W, v.act), at<bf16>(W, v.apre), x_out,
-                                              T, E, s));
-                continue;
-            }
-            float* ytmp = at<float>(W, c->w_dxn);           // x_mid + h ; scratch that is free during the forward pass
-            {
-                GemmParams p = gp(at<bf16>(W, c->w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
-                p.bias = at<float>(A, b.bpr); p.resid = x_mid; p.ldr = E; p.outf = ytmp; p.ldo = E;
-                p.outf2 = at<float>(W, v.hf32); p.ldo2 = E;
-                CHECK(gemm(c, EPI_BIAS_RESID_KEEP, p, s));
-            }
-            CHECK(pevit_launch_ln_fwd(at<float>(W, v.hf32), lp + c->o_nw, lp + c->o_nb, T, E, at<bf16>(W, v.z), nullptr,
-                                      at<float>(W, v.mean_a), at<float>(W, v.rstd_a), s, 0, c->f32));
-            if (c->fused_bn && !c->f32) {
-                // down -> activation -> up (+ bias + x_mid + h) in one launch (adapter.hip bottleneck_pair_kernel)
-                CHECK(pevit_launch_bottleneck_pair(c->d.method == PEVIT_ADAPTER ? 0 : 1, at<bf16>(W, v.z), E, at<bf16>(A, b.wd), lp + c->o_db,
-                                                   nullptr, at<bf16>(W, v.act), at<bf16>(W, v.apre), at<bf16>(A, b.wu), lp + c->o_ub, ytmp,
-                                                   x_out, T, E, s));
+        // x = x + [h + up(act(down(LN_a(h))))]         adapter_model.py:330-336 / compacter_model.py:497-503
+        const float* lp = c->params + c->p_layer0 + c->p_layer_stride * l;
+        if (pl.adapter_fused) {
+            // two launches (adapter_fused.hip): c_proj writes its accumulators once (the bias joins in the adapter kernel), then
+            // LayerNorm -> down -> activation -> up -> residual for 32 rows per workgroup
+            GemmParams p = gp(at<bf16>(W, c->lay.w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
+            p.outf = at<float>(W, v.hf32); p.ldo = E;
+            CHECK(gemm(c, EPI_F32, p, s));
+            PROF(c, s, PEVIT_PROF_ADAPTER_FWD, T, (double)T * E * (4 + 4 + 4 + 2) + (double)T * 64 * 4,
+                 pevit_launch_adapter_fwd(c->d.method == PEVIT_ADAPTER ? 0 : 1, at<float>(W, v.hf32), at<float>(A, b.bpr), x_mid, lp + c->o_nw,
+                                          lp + c->o_nb, at<bf16>(A, b.wd), lp + c->o_db, at<bf16>(A, b.wu), lp + c->o_ub, at<bf16>(W, v.z),
+                                          at<float>(W, v.mean_a), at<float>(W, v.rstd_a), at<bf16>(W, v.act), at<bf16>(W, v.apre), x_out,
+                                          T, E, s));
+            continue;
+        }
+        float* ytmp = at<float>(W, c->lay.w_dxn);           // x_mid + h ; scratch that is free during the forward pass
+        {
+            GemmParams p = gp(at<bf16>(W, c->lay.w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
+            p.bias = at<float>(A, b.bpr); p.resid = x_mid; p.ldr = E; p.outf = ytmp; p.ldo = E;
+            p.outf2 = at<float>(W, v.hf32); p.ldo2 = E;
+            CHECK(gemm(c, EPI_BIAS_RESID_KEEP, p, s));
+        }
+        CHECK(pevit_launch_ln_fwd(at<float>(W, v.hf32), lp + c->o_nw, lp + c->o_nb, T, E, at<bf16>(W, v.z), nullptr,
+                                  at<float>(W, v.mean_a), at<float>(W, v.rstd_a), s, 0, c->f32));
+        {
+            GemmParams p = gp(at<bf16>(W, v.z), E, at<bf16>(A, b.wd), E, 64, T, 64, E);
+            p.bias = lp + c->o_db;
+            if (c->d.method == PEVIT_ADAPTER) {
+                p.outb = at<bf16>(W, v.act); p.ldob = 64;
+                CHECK(gemm(c, EPI_BIAS_RELU_BF16, p, s));
             } else {
-            {
-                    GemmParams p = gp(at<bf16>(W, v.z), E, at<bf16>(A, b.wd), E, 64, T, 64, E);
-                    p.bias = lp + c->o_db;
-                    if (c->d.method == PEVIT_ADAPTER) {
-                        p.outb = at<bf16>(W, v.act); p.ldob = 64;
-                        CHECK(gemm(c, EPI_BIAS_RELU_BF16, p, s));
-                    } else {
-                        p.outb = at<bf16>(W, v.apre); p.ldob = 64; p.outb2 = at<bf16>(W, v.act); p.ldob2 = 64;
-                        CHECK(gemm(c, EPI_BIAS_GELUNEW, p, s));
-                    }
-                }
-                {
-                    GemmParams p = gp(at<bf16>(W, v.act), 64, at<bf16>(A, b.wu), 64, E, T, E, 64);
-                    p.bias = lp + c->o_ub; p.resid = ytmp; p.ldr = E; p.outf = x_out; p.ldo = E;
-                    CHECK(gemm(c, EPI_BIAS_RESID_F32, p, s));
-                }
+                p.outb = at<bf16>(W, v.apre); p.ldob = 64; p.outb2 = at<bf16>(W, v.act); p.ldob2 = 64;
+                CHECK(gemm(c, EPI_BIAS_GELUNEW, p, s));
             }
+        }
+        {
+            GemmParams p = gp(at<bf16>(W, v.act), 64, at<bf16>(A, b.wu), 64, E, T, E, 64);
+            p.bias = lp + c->o_ub; p.resid = ytmp; p.ldr = E; p.outf = x_out; p.ldo = E;
+            CHECK(gemm(c, EPI_BIAS_RESID_F32, p, s));
         }
     }
     return 0;
 }
 
-// Cross-layer state of the attention-site adapter gradients over one backward walk (block walk or attention seam): the optional
-// side stream of the token-contracted products, and the dP of the previously processed layer that lowrank_combo defers by one launch.
+// Cross-layer state of the attention-site adapter gradients over one backward walk (block walk or attention seam): the dP of the
+// previously processed layer that lowrank_combo defers by one launch.
 struct AttnGradWalk {
-    bool use_side = false, combo = false, side_pending = false;
     int prev_layer = -1, u_par = 0;
     float* u_last = nullptr;
 };
 
-int attn_walk_begin(pevit_ctx* c, AttnGradWalk& w) {
-    const bool site = attention_site(c);
-    w.use_side = c->side_stream && site;
-    w.combo = c->lowrank_combo && site && !c->f32 && !w.use_side;
-    if (w.use_side && !c->side) {
-        HIP_OK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
-    return 0;
-}
-
 // The attention half of block l's backward (the autograd of model.py:612-812 without the QKV dX product): ws+w_dyb (bf16, fp8: with
 // out_proj's channel scales folded in) -> out_proj dX -> attention backward into dqkv -> the low-rank adapter gradient partials of
 // the attention-site methods.  cls: class-token pruning of the last block (only the B class-token rows of dyb are defined).
-int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, int l, bool cls, AttnGradWalk& w) {
+int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, bool cls, AttnGradWalk& w) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
     char* W = c->ws; char* A = c->arena;
-    const bool site = attention_site(c);
     const int chunks = pevit_lowrank_chunks(T);
     const BlockArena& b = c->blk[l];
-    const LayerSaved& v = c->sav[l];
+    const LayerSaved& v = c->lay.sav[l];
     bf16* qkv = at<bf16>(W, v.qkv);
-    bf16* dqkv = at<bf16>(W, c->w_dqkv);
-    bf16* dyb = at<bf16>(W, c->w_dyb);
+    bf16* dqkv = at<bf16>(W, c->lay.w_dqkv);
+    bf16* dyb = at<bf16>(W, c->lay.w_dyb);
     const size_t plane = (size_t)T * E;
     const int R = cls ? B : T;
     const int rs = cls ? N * E : E;            // row stride of [T][E] buffers
     {
         GemmParams p = gpw(c, dyb, rs, b.woT, E, E, R, E, E, 0);
-        p.outb = at<bf16>(W, c->w_dO); p.ldob = rs;
+        p.outb = at<bf16>(W, c->lay.w_dO); p.ldob = rs;
         CHECK(gemm(c, EPI_BF16, p, s));
     }
-    // dqkv / u32 are about to be overwritten: the previous layer's gradient contraction must have read them
-    if (w.side_pending) { HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0)); w.side_pending = false; }
     if (c->f32)
         CHECK(pevit_launch_attn_bwd_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), (const float*)eadv(c, qkv, 2 * plane),
-                                        at<float>(W, v.attn_out), E, at<float>(W, c->w_dO), E, at<float>(W, v.lse), (float*)dqkv,
+                                        at<float>(W, v.attn_out), E, at<float>(W, c->lay.w_dO), E, at<float>(W, v.lse), (float*)dqkv,
                                         c->NQ, B, H, N, s));
     else
         PROF(c, s, PEVIT_PROF_ATTN_BWD, T, (double)T * E * (N <= 64 ? 7 : 8) * 2 + (double)B * H * N * 4,     // q, k, v, (out: N > 64 only), dout in; dq, dk, dv out
-             pevit_launch_attn_bwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<bf16>(W, c->w_dO), E,
+             pevit_launch_attn_bwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<bf16>(W, c->lay.w_dO), E,
                                    at<float>(W, v.lse), dqkv, c->NQ, B, H, N, s, (cls && N <= 64) ? 1 : 0));
-    if (site && w.combo) {
+    float* partial = at<float>(W, c->lay.w_partial + (size_t)l * c->lay.partial_layer);
+    float* dbias = at<float>(W, c->lay.w_dbias + (size_t)l * c->lay.dbias_layer);
+    if (pl.lowrank_combo) {
         // u, dQ_q, dQ_v, d bias of this layer and the dP of the layer before it in ONE launch (lowrank.hip lowrank_combo_kernel)
-        float* u_cur = at<float>(W, w.u_par ? c->w_u32b : c->w_u32);
-        const LayerSaved* pv = w.prev_layer >= 0 ? &c->sav[w.prev_layer] : nullptr;
+        float* u_cur = at<float>(W, w.u_par ? c->lay.w_u32b : c->lay.w_u32);
+        const LayerSaved* pv = w.prev_layer >= 0 ? &c->lay.sav[w.prev_layer] : nullptr;
         PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 3 * 2 + (double)T * 64 * 14 + (double)chunks * 4 * E * 32 * 4,
-             pevit_launch_lowrank_combo(1, pv ? 1 : 0, dqkv, c->NQ, at<bf16>(A, b.qT), u_cur, dqkv + 3 * E, at<float>(W, v.t),
-                                        at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
-                                        at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer),
+             pevit_launch_lowrank_combo(1, pv ? 1 : 0, dqkv, c->NQ, at<bf16>(A, b.qT), u_cur, dqkv + 3 * E, at<float>(W, v.t), partial, dbias,
                                         pv ? at<bf16>(W, pv->xn1) : nullptr, E, w.u_last,
-                                        pv ? at<float>(W, c->w_partial + (size_t)w.prev_layer * c->partial_layer) : nullptr, B, H, N, E, s));
+                                        pv ? at<float>(W, c->lay.w_partial + (size_t)w.prev_layer * c->lay.partial_layer) : nullptr, B, H, N, E, s));
         w.u_last = u_cur; w.prev_layer = l; w.u_par ^= 1;
-    } else if (site) {
-        if (c->f32)
-            CHECK(pevit_launch_lowrank_u_f32((const float*)dqkv, c->NQ, at<float>(A, b.q32), at<float>(W, c->w_u32),
-                                             (float*)eadv(c, dqkv, 3 * (size_t)E), B, H, N, E, s));
-        else
+    } else if (pl.site) {
+        float* u32 = at<float>(W, c->lay.w_u32);
+        if (c->f32) {
+            CHECK(pevit_launch_lowrank_u_f32((const float*)dqkv, c->NQ, at<float>(A, b.q32), u32, (float*)eadv(c, dqkv, 3 * (size_t)E), B, H,
+                                             N, E, s));
+            CHECK(pevit_launch_lowrank_grad_f32(at<float>(W, v.xn1), E, u32, (const float*)dqkv, c->NQ, at<float>(W, v.t), partial, dbias,
+                                                chunks, B, H, N, E, s));
+        } else {
             PROF(c, s, PEVIT_PROF_LOWRANK_U, T, (double)T * E * 2 * 2 + (double)T * 64 * 6,
-                 pevit_launch_lowrank_u(dqkv, c->NQ, at<bf16>(A, b.qT), at<float>(W, c->w_u32), dqkv + 3 * E, B, H, N, E, s));
-        // the token-contracted adapter gradients feed nothing before the end of the step: run them beside
-        // the QKV-backward GEMM / LayerNorm backward / next layer's MLP GEMMs on the second stream
-        hipStream_t gs = s;
-        if (w.use_side) {
-            HIP_OK(hipEventRecord(c->ev_fork, s));
-            HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-            gs = c->side;
+                 pevit_launch_lowrank_u(dqkv, c->NQ, at<bf16>(A, b.qT), u32, dqkv + 3 * E, B, H, N, E, s));
+            PROF(c, s, PEVIT_PROF_LOWRANK_GRAD, T, (double)T * E * 3 * 2 + (double)T * 64 * 8 + (double)chunks * 4 * E * 32 * 4,
+                 pevit_launch_lowrank_grad(at<bf16>(W, v.xn1), E, u32, dqkv, c->NQ, at<float>(W, v.t), partial, dbias, chunks, B, H, N, E, s,
+                                           pl.lowrank_xcd));
         }
-        if (c->f32)
-            CHECK(pevit_launch_lowrank_grad_f32(at<float>(W, v.xn1), E, at<float>(W, c->w_u32), (const float*)dqkv, c->NQ,
-                                                at<float>(W, v.t), at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
-                                                at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer), chunks, B, H, N, E, gs));
-        else
-            PROF(c, gs, PEVIT_PROF_LOWRANK_GRAD, T, (double)T * E * 3 * 2 + (double)T * 64 * 8 + (double)chunks * 4 * E * 32 * 4,
-                 pevit_launch_lowrank_grad(at<bf16>(W, v.xn1), E, at<float>(W, c->w_u32), dqkv, c->NQ, at<float>(W, v.t),
-                                           at<float>(W, c->w_partial + (size_t)l * c->partial_layer),
-                                           at<float>(W, c->w_dbias + (size_t)l * c->dbias_layer), chunks, B, H, N, E, gs, c->lowrank_xcd));
-        if (w.use_side) { HIP_OK(hipEventRecord(c->ev_join, c->side)); w.side_pending = true; }
     }
     return 0;
 }
 
 // QKV dX of block l: dqkv (incl. the 64 adapter columns u of the attention-site methods) -> the gradient of the attention input.
 // dx_f32 == nullptr: into ws+w_dxn in the block walk's hand-over type (bf16 with dx_stored, for LayerNorm backward); else f32 [T][E].
-int attn_qkv_dx(pevit_ctx* c, hipStream_t s, int B, int l, float* dx_f32) {
+int attn_qkv_dx(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, float* dx_f32) {
     const int E = c->E, T = B * c->N;
-    float* dxn = at<float>(c->ws, c->w_dxn);
-    GemmParams p = gp(at<bf16>(c->ws, c->w_dqkv), c->NQ, at<bf16>(c->arena, c->blk[l].wqkvT), c->NQ, E, T, E,
-                      attention_site(c) ? c->NQ : 3 * E);
+    float* dxn = at<float>(c->ws, c->lay.w_dxn);
+    GemmParams p = gp(at<bf16>(c->ws, c->lay.w_dqkv), c->NQ, at<bf16>(c->arena, c->blk[l].wqkvT), c->NQ, E, T, E, pl.site ? c->NQ : 3 * E);
     if (dx_f32) { p.outf = dx_f32; p.ldo = E; CHECK(gemm(c, EPI_F32, p, s)); }
-    else if (c->dx_stored) { p.outb = reinterpret_cast<bf16*>(dxn); p.ldob = E; CHECK(gemm(c, EPI_BF16, p, s)); }
+    else if (pl.dx_stored) { p.outb = reinterpret_cast<bf16*>(dxn); p.ldob = E; CHECK(gemm(c, EPI_BF16, p, s)); }
     else { p.outf = dxn; p.ldo = E; CHECK(gemm(c, EPI_F32, p, s)); }
     return 0;
 }
 
-// end of a walk: join the side stream, and the deferred dP of the last layer walked
+// end of a walk: the deferred dP of the last layer walked (lowrank_combo)
 int attn_walk_end(pevit_ctx* c, hipStream_t s, int B, AttnGradWalk& w) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
-    if (w.side_pending) { HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0)); w.side_pending = false; }
-    if (w.combo && w.prev_layer >= 0)       // the dP of the last layer walked
+    if (w.prev_layer >= 0)
         PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 2 + (double)T * 64 * 4,
-             pevit_launch_lowrank_combo(0, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at<bf16>(c->ws, c->sav[w.prev_layer].xn1), E,
-                                        w.u_last, at<float>(c->ws, c->w_partial + (size_t)w.prev_layer * c->partial_layer), B, H, N, E, s));
+             pevit_launch_lowrank_combo(0, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at<bf16>(c->ws, c->lay.sav[w.prev_layer].xn1), E,
+                                        w.u_last, at<float>(c->ws, c->lay.w_partial + (size_t)w.prev_layer * c->lay.partial_layer), B, H, N, E, s));
     w.prev_layer = -1;
     return 0;
 }
 
-// backward of the blocks.  On entry ws+w_dxa holds dL/dx_final (f32) and ws+w_dyb its bf16 copy.
+int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l_lo, int l_hi);
+
+// backward of the blocks.  On entry ws+w_dxa holds dL/dx_final (f32) and ws+w_dyb its bf16 copy (StepPlan::gstream16: only
+// the bf16 copy is read).
 // On exit ws+w_dxa holds dL/dx_0 if need_dx0.
 // cls_only mirrors blocks_forward: on entry only the class-token rows of dxa / dyb are defined (and
 // read); dxb and dO must have been zeroed by the caller.
 // Layers l_hi-1 .. l_lo are processed (the whole tower: L, 0) and the adapter gradients of exactly these layers are
 // reduced and chained onto the reference's tensors at the end -- data parallelism runs the tower in two halves so that
 // the all-reduce of the upper half's gradients overlaps the backward of the lower half.
-// the residual GRADIENT stream lives in bf16 only (pevit_ctx::gstream16): attention-site adapters, and the post-MLP adapters on
-// their fused kernels; bf16 / fp8 weights (never the f32 verification mode)
-bool gstream16_on(const pevit_ctx* c) {
-    if (!c->gstream16 || c->f32 || !c->dx_stored) return false;
-    if (attention_site(c)) return true;
-    return post_mlp(c) && c->adapter_fused && !c->fused_bn && pevit_adapter_fused_ok(c->E);
-}
-
-int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, int l_lo, int l_hi);
-
-int blocks_backward(pevit_ctx* c, hipStream_t s, int B, bool need_dx0, bool cls_only, int l_hi, int l_lo) {
+int blocks_backward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool need_dx0, bool cls_only, int l_hi, int l_lo) {
     const int E = c->E, T = B * c->N, N = c->N;
-    cls_only = cls_only && !post_mlp(c);
     char* W = c->ws; char* A = c->arena;
-    float* dxa = at<float>(W, c->w_dxa);
-    float* dxb = at<float>(W, c->w_dxb);
-    bf16* dyb = at<bf16>(W, c->w_dyb);
-    float* dxn = at<float>(W, c->w_dxn);
-    const bool gs16 = gstream16_on(c);
+    float* dxa = at<float>(W, c->lay.w_dxa);
+    float* dxb = at<float>(W, c->lay.w_dxb);
+    bf16* dyb = at<bf16>(W, c->lay.w_dyb);
+    float* dxn = at<float>(W, c->lay.w_dxn);
+    const bool gs16 = pl.gstream16;
+    // bytes LayerNorm backward moves per row element: dy (stored type or f32) + x + residual gradient read, gradient written
+    const size_t ln_bwd_bytes = (pl.dx_stored ? c->es : 4) + 4 + (gs16 ? c->es : 4 + 4) + c->es;
     AttnGradWalk walk;
-    CHECK(attn_walk_begin(c, walk));
     int tn_pend = -1, tn_par = 0;          // post-MLP adapters: layer whose d W_down product is still owed, and the d pre buffer in turn
     const bf16* tn_pend_dpre = nullptr;
     for (int l = l_hi - 1; l >= l_lo; --l) {
         const BlockArena& b = c->blk[l];
-        const LayerSaved& v = c->sav[l];
+        const LayerSaved& v = c->lay.sav[l];
         const bf16* mlp_dy = dyb;          // upstream gradient of the MLP output (bf16)
-        if (post_mlp(c)) {
+        if (pl.post_mlp) {
             // out = x_mid + h + up(act(down(LN_a(h)))) :  dx_out (dxa, dyb) flows to x_mid, to h, and into the adapter
             const float* lp = c->params + c->p_layer0 + c->p_layer_stride * l;
-            const bool fused_ad = c->adapter_fused && !c->f32 && !c->fused_bn && pevit_adapter_fused_ok(E);
-            const bool fold = fused_ad && c->adapter_tn_fold;      // both weight-gradient products inside the backward launch
-            bf16* dpre = at<bf16>(W, (fold && tn_par) ? c->w_dpre2 : c->w_dpre);
+            const bool fold = pl.tn_fold;      // both weight-gradient products inside the backward launch
+            bf16* dpre = at<bf16>(W, (fold && tn_par) ? c->lay.w_dpre2 : c->lay.w_dpre);
             // d W_up[e][j] = sum_r dx_out[r][e] act[r][j] ; d b_up = colsum(dx_out)
             if (fold) {}
             else if (c->f32)
-                CHECK(pevit_launch_tn_gemm64_f32((const float*)dyb, E, at<float>(W, v.act), 64, at<float>(W, c->w_tnU + (size_t)l * c->tn_layer),
+                CHECK(pevit_launch_tn_gemm64_f32((const float*)dyb, E, at<float>(W, v.act), 64, at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer),
                                                  nullptr, nullptr, T, E, s));
             else
-                CHECK(pevit_launch_tn_gemm64(dyb, E, at<bf16>(W, v.act), 64, at<float>(W, c->w_tnU + (size_t)l * c->tn_layer),
+                CHECK(pevit_launch_tn_gemm64(dyb, E, at<bf16>(W, v.act), 64, at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer),
                                              nullptr, nullptr, T, E, s));
-            if (fused_ad) {
-                const int pl = tn_pend >= 0 ? tn_pend : l;       // the layer whose d W_down product this launch carries (if any)
+            if (pl.adapter_fused) {
+                const int dwl = tn_pend >= 0 ? tn_pend : l;       // the layer whose d W_down product this launch carries (if any)
                 // d pre, d z and the LayerNorm backward with its affine-gradient column sums in one launch (adapter_fused.hip); the
                 // forward pass left the c_proj accumulators WITHOUT their bias in hf32
                 PROF(c, s, PEVIT_PROF_ADAPTER_BWD, T, (double)T * E * (2 + 4 + 4 + 2) + (double)T * 64 * 4,
                      pevit_launch_adapter_bwd(c->d.method == PEVIT_ADAPTER ? 0 : 1, dyb, gs16 ? nullptr : dxa, at<bf16>(A, b.wuT),
                                               c->d.method == PEVIT_ADAPTER ? at<bf16>(W, v.act) : at<bf16>(W, v.apre), at<bf16>(A, b.wdT),
                                               at<float>(W, v.hf32), at<float>(A, b.bpr), at<float>(W, v.mean_a), at<float>(W, v.rstd_a),
-                                              lp + c->o_nw, dpre, at<bf16>(W, c->w_dhb), at<float>(W, c->w_lnp + (size_t)l * c->lnp_layer), T, E, s,
-                                              fold ? dyb : nullptr, at<bf16>(W, v.act), at<float>(W, c->w_tnU + (size_t)l * c->tn_layer),
-                                              (fold && tn_pend >= 0) ? at<bf16>(W, c->sav[pl].z) : nullptr, tn_pend_dpre,
-                                              at<float>(W, c->w_tnD + (size_t)pl * c->tn_layer), at<float>(W, c->w_csy + (size_t)pl * c->csy_layer),
-                                              c->adapter_tn_fold > 1 ? c->adapter_tn_fold : 0));
+                                              lp + c->o_nw, dpre, at<bf16>(W, c->lay.w_dhb), at<float>(W, c->lay.w_lnp + (size_t)l * c->lay.lnp_layer), T, E, s,
+                                              fold ? dyb : nullptr, at<bf16>(W, v.act), at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer),
+                                              (fold && tn_pend >= 0) ? at<bf16>(W, c->lay.sav[dwl].z) : nullptr, tn_pend_dpre,
+                                              at<float>(W, c->lay.w_tnD + (size_t)dwl * c->lay.tn_layer), at<float>(W, c->lay.w_csy + (size_t)dwl * c->lay.csy_layer),
+                                              pl.tn_fold_wgs));
                 if (fold) { tn_pend = l; tn_pend_dpre = dpre; tn_par ^= 1; }
-            } else if (c->fused_bn && !c->f32) {
-                // d pre = (dx_out W_up) * act'(saved) ; d z = d pre W_down, one launch
-                CHECK(pevit_launch_bottleneck_pair(c->d.method == PEVIT_ADAPTER ? 2 : 3, dyb, E, at<bf16>(A, b.wuT), nullptr,
-                                                   c->d.method == PEVIT_ADAPTER ? at<bf16>(W, v.act) : at<bf16>(W, v.apre), dpre, nullptr,
-                                                   at<bf16>(A, b.wdT), nullptr, nullptr, dxn, T, E, s));
             } else {
-            {   // d act = dx_out W_up ; d pre = d act * act'(pre)
-                GemmParams p = gp(dyb, E, at<bf16>(A, b.wuT), E, 64, T, 64, E);
-                p.outb = dpre; p.ldob = 64; p.ldaux = 64;
-                if (c->d.method == PEVIT_ADAPTER) { p.aux = at<bf16>(W, v.act); CHECK(gemm(c, EPI_DRELU_BF16, p, s)); }
-                else { p.aux = at<bf16>(W, v.apre); CHECK(gemm(c, EPI_DGELUNEW_BF16, p, s)); }
-            }
-            {   // d z = d pre W_down
-                GemmParams p = gp(dpre, 64, at<bf16>(A, b.wdT), 64, E, T, E, 64);
-                p.outf = dxn; p.ldo = E;
-                CHECK(gemm(c, EPI_F32, p, s));
-            }
+                {   // d act = dx_out W_up ; d pre = d act * act'(pre)
+                    GemmParams p = gp(dyb, E, at<bf16>(A, b.wuT), E, 64, T, 64, E);
+                    p.outb = dpre; p.ldob = 64; p.ldaux = 64;
+                    if (c->d.method == PEVIT_ADAPTER) { p.aux = at<bf16>(W, v.act); CHECK(gemm(c, EPI_DRELU_BF16, p, s)); }
+                    else { p.aux = at<bf16>(W, v.apre); CHECK(gemm(c, EPI_DGELUNEW_BF16, p, s)); }
+                }
+                {   // d z = d pre W_down
+                    GemmParams p = gp(dpre, 64, at<bf16>(A, b.wdT), 64, E, T, E, 64);
+                    p.outf = dxn; p.ldo = E;
+                    CHECK(gemm(c, EPI_F32, p, s));
+                }
             }
             // d W_down[j][e] = sum_r d pre[r][j] z[r][e] ; d b_down = colsum(d pre)
             if (fold) {}
             else if (c->f32)
-                CHECK(pevit_launch_tn_gemm64_f32(at<float>(W, v.z), E, (const float*)dpre, 64, at<float>(W, c->w_tnD + (size_t)l * c->tn_layer),
-                                                 nullptr, at<float>(W, c->w_csy + (size_t)l * c->csy_layer), T, E, s));
+                CHECK(pevit_launch_tn_gemm64_f32(at<float>(W, v.z), E, (const float*)dpre, 64, at<float>(W, c->lay.w_tnD + (size_t)l * c->lay.tn_layer),
+                                                 nullptr, at<float>(W, c->lay.w_csy + (size_t)l * c->lay.csy_layer), T, E, s));
             else
-                CHECK(pevit_launch_tn_gemm64(at<bf16>(W, v.z), E, dpre, 64, at<float>(W, c->w_tnD + (size_t)l * c->tn_layer), nullptr,
-                                             at<float>(W, c->w_csy + (size_t)l * c->csy_layer), T, E, s));
+                CHECK(pevit_launch_tn_gemm64(at<bf16>(W, v.z), E, dpre, 64, at<float>(W, c->lay.w_tnD + (size_t)l * c->lay.tn_layer), nullptr,
+                                             at<float>(W, c->lay.w_csy + (size_t)l * c->lay.csy_layer), T, E, s));
             // d h = dx_out + LN_a-backward(d z) ; partial sums for d gamma_a, d beta_a
-            if (!fused_ad)
+            if (!pl.adapter_fused)
                 CHECK(pevit_launch_ln_bwd_affine(dxn, at<float>(W, v.hf32), at<float>(W, v.mean_a), at<float>(W, v.rstd_a), lp + c->o_nw,
-                                                 dxa, nullptr, at<bf16>(W, c->w_dhb),
-                                                 at<float>(W, c->w_lnp + (size_t)l * c->lnp_layer), T, E, s, c->f32));
-            mlp_dy = at<bf16>(W, c->w_dhb);
+                                                 dxa, nullptr, at<bf16>(W, c->lay.w_dhb),
+                                                 at<float>(W, c->lay.w_lnp + (size_t)l * c->lay.lnp_layer), T, E, s, c->f32));
+            mlp_dy = at<bf16>(W, c->lay.w_dhb);
             if (l == 0 && !need_dx0) break;     // nothing trainable below the first block's adapter
         }
         const bool cls = cls_only && l == c->L - 1;
@@ -991,60 +974,50 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, bool need_dx0, bool cls_
         {
             // fp8: mlp_dy arrives with c_proj's channel scales folded in, and leaves with c_fc's (for the next product)
             GemmParams p = gpw(c, mlp_dy, rs, b.wprT, E, 4 * E, R, 4 * E, E, 0);
-            p.aux = at<bf16>(W, v.h); p.ldaux = 4 * E; p.outb = at<bf16>(W, c->w_dh); p.ldob = 4 * E;
+            p.aux = at<bf16>(W, v.h); p.ldaux = 4 * E; p.outb = at<bf16>(W, c->lay.w_dh); p.ldob = 4 * E;
             if (c->fp8) p.oscale = at<float>(A, b.sfc);
             CHECK(gemm(c, EPI_DGELU_BF16, p, s));
         }
         {
             // the LN-input gradient leaves the GEMM in the activation storage type (bf16): LayerNorm backward is
             // HBM-bound, and this halves the bytes on both sides of the hand-over
-            GemmParams p = gpw(c, at<bf16>(W, c->w_dh), 4 * E, b.wfcT, 4 * E, E, R, E, 4 * E, 0);
-            if (c->dx_stored) { p.outb = reinterpret_cast<bf16*>(dxn); p.ldob = E; CHECK(gemm(c, EPI_BF16, p, s)); }
+            GemmParams p = gpw(c, at<bf16>(W, c->lay.w_dh), 4 * E, b.wfcT, 4 * E, E, R, E, 4 * E, 0);
+            if (pl.dx_stored) { p.outb = reinterpret_cast<bf16*>(dxn); p.ldob = E; CHECK(gemm(c, EPI_BF16, p, s)); }
             else { p.outf = dxn; p.ldo = E; CHECK(gemm(c, EPI_F32, p, s)); }
         }
-        // fp8: the bf16 copy feeds the out-projection backward, whose contraction runs over out_proj's output channels
-        // dy (stored type or f32) + x + residual gradient read, f32 gradient + its stored copy written
-        if (gs16)
-            PROF(c, s, PEVIT_PROF_LN_BWD, R, (double)R * E * (c->es + 4 + c->es + c->es),
-                 pevit_launch_ln_bwd(dxn, at<float>(W, v.x_mid), at<float>(W, v.mean2), at<float>(W, v.rstd2),
-                                     at<float>(A, b.ln2w), reinterpret_cast<const float*>(dyb), nullptr, dyb, R, E, s, (size_t)rs,
-                                     c->fp8 ? at<float>(A, b.so) : nullptr, 0, 1, 0, 1, c->fp8 ? at<float>(A, b.spr) : nullptr));
-        else
-        PROF(c, s, PEVIT_PROF_LN_BWD, R, (double)R * E * ((c->dx_stored ? c->es : 4) + 4 + 4 + 4 + c->es),
-             pevit_launch_ln_bwd(dxn, at<float>(W, v.x_mid), at<float>(W, v.mean2), at<float>(W, v.rstd2),
-                                 at<float>(A, b.ln2w), dxa, dxb, dyb, R, E, s, (size_t)rs,
-                                 c->fp8 ? at<float>(A, b.so) : nullptr, c->f32, c->dx_stored));
+        // fp8: the bf16 copy feeds the out-projection backward, whose contraction runs over out_proj's output channels.
+        // gs16: the residual gradient is the bf16 copy dyb itself, read and rewritten in place (no f32 pair dxa / dxb)
+        PROF(c, s, PEVIT_PROF_LN_BWD, R, (double)R * E * ln_bwd_bytes,
+             pevit_launch_ln_bwd(dxn, at<float>(W, v.x_mid), at<float>(W, v.mean2), at<float>(W, v.rstd2), at<float>(A, b.ln2w),
+                                 gs16 ? reinterpret_cast<const float*>(dyb) : dxa, gs16 ? nullptr : dxb, dyb, R, E, s, (size_t)rs,
+                                 c->fp8 ? at<float>(A, b.so) : nullptr, c->f32, pl.dx_stored, 0, gs16,
+                                 gs16 && c->fp8 ? at<float>(A, b.spr) : nullptr));
         // ---- attention branch
-        CHECK(attn_core_bwd(c, s, B, l, cls, walk));
+        CHECK(attn_core_bwd(c, s, B, pl, l, cls, walk));
         if (l > 0 || need_dx0) {
-            CHECK(attn_qkv_dx(c, s, B, l, nullptr));
-            // fp8: this bf16 copy is the upstream gradient of layer l-1's c_proj backward
-            if (gs16)      // the f32 copy only where the caller asked for dx (the lowest block walked)
-                PROF(c, s, PEVIT_PROF_LN_BWD, T, (double)T * E * (c->es + 4 + c->es + c->es),
-                     pevit_launch_ln_bwd(dxn, at<float>(W, v.x_in), at<float>(W, v.mean1), at<float>(W, v.rstd1),
-                                         at<float>(A, b.ln1w), reinterpret_cast<const float*>(dyb), (need_dx0 && l == l_lo) ? dxa : nullptr, dyb,
-                                         T, E, s, 0, (c->fp8 && l > 0) ? at<float>(A, c->blk[l - 1].spr) : nullptr, 0, 1, cls ? N : 0, 1,
-                                         c->fp8 ? at<float>(A, b.so) : nullptr));
-            else
-            PROF(c, s, PEVIT_PROF_LN_BWD, T, (double)T * E * ((c->dx_stored ? c->es : 4) + 4 + 4 + 4 + c->es),
-                 pevit_launch_ln_bwd(dxn, at<float>(W, v.x_in), at<float>(W, v.mean1), at<float>(W, v.rstd1),
-                                     at<float>(A, b.ln1w), dxb, dxa, dyb, T, E, s, 0,
-                                     (c->fp8 && l > 0) ? at<float>(A, c->blk[l - 1].spr) : nullptr, c->f32, c->dx_stored,
-                                     cls ? N : 0));        // last block, class-token pruning: dxb carries a gradient on the class rows only
+            CHECK(attn_qkv_dx(c, s, B, pl, l, nullptr));
+            // fp8: this bf16 copy is the upstream gradient of layer l-1's c_proj backward.  gs16: the f32 copy only where the caller
+            // asked for dx (the lowest block walked).  Last block, class-token pruning: the residual gradient sits on the class rows only
+            float* dx_out = gs16 ? ((need_dx0 && l == l_lo) ? dxa : nullptr) : dxa;
+            PROF(c, s, PEVIT_PROF_LN_BWD, T, (double)T * E * ln_bwd_bytes,
+                 pevit_launch_ln_bwd(dxn, at<float>(W, v.x_in), at<float>(W, v.mean1), at<float>(W, v.rstd1), at<float>(A, b.ln1w),
+                                     gs16 ? reinterpret_cast<const float*>(dyb) : dxb, dx_out, dyb, T, E, s, 0,
+                                     (c->fp8 && l > 0) ? at<float>(A, c->blk[l - 1].spr) : nullptr, c->f32, pl.dx_stored, cls ? N : 0, gs16,
+                                     gs16 && c->fp8 ? at<float>(A, b.so) : nullptr));
         }
     }
-    // (the side stream / deferred dP belong to the attention-site methods, the owed d W_down product to the post-MLP ones: at most
-    // one of the two below has work)
+    // (the deferred dP belongs to the attention-site methods, the owed d W_down product to the post-MLP ones: at most one of the
+    // two below has work)
     CHECK(attn_walk_end(c, s, B, walk));
     if (tn_pend >= 0)                   // the d W_down product of the last adapter walked
-        CHECK(pevit_launch_tn_gemm64(at<bf16>(W, c->sav[tn_pend].z), E, tn_pend_dpre, 64, at<float>(W, c->w_tnD + (size_t)tn_pend * c->tn_layer),
-                                     nullptr, at<float>(W, c->w_csy + (size_t)tn_pend * c->csy_layer), T, E, s));
-    return reduce_adapter_grads(c, s, B, l_lo, l_hi);
+        CHECK(pevit_launch_tn_gemm64(at<bf16>(W, c->lay.sav[tn_pend].z), E, tn_pend_dpre, 64, at<float>(W, c->lay.w_tnD + (size_t)tn_pend * c->lay.tn_layer),
+                                     nullptr, at<float>(W, c->lay.w_csy + (size_t)tn_pend * c->lay.csy_layer), T, E, s));
+    return reduce_adapter_grads(c, s, B, pl, l_lo, l_hi);
 }
 
 // adapter gradients of layers [l_lo, l_hi): reduce the per-layer partials and chain onto the reference's tensors (flat gradient
 // buffer, accumulating)
-int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, int l_lo, int l_hi) {
+int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l_lo, int l_hi) {
     const int E = c->E, T = B * c->N;
     char* W = c->ws;
     const int chunks = pevit_lowrank_chunks(T);
@@ -1052,34 +1025,33 @@ int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, int l_lo, int l_hi)
     const size_t pl0 = c->p_layer0 + c->p_layer_stride * l_lo;          // first float of layer l_lo's parameters
     if (nl <= 0) return 0;
     if (c->d.method == PEVIT_KADAPTATION) {
-        CHECK(pevit_launch_chain_kadapt(at<float>(W, c->w_partial + (size_t)l_lo * c->partial_layer), c->partial_layer / 4,
-                                        at<float>(W, c->w_dbias + (size_t)l_lo * c->dbias_layer), c->dbias_layer / 4, chunks,
-                                        c->ascale, nl, at<float>(W, c->w_G) + (size_t)l_lo * 4 * E * 32,
-                                        at<float>(W, c->w_rule) + (size_t)l_lo * 4096, c->params, c->grads, pl0, c->p_layer_stride, E, s));
+        CHECK(pevit_launch_chain_kadapt(at<float>(W, c->lay.w_partial + (size_t)l_lo * c->lay.partial_layer), c->lay.partial_layer / 4,
+                                        at<float>(W, c->lay.w_dbias + (size_t)l_lo * c->lay.dbias_layer), c->lay.dbias_layer / 4, chunks,
+                                        c->ascale, nl, at<float>(W, c->lay.w_G) + (size_t)l_lo * 4 * E * 32,
+                                        at<float>(W, c->lay.w_rule) + (size_t)l_lo * 4096, c->params, c->grads, pl0, c->p_layer_stride, E, s));
         // the shared rule factors collect from every layer: each range adds its own layers (top first, one running sum), so a
         // backward that never reaches block 0 keeps its rule contributions and a walk in ranges equals the one-call backward
-        CHECK(pevit_launch_rule_sum(at<float>(W, c->w_rule), c->grads, l_lo, l_hi, s));
+        CHECK(pevit_launch_rule_sum(at<float>(W, c->lay.w_rule), c->grads, l_lo, l_hi, s));
     } else if (c->d.method == PEVIT_LORA) {
-        CHECK(pevit_launch_chain_lora(at<float>(W, c->w_partial + (size_t)l_lo * c->partial_layer), c->partial_layer / 4, chunks,
-                                      c->ascale, c->d.lora_rank, nl, at<float>(W, c->w_G) + (size_t)l_lo * 4 * E * 32, c->grads, pl0,
+        CHECK(pevit_launch_chain_lora(at<float>(W, c->lay.w_partial + (size_t)l_lo * c->lay.partial_layer), c->lay.partial_layer / 4, chunks,
+                                      c->ascale, c->d.lora_rank, nl, at<float>(W, c->lay.w_G) + (size_t)l_lo * 4 * E * 32, c->grads, pl0,
                                       c->p_layer_stride, E, s));
-    } else if (post_mlp(c)) {
-        const bool fused_lnp = c->adapter_fused && !c->f32 && !c->fused_bn && pevit_adapter_fused_ok(E);
-        const int tch = pevit_tn_chunks(T), lnb = fused_lnp ? pevit_adapter_blocks(T) : pevit_lna_blocks(T);
+    } else if (pl.post_mlp) {
+        const int tch = pevit_tn_chunks(T), lnb = pl.adapter_fused ? pevit_adapter_blocks(T) : pevit_lna_blocks(T);
         const size_t ps = c->p_layer_stride, gl = (size_t)E * 64;
         float* g0 = c->grads + pl0;
-        float* Gd = at<float>(W, c->w_Gd) + (size_t)l_lo * gl;
-        float* Gu = at<float>(W, c->w_Gu) + (size_t)l_lo * gl;
+        float* Gd = at<float>(W, c->lay.w_Gd) + (size_t)l_lo * gl;
+        float* Gu = at<float>(W, c->lay.w_Gu) + (size_t)l_lo * gl;
         CHECK(pevit_launch_zero(Gd, (size_t)nl * gl * 4, s));
         CHECK(pevit_launch_zero(Gu, (size_t)nl * gl * 4, s));
-        CHECK(pevit_launch_colsum_reduce(at<float>(W, c->w_tnD + (size_t)l_lo * c->tn_layer), tch, (int)gl, Gd, nl, c->tn_layer / 4, gl, s));
-        CHECK(pevit_launch_colsum_reduce(at<float>(W, c->w_tnU + (size_t)l_lo * c->tn_layer), tch, (int)gl, Gu, nl, c->tn_layer / 4, gl, s));
+        CHECK(pevit_launch_colsum_reduce(at<float>(W, c->lay.w_tnD + (size_t)l_lo * c->lay.tn_layer), tch, (int)gl, Gd, nl, c->lay.tn_layer / 4, gl, s));
+        CHECK(pevit_launch_colsum_reduce(at<float>(W, c->lay.w_tnU + (size_t)l_lo * c->lay.tn_layer), tch, (int)gl, Gu, nl, c->lay.tn_layer / 4, gl, s));
         // biases and LayerNorm affine: straight column sums into the flat gradient buffer
         // d b_up from the f32 column sums of the upstream gradient (third plane of the LN partials)
-        CHECK(pevit_launch_colsum_reduce(at<float>(W, c->w_csy + (size_t)l_lo * c->csy_layer), tch, 64, g0 + c->o_db, nl,
-                                         c->csy_layer / 4, ps, s));
-        CHECK(pevit_launch_colsum_reduce3(at<float>(W, c->w_lnp + (size_t)l_lo * c->lnp_layer), lnb, E, g0 + c->o_nw, g0 + c->o_nb,
-                                          g0 + c->o_ub, nl, c->lnp_layer / 4, ps, s));
+        CHECK(pevit_launch_colsum_reduce(at<float>(W, c->lay.w_csy + (size_t)l_lo * c->lay.csy_layer), tch, 64, g0 + c->o_db, nl,
+                                         c->lay.csy_layer / 4, ps, s));
+        CHECK(pevit_launch_colsum_reduce3(at<float>(W, c->lay.w_lnp + (size_t)l_lo * c->lay.lnp_layer), lnb, E, g0 + c->o_nw, g0 + c->o_nb,
+                                          g0 + c->o_ub, nl, c->lay.lnp_layer / 4, ps, s));
         if (c->d.method == PEVIT_ADAPTER) {
             CHECK(pevit_launch_chain_adapter(Gd, Gu, g0 + c->o_dw, g0 + c->o_uw, E, nl, gl, ps, s));
         } else {
@@ -1100,12 +1072,13 @@ extern "C" int pevit_blocks_forward(pevit_ctx* c, void* stream, const float* x_n
     CHECK(check_ready(c, B, "blocks_forward"));
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("blocks_forward: bad block range [%d, %d)", l_lo, l_hi); return -1; }
     hipStream_t s = (hipStream_t)stream;
-    size_t total; layout_workspace(c, B, c->sav, &total, c);
-    CHECK(pevit_launch_permute_rows(x_nbe, at<float>(c->ws, c->sav[l_lo].x_in), c->N, B, c->E, 1, s));
-    CHECK(blocks_forward(c, s, B, false, l_lo, l_hi));
-    const size_t out = l_hi < c->L ? c->sav[l_hi].x_in : c->w_xfinal;
+    c->lay = layout_workspace(c, B);
+    const StepPlan pl = plan_step(c, B);
+    CHECK(pevit_launch_permute_rows(x_nbe, at<float>(c->ws, c->lay.sav[l_lo].x_in), c->N, B, c->E, 1, s));
+    CHECK(blocks_forward(c, s, B, pl, false, l_lo, l_hi));
+    const size_t out = l_hi < c->L ? c->lay.sav[l_hi].x_in : c->lay.w_xfinal;
     CHECK(pevit_launch_permute_rows(at<float>(c->ws, out), y_nbe, c->N, B, c->E, 0, s));
-    c->saved_batch = save_for_backward ? B : 0; c->saved_kind = 1;
+    c->saved = SavedForward{Saved::blocks, save_for_backward ? B : 0, -1, pl};
     return 0;
 }
 
@@ -1119,21 +1092,17 @@ extern "C" int pevit_transformer_forward(pevit_ctx* c, void* stream, const float
 extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy_nbe, float* dx_nbe, int B, int l_lo, int l_hi) {
     CHECK(check_ready(c, B, "blocks_backward"));
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("blocks_backward: bad block range [%d, %d)", l_lo, l_hi); return -1; }
-    if (c->saved_batch != B || c->saved_kind != 1) {
-        pevit_set_error("blocks_backward: the saved activations are not those of a blocks/transformer forward with batch %d "
-                        "(saved: batch %d, %s)", B, c->saved_batch, saved_name(c));
-        return -1;
-    }
+    CHECK(check_saved(c, Saved::blocks, B, -1, "blocks_backward"));
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * c->N * c->E;
-    CHECK(pevit_launch_permute_rows(dy_nbe, at<float>(c->ws, c->w_dxa), c->N, B, c->E, 1, s));
+    CHECK(pevit_launch_permute_rows(dy_nbe, at<float>(c->ws, c->lay.w_dxa), c->N, B, c->E, 1, s));
     if (c->fp8)
-        CHECK(pevit_launch_cast_bf16_cols(at<float>(c->ws, c->w_dxa), at<bf16>(c->ws, c->w_dyb), (size_t)B * c->N, c->E,
+        CHECK(pevit_launch_cast_bf16_cols(at<float>(c->ws, c->lay.w_dxa), at<bf16>(c->ws, c->lay.w_dyb), (size_t)B * c->N, c->E,
                                           at<float>(c->arena, c->blk[l_hi - 1].spr), s));
     else
-        CHECK(pevit_launch_cast_bf16(at<float>(c->ws, c->w_dxa), at<bf16>(c->ws, c->w_dyb), n, 1.0f, s, c->f32));
-    CHECK(blocks_backward(c, s, B, dx_nbe != nullptr, false, l_hi, l_lo));
-    if (dx_nbe) CHECK(pevit_launch_permute_rows(at<float>(c->ws, c->w_dxa), dx_nbe, c->N, B, c->E, 0, s));
+        CHECK(pevit_launch_cast_bf16(at<float>(c->ws, c->lay.w_dxa), at<bf16>(c->ws, c->lay.w_dyb), n, 1.0f, s, c->f32));
+    CHECK(blocks_backward(c, s, B, c->saved.plan, dx_nbe != nullptr, false, l_hi, l_lo));
+    if (dx_nbe) CHECK(pevit_launch_permute_rows(at<float>(c->ws, c->lay.w_dxa), dx_nbe, c->N, B, c->E, 0, s));
     return 0;
 }
 
@@ -1151,17 +1120,18 @@ extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, co
         return -1;
     }
     hipStream_t s = (hipStream_t)stream;
-    size_t total; layout_workspace(c, B, c->sav, &total, c);
+    c->lay = layout_workspace(c, B);
+    const StepPlan pl = plan_step(c, B);
     const int E = c->E, N = c->N, T = B * N;
     char* W = c->ws; char* A = c->arena;
     const BlockArena& b = c->blk[layer];
-    const LayerSaved& v = c->sav[layer];
-    float* xin = at<float>(W, c->w_dxn);          // [T][E] f32 scratch (free in a forward pass)
-    float* yout = at<float>(W, c->w_dxa);
+    const LayerSaved& v = c->lay.sav[layer];
+    float* xin = at<float>(W, c->lay.w_dxn);          // [T][E] f32 scratch (free in a forward pass)
+    float* yout = at<float>(W, c->lay.w_dxa);
     CHECK(pevit_launch_permute_rows(x_nbe, xin, N, B, E, 1, s));
     CHECK(pevit_launch_cast_bf16(xin, at<bf16>(W, v.xn1), (size_t)T * E, 1.0f, s, c->f32));
-    if (attention_site(c)) CHECK(prep_adapters(c, s));
-    CHECK(attn_core_fwd(c, s, B, layer, nullptr, nullptr));
+    if (pl.site) CHECK(prep_adapters(c, s));
+    CHECK(attn_core_fwd(c, s, B, pl, layer, nullptr, nullptr));
     if (weights) {
         const bf16* qkv = at<bf16>(W, v.qkv);
         const size_t plane = (size_t)T * E;
@@ -1177,7 +1147,7 @@ extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, co
         CHECK(gemm(c, EPI_BIAS_F32, p, s));
     }
     CHECK(pevit_launch_permute_rows(yout, y_nbe, N, B, E, 0, s));
-    c->saved_batch = save_for_backward ? B : 0; c->saved_kind = 3; c->saved_layer = layer;
+    c->saved = SavedForward{Saved::attention, save_for_backward ? B : 0, layer, pl};
     return 0;
 }
 
@@ -1187,31 +1157,24 @@ extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, co
 extern "C" int pevit_attention_backward(pevit_ctx* c, void* stream, int layer, const float* dy_nbe, float* dx_nbe, int B) {
     CHECK(check_ready(c, B, "attention_backward"));
     if (layer < 0 || layer >= c->L) { pevit_set_error("attention_backward: layer %d outside [0, %d)", layer, c->L); return -1; }
-    if (c->saved_batch != B || c->saved_kind != 3 || c->saved_layer != layer) {
-        char what[64];
-        if (c->saved_kind == 3) snprintf(what, sizeof(what), "attention_forward of layer %d", c->saved_layer);
-        else snprintf(what, sizeof(what), "%s", saved_name(c));
-        pevit_set_error("attention_backward: the saved activations are not those of an attention_forward of layer %d with batch %d "
-                        "(saved: batch %d, %s)", layer, B, c->saved_batch, what);
-        return -1;
-    }
+    CHECK(check_saved(c, Saved::attention, B, layer, "attention_backward"));
+    const StepPlan& pl = c->saved.plan;
     hipStream_t s = (hipStream_t)stream;
     const int E = c->E, N = c->N, T = B * N;
     char* W = c->ws;
-    float* dy = at<float>(W, c->w_dxa);
+    float* dy = at<float>(W, c->lay.w_dxa);
     CHECK(pevit_launch_permute_rows(dy_nbe, dy, N, B, E, 1, s));
     // fp8: out_proj's channel scales ride on the A operand of its dX product (as LayerNorm backward leaves them in the block walk)
     if (c->fp8)
-        CHECK(pevit_launch_cast_bf16_cols(dy, at<bf16>(W, c->w_dyb), (size_t)T, E, at<float>(c->arena, c->blk[layer].so), s));
+        CHECK(pevit_launch_cast_bf16_cols(dy, at<bf16>(W, c->lay.w_dyb), (size_t)T, E, at<float>(c->arena, c->blk[layer].so), s));
     else
-        CHECK(pevit_launch_cast_bf16(dy, at<bf16>(W, c->w_dyb), (size_t)T * E, 1.0f, s, c->f32));
+        CHECK(pevit_launch_cast_bf16(dy, at<bf16>(W, c->lay.w_dyb), (size_t)T * E, 1.0f, s, c->f32));
     AttnGradWalk walk;
-    CHECK(attn_walk_begin(c, walk));
-    CHECK(attn_core_bwd(c, s, B, layer, false, walk));
-    float* dx = at<float>(W, c->w_dxb);
-    if (dx_nbe) CHECK(attn_qkv_dx(c, s, B, layer, dx));
+    CHECK(attn_core_bwd(c, s, B, pl, layer, false, walk));
+    float* dx = at<float>(W, c->lay.w_dxb);
+    if (dx_nbe) CHECK(attn_qkv_dx(c, s, B, pl, layer, dx));
     CHECK(attn_walk_end(c, s, B, walk));
-    if (attention_site(c)) CHECK(reduce_adapter_grads(c, s, B, layer, layer + 1));
+    if (pl.site) CHECK(reduce_adapter_grads(c, s, B, pl, layer, layer + 1));
     if (dx_nbe) CHECK(pevit_launch_permute_rows(dx, dx_nbe, N, B, E, 0, s));
     return 0;
 }
@@ -1231,8 +1194,8 @@ extern "C" int pevit_sgd_step(pevit_ctx* c, void* stream, float lr, float moment
     if (!c || !c->params || !c->grads || !c->mom) { pevit_set_error("sgd_step: parameters/momentum not set"); return -1; }
     // the error word of the workspace bound NOW (a re-bind moves it; without stream-K slots -- f32 verification mode -- there is
     // no hand-off that could fail and nothing to guard)
-    unsigned* poison = (c->ws && c->sk_slots) ? at<unsigned>(c->ws, c->w_skflag) + c->sk_slots : nullptr;
-    unsigned* skipped = poison ? at<unsigned>(c->ws, c->w_skflag) + PEVIT_SK_MAX_SLOTS + 1 : nullptr;
+    unsigned* poison = (c->ws && c->sk_slots) ? at<unsigned>(c->ws, c->lay.w_skflag) + c->sk_slots : nullptr;
+    unsigned* skipped = poison ? at<unsigned>(c->ws, c->lay.w_skflag) + PEVIT_SK_MAX_SLOTS + 1 : nullptr;
     float* loss_slot = c->last_loss; c->last_loss = nullptr;
     return pevit_launch_sgd(c->params, c->grads, c->mom, c->grad_mask, c->n_total, lr, momentum, wd, flags,
                             grad_scale, (hipStream_t)stream, poison, skipped, c->ext_poison, (poison || c->ext_poison) ? loss_slot : nullptr);
@@ -1312,41 +1275,42 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
     const float* images = (const float*)images_any;
     CHECK(check_ready(c, B, "visual_forward"));
     hipStream_t s = (hipStream_t)stream;
-    size_t total; layout_workspace(c, B, c->sav, &total, c);
+    c->lay = layout_workspace(c, B);
+    const StepPlan pl = plan_step(c, B);
     char* W = c->ws; char* A = c->arena;
     const int E = c->E, N = c->N, T = B * N;
-    float* xpre = at<float>(W, c->w_dxn);               // scratch, free during the forward pass
+    float* xpre = at<float>(W, c->lay.w_dxn);               // scratch, free during the forward pass
     if (u8)
         PROF(c, s, PEVIT_PROF_IM2COL, B, (double)B * 3 * c->R * c->R * 1 + (double)B * c->G2 * c->Kpatch * c->es,
-             pevit_launch_im2col_u8((const unsigned char*)images_any, c->img_mean, c->img_std, at<bf16>(W, c->w_patches), B, c->R, c->P,
+             pevit_launch_im2col_u8((const unsigned char*)images_any, c->img_mean, c->img_std, at<bf16>(W, c->lay.w_patches), B, c->R, c->P,
                                     c->Kpatch, s, c->f32));
     else
         PROF(c, s, PEVIT_PROF_IM2COL, B, (double)B * 3 * c->R * c->R * 4 + (double)B * c->G2 * c->Kpatch * c->es,
-             pevit_launch_im2col(images, at<bf16>(W, c->w_patches), B, c->R, c->P, c->Kpatch, s, c->f32));
+             pevit_launch_im2col(images, at<bf16>(W, c->lay.w_patches), B, c->R, c->P, c->Kpatch, s, c->f32));
     CHECK(pevit_launch_cls_row(at<float>(A, c->a_cls), at<float>(A, c->a_pos), xpre, B, N, E, s));
     {
-        GemmParams p = gp(at<bf16>(W, c->w_patches), c->Kpatch, at<bf16>(A, c->a_conv), c->Kpatch, E, B * c->G2, E, c->Kpatch);
+        GemmParams p = gp(at<bf16>(W, c->lay.w_patches), c->Kpatch, at<bf16>(A, c->a_conv), c->Kpatch, E, B * c->G2, E, c->Kpatch);
         p.resid = at<float>(A, c->a_pos); p.ldr = E; p.outf = xpre; p.ldo = E; p.Ntok = N;
         CHECK(gemm(c, EPI_PATCH_EMBED, p, s));
     }
     CHECK(pevit_launch_ln_fwd(xpre, at<float>(A, c->a_lnpre_w), at<float>(A, c->a_lnpre_b), T, E, nullptr,
-                              at<float>(W, c->sav[0].x_in), nullptr, nullptr, s));
+                              at<float>(W, c->lay.sav[0].x_in), nullptr, nullptr, s));
     if (c->gate_now) {                                  // fused step with a gate (pevit_set_step_gate): parameters and gradient buffer from here on
         c->gate_now = false;
         HIP_OK(hipStreamWaitEvent(s, c->step_gate, 0));
         CHECK(pevit_zero_grads(c, stream));
     }
-    CHECK(blocks_forward(c, s, B, true));
+    CHECK(blocks_forward(c, s, B, pl, pl.cls_prune));
     // ln_post on the class token of every image (row b*N), then @ proj
-    CHECK(pevit_launch_ln_fwd(at<float>(W, c->w_xfinal), at<float>(A, c->a_lnpost_w), at<float>(A, c->a_lnpost_b), B, E,
-                              at<bf16>(W, c->w_xpost), nullptr, at<float>(W, c->w_pmean), at<float>(W, c->w_prstd), s,
+    CHECK(pevit_launch_ln_fwd(at<float>(W, c->lay.w_xfinal), at<float>(A, c->a_lnpost_w), at<float>(A, c->a_lnpost_b), B, E,
+                              at<bf16>(W, c->lay.w_xpost), nullptr, at<float>(W, c->lay.w_pmean), at<float>(W, c->lay.w_prstd), s,
                               (size_t)N * E, c->f32));
     {
-        GemmParams p = gp(at<bf16>(W, c->w_xpost), E, at<bf16>(A, c->a_proj), E, c->D, B, c->D, E);
-        p.outf = feat ? feat : at<float>(W, c->w_feat); p.ldo = c->D;
+        GemmParams p = gp(at<bf16>(W, c->lay.w_xpost), E, at<bf16>(A, c->a_proj), E, c->D, B, c->D, E);
+        p.outf = feat ? feat : at<float>(W, c->lay.w_feat); p.ldo = c->D;
         CHECK(gemm(c, EPI_F32, p, s));
     }
-    c->saved_batch = save_for_backward ? B : 0; c->saved_kind = 2;
+    c->saved = SavedForward{Saved::visual, save_for_backward ? B : 0, -1, pl};
     return 0;
 }
 
@@ -1355,25 +1319,22 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
 // parallelism calls (L, L/2) then (L/2, 0) and all-reduces the first part's gradients while the second runs.
 extern "C" int pevit_visual_backward_part(pevit_ctx* c, void* stream, const float* dfeat, int B, int l_hi, int l_lo) {
     CHECK(check_ready(c, B, "visual_backward"));
-    if (c->saved_batch != B || c->saved_kind != 2) {
-        pevit_set_error("visual_backward: the saved activations are not those of a visual_forward with batch %d (saved: batch %d, %s)",
-                        B, c->saved_batch, saved_name(c));
-        return -1;
-    }
+    CHECK(check_saved(c, Saved::visual, B, -1, "visual_backward"));
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("visual_backward: bad layer range [%d, %d)", l_lo, l_hi); return -1; }
     if (c->d.method == PEVIT_NONE) return 0;
     hipStream_t s = (hipStream_t)stream;
     char* W = c->ws; char* A = c->arena;
     const int E = c->E, N = c->N, T = B * N;
-    const bool cls = !post_mlp(c);
+    const StepPlan& pl = c->saved.plan;
+    const bool cls = pl.cls_prune;
     if (l_hi == c->L) {
         if (!dfeat) { pevit_set_error("visual_backward: dfeat is required for the part that starts at the last block"); return -1; }
         // (the head's BatchNorm backward leaves the bf16 copy of ITS dfeat in w_dfeatb: no cast launch then)
-        if (c->dfeatb_of != dfeat) CHECK(pevit_launch_cast_bf16(dfeat, at<bf16>(W, c->w_dfeatb), (size_t)B * c->D, 1.0f, s, c->f32));
+        if (c->dfeatb_of != dfeat) CHECK(pevit_launch_cast_bf16(dfeat, at<bf16>(W, c->lay.w_dfeatb), (size_t)B * c->D, 1.0f, s, c->f32));
         c->dfeatb_of = nullptr;
         {
-            GemmParams p = gp(at<bf16>(W, c->w_dfeatb), c->D, at<bf16>(A, c->a_projT), c->D, E, B, E, c->D);
-            p.outf = at<float>(W, c->w_dxpost); p.ldo = E;
+            GemmParams p = gp(at<bf16>(W, c->lay.w_dfeatb), c->D, at<bf16>(A, c->a_projT), c->D, E, B, E, c->D);
+            p.outf = at<float>(W, c->lay.w_dxpost); p.ldo = E;
             CHECK(gemm(c, EPI_F32, p, s));
         }
         // dL/dx_final is zero except on the class-token rows.  With class-token pruning of the last block
@@ -1382,17 +1343,17 @@ extern "C" int pevit_visual_backward_part(pevit_ctx* c, void* stream, const floa
         if (cls) {
             // ... or not read at all: LayerNorm backward takes the residual gradient on the class-token rows only (res_period), and
             // the attention backward for N <= 64 reads dO on token 0 only (dout_cls_only) -- no fill of dxb (19.7 MB) / dO (9.8 MB)
-            if (c->f32 || N > 64) CHECK(pevit_launch_zero(W + c->w_dO, (size_t)T * E * c->es, s));
+            if (c->f32 || N > 64) CHECK(pevit_launch_zero(W + c->lay.w_dO, (size_t)T * E * c->es, s));
         } else {
-            if (!gstream16_on(c)) CHECK(pevit_launch_zero(W + c->w_dxa, (size_t)T * E * 4, s));      // (the bf16 stream never reads the f32 copy)
-            CHECK(pevit_launch_zero(W + c->w_dyb, (size_t)T * E * c->es, s));
+            if (!pl.gstream16) CHECK(pevit_launch_zero(W + c->lay.w_dxa, (size_t)T * E * 4, s));      // (the bf16 stream never reads the f32 copy)
+            CHECK(pevit_launch_zero(W + c->lay.w_dyb, (size_t)T * E * c->es, s));
         }
-        CHECK(pevit_launch_ln_bwd(at<float>(W, c->w_dxpost), at<float>(W, c->w_xfinal), at<float>(W, c->w_pmean),
-                                  at<float>(W, c->w_prstd), at<float>(A, c->a_lnpost_w), nullptr, at<float>(W, c->w_dxa),
-                                  at<bf16>(W, c->w_dyb), B, E, s, (size_t)N * E,
+        CHECK(pevit_launch_ln_bwd(at<float>(W, c->lay.w_dxpost), at<float>(W, c->lay.w_xfinal), at<float>(W, c->lay.w_pmean),
+                                  at<float>(W, c->lay.w_prstd), at<float>(A, c->a_lnpost_w), nullptr, at<float>(W, c->lay.w_dxa),
+                                  at<bf16>(W, c->lay.w_dyb), B, E, s, (size_t)N * E,
                                   c->fp8 ? at<float>(A, c->blk[c->L - 1].spr) : nullptr, c->f32));
     }
-    CHECK(blocks_backward(c, s, B, false, cls, l_hi, l_lo));
+    CHECK(blocks_backward(c, s, B, pl, false, cls, l_hi, l_lo));
     return 0;
 }
 
@@ -1412,15 +1373,15 @@ extern "C" int pevit_head_forward_backward(pevit_ctx* c, void* stream, const flo
     if (bn_training && B < 2) { pevit_set_error("head: BatchNorm in training mode needs more than 1 sample per batch (got %d)", B); return -1; }
     hipStream_t s = (hipStream_t)stream;
     char* W = c->ws;
-    if (c->saved_batch == 0) { size_t total; layout_workspace(c, B, c->sav, &total, c); }
+    if (c->saved.batch == 0) c->lay = layout_workspace(c, B);
     if (labels) c->last_loss = loss;
     // only inside the fused step (train_fb_impl): there nobody can touch dfeat between the head and the tower backward
-    bf16* dfb = (c->in_fused_step && dfeat && labels && !c->f32) ? at<bf16>(W, c->w_dfeatb) : nullptr;
+    bf16* dfb = (c->in_fused_step && dfeat && labels && !c->f32) ? at<bf16>(W, c->lay.w_dfeatb) : nullptr;
     c->dfeatb_of = dfb ? dfeat : nullptr;
     return pevit_launch_head(feat, labels, c->params + c->p_head_w, c->params + c->p_head_b,
                              labels ? c->grads + c->p_head_w : nullptr, labels ? c->grads + c->p_head_b : nullptr,
-                             running_mean, running_var, bn_training, at<float>(W, c->w_ybn), at<float>(W, c->w_bnrstd),
-                             logits, at<float>(W, c->w_dlogits), at<float>(W, c->w_dybn), loss, dfeat, B, c->D, c->C, s, dfb);
+                             running_mean, running_var, bn_training, at<float>(W, c->lay.w_ybn), at<float>(W, c->lay.w_bnrstd),
+                             logits, at<float>(W, c->lay.w_dlogits), at<float>(W, c->lay.w_dybn), loss, dfeat, B, c->D, c->C, s, dfb);
 }
 
 static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, float* running_mean,
@@ -1444,8 +1405,8 @@ static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8,
     const int frc = visual_forward_impl(c, stream, images, u8, nullptr, B, 1);
     c->gate_now = false;
     if (frc) return frc;
-    float* feat = at<float>(c->ws, c->w_feat);
-    float* dfeat = at<float>(c->ws, c->w_dfeat);
+    float* feat = at<float>(c->ws, c->lay.w_feat);
+    float* dfeat = at<float>(c->ws, c->lay.w_dfeat);
     c->in_fused_step = true;
     const int hrc = pevit_head_forward_backward(c, stream, feat, labels, running_mean, running_var, bn_training, logits, loss, dfeat, B);
     c->in_fused_step = false;
@@ -1540,14 +1501,14 @@ extern "C" int pevit_op_gemm(void* stream, int epi, const void* A, int lda, cons
 extern "C" int pevit_streamk_error(pevit_ctx* c, void* stream) {
     GemmParams p; memset(&p, 0, sizeof(p));
     unsigned* flag = nullptr;
-    if (c) { if (!c->ws || !c->sk_slots) return 0; flag = at<unsigned>(c->ws, c->w_skflag) + c->sk_slots; }
+    if (c) { if (!c->ws || !c->sk_slots) return 0; flag = at<unsigned>(c->ws, c->lay.w_skflag) + c->sk_slots; }
     else { if (op_sk_workspace(p)) return -1; flag = p.sk_flag + p.sk_slots; }
     unsigned v = 0;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
     if (hipMemcpy(&v, flag, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     if (v) {
         (void)hipMemset(flag, 0, 4);
-        if (c) (void)hipMemset(at<unsigned>(c->ws, c->w_skflag) + PEVIT_SK_MAX_SLOTS + 1, 0, 4);    // the skipped-update counter with it
+        if (c) (void)hipMemset(at<unsigned>(c->ws, c->lay.w_skflag) + PEVIT_SK_MAX_SLOTS + 1, 0, 4);    // the skipped-update counter with it
     }
     return v ? 1 : 0;
 }
@@ -1558,8 +1519,8 @@ extern "C" int pevit_streamk_status(pevit_ctx* c, void* stream, unsigned* error_
     unsigned v[2] = {0, 0};
     if (c->ws && c->sk_slots) {
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
-        if (hipMemcpy(&v[0], at<unsigned>(c->ws, c->w_skflag) + c->sk_slots, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        if (hipMemcpy(&v[1], at<unsigned>(c->ws, c->w_skflag) + PEVIT_SK_MAX_SLOTS + 1, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (hipMemcpy(&v[0], at<unsigned>(c->ws, c->lay.w_skflag) + c->sk_slots, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (hipMemcpy(&v[1], at<unsigned>(c->ws, c->lay.w_skflag) + PEVIT_SK_MAX_SLOTS + 1, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     }
     if (error_word) *error_word = v[0];
     if (skipped_updates) *skipped_updates = v[1];
@@ -1714,8 +1675,7 @@ extern "C" int pevit_tune(pevit_ctx* c, const char* key, int value) {
     };
     // these need a context
     static const struct { const char* key; int pevit_ctx::*field; } ctx_keys[] = {
-        {"side_stream", &pevit_ctx::side_stream}, {"fused_bottleneck", &pevit_ctx::fused_bn}, {"dx_stored", &pevit_ctx::dx_stored},
-        {"gstream_bf16", &pevit_ctx::gstream16}, {"profile_all", &pevit_ctx::prof_all}, {"fused_attn_delta", &pevit_ctx::fused_attn_delta},
+        {"dx_stored", &pevit_ctx::dx_stored}, {"gstream_bf16", &pevit_ctx::gstream16}, {"profile_all", &pevit_ctx::prof_all}, {"fused_attn_delta", &pevit_ctx::fused_attn_delta},
         {"fp8_tail", &pevit_ctx::fp8_tail}, {"adapter_fused", &pevit_ctx::adapter_fused}, {"adapter_tn_fold", &pevit_ctx::adapter_tn_fold},
         {"lowrank_combo", &pevit_ctx::lowrank_combo}, {"lowrank_xcd", &pevit_ctx::lowrank_xcd},
     };

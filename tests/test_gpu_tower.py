@@ -731,3 +731,42 @@ def test_combined_lowrank_backward_equals_the_two_launches(method, arch_name, B)
             assert rel_err(g1[k], g0[k]) < 2e-3, (k, rel_err(g1[k], g0[k]))
         else:
             assert float(g1[k].abs().max()) == 0.0, k
+
+
+@pytest.mark.parametrize("method,knob", [("adapter", "adapter_fused"), ("compacter", "adapter_fused"), ("kadaptation", "lowrank_combo"),
+                                         ("kadaptation", "gstream_bf16")])
+def test_a_knob_changed_between_forward_and_backward_takes_effect_at_the_next_forward(method, knob):
+    """The launch paths of a step are planned once per forward (capi.hip plan_step) and the backward runs on its forward's plan:
+    a `tune` between visual_forward and visual_backward leaves that backward's gradients bit-identical to the unchanged pair
+    (the fused adapter forward leaves hf32 without its bias, which the separate launches' backward would read as LayerNorm
+    input), and the next forward takes the new path -- bit-identical to an engine tuned before its first forward."""
+    from pevit_amd.engine import HipEngine, adapter_param_spec
+    from pevit_amd.synth import ARCHS, randomize_adapters, synth_batch, synth_state_dict
+    arch, B, C = ARCHS["tiny-256"], 7, 10
+    sd = {k: v for k, v in synth_state_dict(arch, seed=2, text_tower=False).items() if k.startswith("visual.")}
+    ad = [(n, torch.zeros(s)) for n, s, _ in adapter_param_spec(method, arch.width, arch.layers)]
+    randomize_adapters(ad, seed=3); sd.update(dict(ad))
+    images = synth_batch(B, arch.resolution, C, seed_img=3, seed_lbl=4)[0].cuda()
+    dfeat = torch.randn(B, arch.embed_dim, generator=torch.Generator().manual_seed(5)).cuda()
+
+    def grads(eng, tune_between=False):
+        eng.zero_grad()
+        eng.visual_forward(images)
+        if tune_between:
+            assert eng.tune(knob, 0) == 0
+        eng.visual_backward(dfeat)
+        torch.cuda.synchronize()
+        return {k: v.cpu().clone() for k, v in eng.grad_views().items()}
+
+    eng = HipEngine(arch, method, C, B)
+    eng.load_state_dict(sd)
+    g_on = grads(eng)
+    g_switched = grads(eng, tune_between=True)
+    g_next = grads(eng)
+    ref = HipEngine(arch, method, C, B)
+    ref.load_state_dict(sd)
+    assert ref.tune(knob, 0) == 0
+    g_off = grads(ref)
+    for k in g_on:
+        assert torch.equal(g_switched[k], g_on[k]), (k, rel_err(g_switched[k], g_on[k]))
+        assert torch.equal(g_next[k], g_off[k]), (k, rel_err(g_next[k], g_off[k]))

@@ -84,6 +84,20 @@ def test_bad_dims_fail_loudly(lib):
     lib.pevit_ctx_destroy(ctx)
 
 
+def test_tune_refuses_retired_and_unknown_keys(lib):
+    """The measured-loser paths "side_stream" and "fused_bottleneck" are gone: their keys are unknown like any other."""
+    d = _lib.PevitDims(128, 2, 16, 48, 64, 2, 4, 10)
+    ctx = C.c_void_p()
+    assert lib.pevit_ctx_create(C.byref(d), C.byref(ctx)) == 0
+    for key in (b"adapter_fused", b"adapter_tn_fold", b"lowrank_combo", b"gstream_bf16", b"dx_stored", b"fp8_tail",
+                b"fused_attn_delta", b"lowrank_xcd", b"profile_all"):
+        assert lib.pevit_tune(ctx, key, 1) == 0, key
+    for key in (b"side_stream", b"fused_bottleneck", b"no_such_knob"):
+        assert lib.pevit_tune(ctx, key, 1) == -1, key
+        assert b"unknown key" in lib.pevit_last_error()
+    lib.pevit_ctx_destroy(ctx)
+
+
 @pytest.mark.parametrize("case", ["tiny_kadaptation", "tiny_lora", "tiny_lora_r8", "tiny_adapter", "tiny_compacter"])
 def test_param_spec_order_matches_reference_named_parameters(case):
     meta, t = load_golden(case)
