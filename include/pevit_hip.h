@@ -184,6 +184,19 @@ int pevit_train_forward_backward_u8(pevit_ctx* ctx, void* stream, const uint8_t*
 int pevit_train_forward_backward(pevit_ctx* ctx, void* stream, const float* images, const int64_t* labels,
                                  float* running_mean, float* running_var, int bn_training, float* logits,
                                  float* loss, int batch);
+/* ---- multi-label: the three entries above with BCEWithLogitsLoss(reduction="mean") in place of the cross-entropy.
+ * targets: f32 (B x C) row-major, multi-hot or soft; loss = sum(l) / (B*C) with l = max(x,0) - x*y + log1p(exp(-|x|)),
+ * dlogits = (sigmoid(x) - y) / (B*C).  Everything else -- BatchNorm, the head gradients, dfeat, the tower backward, the loss
+ * slot that a withheld update overwrites with NaN -- is what the cross-entropy entries do. */
+int pevit_head_forward_backward_bce(pevit_ctx* ctx, void* stream, const float* feat, const float* targets,
+                                    float* running_mean, float* running_var, int bn_training, float* logits,
+                                    float* loss, float* dfeat_or_null, int batch);
+int pevit_train_forward_backward_bce(pevit_ctx* ctx, void* stream, const float* images, const float* targets,
+                                     float* running_mean, float* running_var, int bn_training, float* logits,
+                                     float* loss, int batch);
+int pevit_train_forward_backward_bce_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const float* targets,
+                                        float* running_mean, float* running_var, int bn_training, float* logits,
+                                        float* loss, int batch);
 
 /* ---- measurement: HIP events around every MFMA GEMM launch of the context (the dominant kernel
  * family); totals over the GEMM launches recorded between begin and end.  With pevit_tune(ctx, "profile_all", 1) the

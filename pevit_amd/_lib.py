@@ -60,6 +60,9 @@ SIGNATURES = {
     "pevit_set_input_norm": (c_int, [P, P, P]),
     "pevit_visual_forward_u8": (c_int, [P, P, P, P, c_int, c_int]),
     "pevit_train_forward_backward_u8": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
+    "pevit_head_forward_backward_bce": (c_int, [P, P, P, P, P, P, c_int, P, P, P, c_int]),
+    "pevit_train_forward_backward_bce": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
+    "pevit_train_forward_backward_bce_u8": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
     "pevit_profile_begin": (c_int, [P, c_int]),
     "pevit_profile_end": (c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_int)]),
     "pevit_profile_launch": (c_int, [P, c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_int)]),

@@ -1361,45 +1361,70 @@ extern "C" int pevit_visual_backward(pevit_ctx* c, void* stream, const float* df
     return pevit_visual_backward_part(c, stream, dfeat, B, c ? c->L : 0, 0);
 }
 
-extern "C" int pevit_head_forward_backward(pevit_ctx* c, void* stream, const float* feat, const int64_t* labels,
-                                           float* running_mean, float* running_var, int bn_training, float* logits,
-                                           float* loss, float* dfeat, int B) {
+// labels (B) int64 -> cross-entropy, targets (B x C) f32 -> BCE with logits, neither -> forward only; never both
+static int head_fb_impl(pevit_ctx* c, void* stream, const float* feat, const int64_t* labels, const float* targets,
+                        float* running_mean, float* running_var, int bn_training, float* logits, float* loss, float* dfeat, int B) {
     if (!c || !c->ws || !c->params || !c->grads) { pevit_set_error("head: context not ready"); return -1; }
     if (B <= 0 || B > c->max_batch) { pevit_set_error("head: batch %d outside [1,%d]", B, c->max_batch); return -1; }
     if (!feat || !running_mean || !running_var || !logits) { pevit_set_error("head: null argument"); return -1; }
-    if (labels && !loss) { pevit_set_error("head: labels given but loss is null"); return -1; }
+    if (labels && targets) { pevit_set_error("head: labels and targets both given"); return -1; }
+    const bool has_loss = labels || targets;
+    if (has_loss && !loss) { pevit_set_error("head: labels given but loss is null"); return -1; }
     // torch.nn.BatchNorm1d raises "Expected more than 1 value per channel when training" (the reference's train_one
     // skips such batches, kadaptation_clip.py:341); the batch variance of one sample is 0, never a usable statistic
     if (bn_training && B < 2) { pevit_set_error("head: BatchNorm in training mode needs more than 1 sample per batch (got %d)", B); return -1; }
     hipStream_t s = (hipStream_t)stream;
     char* W = c->ws;
     if (c->saved.batch == 0) c->lay = layout_workspace(c, B);
-    if (labels) c->last_loss = loss;
+    if (has_loss) c->last_loss = loss;
     // only inside the fused step (train_fb_impl): there nobody can touch dfeat between the head and the tower backward
-    bf16* dfb = (c->in_fused_step && dfeat && labels && !c->f32) ? at<bf16>(W, c->lay.w_dfeatb) : nullptr;
+    bf16* dfb = (c->in_fused_step && dfeat && has_loss && !c->f32) ? at<bf16>(W, c->lay.w_dfeatb) : nullptr;
     c->dfeatb_of = dfb ? dfeat : nullptr;
-    return pevit_launch_head(feat, labels, c->params + c->p_head_w, c->params + c->p_head_b,
-                             labels ? c->grads + c->p_head_w : nullptr, labels ? c->grads + c->p_head_b : nullptr,
+    return pevit_launch_head(feat, labels, targets, c->params + c->p_head_w, c->params + c->p_head_b,
+                             has_loss ? c->grads + c->p_head_w : nullptr, has_loss ? c->grads + c->p_head_b : nullptr,
                              running_mean, running_var, bn_training, at<float>(W, c->lay.w_ybn), at<float>(W, c->lay.w_bnrstd),
                              logits, at<float>(W, c->lay.w_dlogits), at<float>(W, c->lay.w_dybn), loss, dfeat, B, c->D, c->C, s, dfb);
 }
+extern "C" int pevit_head_forward_backward(pevit_ctx* c, void* stream, const float* feat, const int64_t* labels,
+                                           float* running_mean, float* running_var, int bn_training, float* logits,
+                                           float* loss, float* dfeat, int B) {
+    return head_fb_impl(c, stream, feat, labels, nullptr, running_mean, running_var, bn_training, logits, loss, dfeat, B);
+}
+extern "C" int pevit_head_forward_backward_bce(pevit_ctx* c, void* stream, const float* feat, const float* targets,
+                                               float* running_mean, float* running_var, int bn_training, float* logits,
+                                               float* loss, float* dfeat, int B) {
+    if (!targets) { pevit_set_error("head_bce: targets is null (the forward alone is pevit_head_forward_backward with no labels)"); return -1; }
+    return head_fb_impl(c, stream, feat, nullptr, targets, running_mean, running_var, bn_training, logits, loss, dfeat, B);
+}
 
-static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, float* running_mean,
-                         float* running_var, int bn_training, float* logits, float* loss, int B);
+static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, const float* targets,
+                         float* running_mean, float* running_var, int bn_training, float* logits, float* loss, int B);
 extern "C" int pevit_train_forward_backward(pevit_ctx* c, void* stream, const float* images, const int64_t* labels,
                                             float* running_mean, float* running_var, int bn_training, float* logits,
                                             float* loss, int B) {
-    return train_fb_impl(c, stream, images, 0, labels, running_mean, running_var, bn_training, logits, loss, B);
+    return train_fb_impl(c, stream, images, 0, labels, nullptr, running_mean, running_var, bn_training, logits, loss, B);
 }
 extern "C" int pevit_train_forward_backward_u8(pevit_ctx* c, void* stream, const uint8_t* images, const int64_t* labels,
                                                float* running_mean, float* running_var, int bn_training, float* logits,
                                                float* loss, int B) {
     if (c && !c->img_norm_set) { pevit_set_error("train_forward_backward_u8: call pevit_set_input_norm first"); return -1; }
-    return train_fb_impl(c, stream, images, 1, labels, running_mean, running_var, bn_training, logits, loss, B);
+    return train_fb_impl(c, stream, images, 1, labels, nullptr, running_mean, running_var, bn_training, logits, loss, B);
 }
-static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, float* running_mean,
-                         float* running_var, int bn_training, float* logits, float* loss, int B) {
+extern "C" int pevit_train_forward_backward_bce(pevit_ctx* c, void* stream, const float* images, const float* targets,
+                                                float* running_mean, float* running_var, int bn_training, float* logits,
+                                                float* loss, int B) {
+    return train_fb_impl(c, stream, images, 0, nullptr, targets, running_mean, running_var, bn_training, logits, loss, B);
+}
+extern "C" int pevit_train_forward_backward_bce_u8(pevit_ctx* c, void* stream, const uint8_t* images, const float* targets,
+                                                   float* running_mean, float* running_var, int bn_training, float* logits,
+                                                   float* loss, int B) {
+    if (c && !c->img_norm_set) { pevit_set_error("train_forward_backward_bce_u8: call pevit_set_input_norm first"); return -1; }
+    return train_fb_impl(c, stream, images, 1, nullptr, targets, running_mean, running_var, bn_training, logits, loss, B);
+}
+static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, const float* targets,
+                         float* running_mean, float* running_var, int bn_training, float* logits, float* loss, int B) {
     CHECK(check_ready(c, B, "train_forward_backward"));
+    if (!labels == !targets) { pevit_set_error("train_forward_backward: exactly one of labels and targets must be given"); return -1; }
     c->gate_now = c->step_gate != nullptr;              // with a gate the gradients are cleared behind it, inside the forward pass
     if (!c->gate_now) CHECK(pevit_zero_grads(c, stream));
     const int frc = visual_forward_impl(c, stream, images, u8, nullptr, B, 1);
@@ -1408,7 +1433,7 @@ static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8,
     float* feat = at<float>(c->ws, c->lay.w_feat);
     float* dfeat = at<float>(c->ws, c->lay.w_dfeat);
     c->in_fused_step = true;
-    const int hrc = pevit_head_forward_backward(c, stream, feat, labels, running_mean, running_var, bn_training, logits, loss, dfeat, B);
+    const int hrc = head_fb_impl(c, stream, feat, labels, targets, running_mean, running_var, bn_training, logits, loss, dfeat, B);
     c->in_fused_step = false;
     if (hrc) { c->dfeatb_of = nullptr; return hrc; }
     CHECK(pevit_visual_backward(c, stream, dfeat, B));

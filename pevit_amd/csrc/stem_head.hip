@@ -4,9 +4,9 @@
 // class token + positional embedding; ln_pre.  Only the im2col gather and the class-token row
 // live here, the contraction itself is the MFMA GEMM (EPI_PATCH_EMBED adds the positional rows).
 //
-// Head, reference kadaptation_clip.py:128-132,176-185,276: BatchNorm1d(D, affine=False) ->
-// Linear(D, C) -> CrossEntropyLoss(mean), plus its backward.  B x D x C is tiny (128x512x100),
-// so these are plain f32 VALU kernels: they are launch-latency, not throughput, work.
+// Head, reference kadaptation_clip.py:128-132,176-185,273-276: BatchNorm1d(D, affine=False) ->
+// Linear(D, C) -> CrossEntropyLoss(mean), or BCEWithLogitsLoss(mean) on multi-hot targets, plus its backward.
+// B x D x C is tiny (128x512x100), so these are plain f32 VALU kernels: they are launch-latency, not throughput, work.
 #include "common.h"
 #include "kernels.h"
 
@@ -430,6 +430,63 @@ __global__ __launch_bounds__(1024) void ce_loss_kernel(const float* __restrict__
     }
 }
 
+// torch.nn.BCEWithLogitsLoss(reduction="mean") on f32 targets (multi-hot or soft), B x C row-major, as ONE workgroup for any B:
+//   l = max(x,0) - x*y + log1p(e),  sigma = x >= 0 ? 1/(1+e) : e/(1+e),  e = exp(-|x|)   (finite for every finite x)
+//   loss = sum(l) / (B*C),  dlogits = (sigma - y) * (1 / (B*C))
+// Wave w takes rows w, w + 16, ... FOUR at a time; lane holds columns lane, lane + 64 of each 128-column slice.  Every load of a
+// group is requested before its first reduction (indices clamped, no load behind a bounds branch).  Each wave adds its row sums in
+// row order, wave 0 adds the 16 partials in wave order: the same bits on every run.
+__global__ __launch_bounds__(1024) void bce_loss_kernel(const float* __restrict__ logits, const float* __restrict__ targets,
+                                                        float* __restrict__ dlogits, float* __restrict__ loss, int B, int Cc) {
+    __shared__ float part_s[16];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const float n = (float)B * (float)Cc, inv_n = 1.f / n;    // torch's mean backward: the gradient times the rounded 1/n
+    constexpr int RU = 4;                               // (8 spills VGPRs under the 1024-thread bound)
+    float wacc = 0.f;
+    for (int b0 = wid; b0 < B; b0 += 16 * RU) {
+        float rs[RU];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) rs[u] = 0.f;
+        for (int cb = 0; cb < Cc; cb += 128) {
+            const int c0 = min(cb + lane, Cc - 1), c1 = min(cb + lane + 64, Cc - 1);
+            const bool ok0 = cb + lane < Cc, ok1 = cb + lane + 64 < Cc;
+            float x0[RU], x1[RU], y0[RU], y1[RU];
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const size_t r = (size_t)min(b0 + 16 * u, B - 1) * Cc;
+                x0[u] = logits[r + c0]; x1[u] = logits[r + c1];
+                y0[u] = targets[r + c0]; y1[u] = targets[r + c1];
+            }
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int b = b0 + 16 * u;
+                const float e0 = expf(-fabsf(x0[u])), e1 = expf(-fabsf(x1[u]));
+                const float l0 = fmaxf(x0[u], 0.f) - x0[u] * y0[u] + log1pf(e0);
+                const float l1 = fmaxf(x1[u], 0.f) - x1[u] * y1[u] + log1pf(e1);
+                const float s0 = (x0[u] >= 0.f ? 1.f : e0) * __builtin_amdgcn_rcpf(1.f + e0);
+                const float s1 = (x1[u] >= 0.f ? 1.f : e1) * __builtin_amdgcn_rcpf(1.f + e1);
+                rs[u] += (ok0 ? l0 : 0.f) + (ok1 ? l1 : 0.f);
+                if (b < B) {
+                    if (ok0) dlogits[(size_t)b * Cc + cb + lane] = (s0 - y0[u]) * inv_n;
+                    if (ok1) dlogits[(size_t)b * Cc + cb + lane + 64] = (s1 - y1[u]) * inv_n;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+            if (b0 + 16 * u >= B) break;                   // wave-uniform
+            wacc += wave_sum(rs[u]);
+        }
+    }
+    if (lane == 0) part_s[wid] = wacc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int w = 0; w < 16; ++w) s += part_s[w];
+        loss[0] = s / n;
+    }
+}
+
 // loss = sum(rowloss) / (number of non-ignored rows): one wave, fixed summation order
 __global__ void loss_mean_kernel(const float* __restrict__ rowloss, const int64_t* __restrict__ labels,
                                  float* __restrict__ loss, int B) {
@@ -489,8 +546,8 @@ int pevit_launch_cls_row(const float* cls, const float* pos, float* x, int B, in
     LAUNCH_OK("cls_row_kernel");
     return 0;
 }
-int pevit_launch_head(const float* feat, const int64_t* labels, const float* W, const float* bias, float* gW, float* gb,
-                      float* running_mean, float* running_var, int training, float* ybn, float* rstd, float* logits,
+int pevit_launch_head(const float* feat, const int64_t* labels, const float* targets, const float* W, const float* bias, float* gW,
+                      float* gb, float* running_mean, float* running_var, int training, float* ybn, float* rstd, float* logits,
                       float* dlogits, float* dybn, float* loss, float* dfeat, int B, int D, int Cc, hipStream_t s, bf16* dfeat_b16) {
     hipLaunchKernelGGL(bn_fwd_kernel, dim3(ceil_div(D, 16)), dim3(256), 0, s, feat, ybn, rstd, running_mean, running_var,
                        training, B, D);
@@ -500,9 +557,12 @@ int pevit_launch_head(const float* feat, const int64_t* labels, const float* W, 
         hipLaunchKernelGGL(small_gemm_kernel, dim3(ceil_div(Cc, 32), ceil_div(B, 32)), dim3(256), 0, s, g);
         LAUNCH_OK("small_gemm_kernel");
     }
-    if (!labels) return 0;
+    if (!labels && !targets) return 0;
     float* rowloss = dybn;      // dybn is written later (by the dgrad product); reuse its head as scratch
-    if (B <= 2048) {        // one workgroup: cross entropy of every row + the mean (bit-identical to the two kernels below)
+    if (targets) {          // multi-label: BCEWithLogitsLoss on f32 targets, one workgroup for any batch
+        hipLaunchKernelGGL(bce_loss_kernel, dim3(1), dim3(1024), 0, s, logits, targets, dlogits, loss, B, Cc);
+        LAUNCH_OK("bce_loss_kernel");
+    } else if (B <= 2048) {        // one workgroup: cross entropy of every row + the mean (bit-identical to the two kernels below)
         hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(1024), 0, s, logits, labels, dlogits, rowloss, loss, B, Cc);
         LAUNCH_OK("ce_loss_kernel");
     } else {

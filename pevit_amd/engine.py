@@ -220,7 +220,8 @@ class HipEngine:
 
     def _check_batch(self, images, labels=None):
         """The C ABI takes raw pointers: reject anything that is not what it will read (f32 NCHW images -- or uint8 pixels once
-        set_input_normalization has been called -- and int64 class indices, contiguous, on this engine's device)."""
+        set_input_normalization has been called -- and int64 class indices (B,) or f32 multi-label targets (B, num_classes),
+        contiguous, on this engine's device)."""
         a = self.arch
         ok_dtype = images.dtype == torch.float32 or (images.dtype == torch.uint8 and getattr(self, "_input_norm", None) is not None)
         if images.device != self.device or not ok_dtype or not images.is_contiguous() or \
@@ -229,10 +230,26 @@ class HipEngine:
                                   f"(or uint8 after set_input_normalization); got {tuple(images.shape)} {images.dtype} on {images.device}")
         if images.shape[0] > self.max_batch:
             raise _lib.PevitError(f"batch {images.shape[0]} exceeds the bound workspace ({self.max_batch}): call ensure_batch")
-        if labels is not None and (labels.device != self.device or labels.dtype != torch.int64 or not labels.is_contiguous()
-                                   or tuple(labels.shape) != (images.shape[0],)):
-            raise _lib.PevitError(f"labels must be a contiguous int64 tensor ({images.shape[0]},) on {self.device}; "
-                                  f"got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+        return None if labels is None else self._check_labels(labels, images.shape[0])
+
+    def _check_labels(self, labels, B):
+        """True for multi-label targets (BCEWithLogitsLoss), False for class indices (cross-entropy)."""
+        if labels.device == self.device and labels.is_contiguous():
+            if labels.dtype == torch.int64 and tuple(labels.shape) == (B,):
+                return False
+            if labels.dtype == torch.float32 and tuple(labels.shape) == (B, self.num_classes):
+                return True
+        raise _lib.PevitError(f"labels must be a contiguous int64 tensor ({B},) or float32 tensor ({B}, {self.num_classes}) on "
+                              f"{self.device}; got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+
+    def _train_fn(self, images, bce):
+        """The fused C entry for this input form: uint8 or f32 pixels x cross-entropy or BCE."""
+        if images.dtype == torch.uint8:
+            return self.lib.pevit_train_forward_backward_bce_u8 if bce else self.lib.pevit_train_forward_backward_u8
+        return self.lib.pevit_train_forward_backward_bce if bce else self.lib.pevit_train_forward_backward
+
+    def _head_fn(self, labels, B):
+        return self.lib.pevit_head_forward_backward_bce if self._check_labels(labels, B) else self.lib.pevit_head_forward_backward
 
     def transformer_forward(self, x_nbe: torch.Tensor, save: bool = True) -> torch.Tensor:
         self.dp_flush()
@@ -343,12 +360,15 @@ class HipEngine:
         _lib.check(self.lib.pevit_visual_backward(self._ctx, _lib.stream_ptr(), _lib.ptr(d), B), "pevit_visual_backward")
 
     def head_forward_backward(self, feat, labels, bn_training=True, need_dfeat=True):
+        """BatchNorm1d -> Linear -> loss, forward and backward.  ``labels``: int64 (B,) -> cross-entropy, float32 (B, num_classes)
+        -> BCEWithLogitsLoss, None -> forward only."""
         self.dp_flush()
         B = feat.shape[0]
+        fn = self.lib.pevit_head_forward_backward if labels is None else self._head_fn(labels, B)
         logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=self.device)
         loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         dfeat = torch.empty_like(feat) if (need_dfeat and labels is not None) else None
-        _lib.check(self.lib.pevit_head_forward_backward(
+        _lib.check(fn(
             self._ctx, _lib.stream_ptr(), _lib.ptr(feat.contiguous()), _lib.ptr(labels), _lib.ptr(self.running_mean),
             _lib.ptr(self.running_var), int(bn_training), _lib.ptr(logits), _lib.ptr(loss), _lib.ptr(dfeat), B),
             "pevit_head_forward_backward")
@@ -359,17 +379,18 @@ class HipEngine:
         _lib.check(self.lib.pevit_zero_grads(self._ctx, _lib.stream_ptr()), "pevit_zero_grads")
 
     def forward_backward(self, images, labels, bn_training=True, logits_out=None, loss_out=None):
-        """zero_grad -> forward -> CE -> backward; gradients land in ``self.grads``.  Returns
+        """zero_grad -> forward -> loss -> backward; gradients land in ``self.grads``.  ``labels``: int64 (B,) class indices
+        (cross-entropy) or float32 (B, num_classes) multi-label targets (BCEWithLogitsLoss, mean over B * num_classes).  Returns
         (logits, loss) as device tensors without synchronising (the reference's
         ``loss.item()`` per step, kadaptation_clip.py:354, is the caller's choice).  ``logits_out`` (B, C) / ``loss_out`` (1,):
         caller-owned f32 destinations (an epoch buffer of the harness) instead of the engine's per-step buffers, which the
         next step overwrites."""
         B = images.shape[0]
-        self._check_batch(images, labels)
+        bce = self._check_batch(images, labels)
         self.forward_generation += 1
         logits = self._logits[:B] if logits_out is None else self._out_buf(logits_out, (B, self.num_classes))
         loss = self._loss if loss_out is None else self._out_buf(loss_out, (1,))
-        fn = self.lib.pevit_train_forward_backward_u8 if images.dtype == torch.uint8 else self.lib.pevit_train_forward_backward
+        fn = self._train_fn(images, bce)
         _lib.check(fn(self._ctx, _lib.stream_ptr(), _lib.ptr(images), _lib.ptr(labels), _lib.ptr(self.running_mean),
                       _lib.ptr(self.running_var), int(bn_training), _lib.ptr(logits), _lib.ptr(loss), B),
                    "pevit_train_forward_backward")
@@ -568,8 +589,7 @@ class HipEngine:
         # recorded OUTSIDE the capture (and the gated zero_grads path) into the graph
         self.dp_pipeline_off()
         B = images.shape[0]
-        self._check_batch(images, labels)
-        fn = self.lib.pevit_train_forward_backward_u8 if images.dtype == torch.uint8 else self.lib.pevit_train_forward_backward
+        fn = self._train_fn(images, self._check_batch(images, labels))
         flags = 2 if nesterov else 0
         logits, loss = self._logits[:B], self._loss
         graph = torch.cuda.CUDAGraph()
@@ -683,7 +703,7 @@ class HipEngine:
             self._dp_streamk_off = True
         self.zero_grad()
         feat = self.visual_forward(images, save=True)
-        _lib.check(self.lib.pevit_head_forward_backward(
+        _lib.check(self._head_fn(labels, B)(
             self._ctx, _lib.stream_ptr(), _lib.ptr(feat), _lib.ptr(labels), _lib.ptr(self.running_mean),
             _lib.ptr(self.running_var), int(bn_training), _lib.ptr(self._logits), _lib.ptr(self._loss),
             _lib.ptr(self._dfeat(B)), B), "pevit_head_forward_backward")

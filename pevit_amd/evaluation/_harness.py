@@ -387,10 +387,14 @@ class ClassifierBase(nn.Module):
 
     # ---- fused step ----------------------------------------------------------------------
     def can_fuse(self, criterion, optimizer) -> bool:
-        """True when one ``pevit_train_forward_backward`` + ``pevit_sgd_step`` is exactly the reference step."""
-        if not isinstance(criterion, nn.CrossEntropyLoss) or criterion.weight is not None:
+        """True when one ``pevit_train_forward_backward`` (cross-entropy) or ``pevit_train_forward_backward_bce`` (multi-label
+        BCEWithLogitsLoss) + ``pevit_sgd_step`` is exactly the reference step."""
+        if isinstance(criterion, nn.BCEWithLogitsLoss):
+            if criterion.weight is not None or criterion.pos_weight is not None or criterion.reduction != "mean":
+                return False
+        elif not isinstance(criterion, nn.CrossEntropyLoss) or criterion.weight is not None:
             return False
-        if criterion.reduction != "mean" or getattr(criterion, "label_smoothing", 0.0) != 0.0 or criterion.ignore_index >= 0:
+        elif criterion.reduction != "mean" or getattr(criterion, "label_smoothing", 0.0) != 0.0 or criterion.ignore_index >= 0:
             return False
         if type(optimizer) is not torch.optim.SGD or not isinstance(self.channel_bn, nn.BatchNorm1d):
             return False
@@ -615,7 +619,15 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
             if not target.is_cuda:
                 target = target.cuda(dev, non_blocking=True)
 
-            if fused and target.dim() == 1 and target.dtype == torch.int64:
+            # the fused step pairs the criterion with its target form: class indices for cross-entropy, (B, C) multi-hot for BCE
+            # (float targets under cross-entropy are soft labels: the autograd route)
+            if fused and isinstance(criterion, nn.BCEWithLogitsLoss):
+                fuse_now = target.dim() == 2 and target.is_floating_point()
+                if fuse_now:
+                    target = target.float()
+            else:
+                fuse_now = fused and target.dim() == 1 and target.dtype == torch.int64
+            if fuse_now:
                 n = images.shape[0]
                 direct = out_buf is not None and row + n <= out_buf.shape[0] and step < loss_buf.shape[0]
                 output, loss = model.fused_train_step(images, target, optimizer,

@@ -4,12 +4,13 @@ The reference builds its datasets through the ``vision_datasets`` hub (download,
 torchvision transforms); that dataset layer is outside this build.  What the harness needs from it is kept:
 three loaders over ``(image fp32 (3,R,R), target)`` pairs with the reference's batch size (64), the
 class-balanced deterministic validation split -- per class the first ceil(20 %) samples go to validation,
-feature.py:137-149 -- and train / val being ``Subset`` views of ONE dataset so that
-``merge_trainval_loader`` can put them back together for the final run.
+feature.py:137-149, or the greedy multi-label rule of feature.py:150-163 -- and train / val being ``Subset`` views of ONE
+dataset so that ``merge_trainval_loader`` can put them back together for the final run.
 
 Sources: ``<DATASET.ROOT>/<DATASET.DATASET>.npz`` holding already preprocessed tensors
 (``train_images``, ``train_labels``, ``test_images``, ``test_labels``; images float32 (N,3,R,R) or uint8, in
-which case INPUT.MEAN / INPUT.STD are applied), or ``DATASET.DATASET == 'synthetic'`` (seeded random tensors,
+which case INPUT.MEAN / INPUT.STD are applied; labels (N,) class indices, or (N, C) multi-hot with C > 1 -- bool, integer
+or float -- which become float32 targets for BCEWithLogitsLoss), or ``DATASET.DATASET == 'synthetic'`` (seeded random tensors,
 for smoke runs and benchmarks).
 """
 from __future__ import annotations
@@ -111,6 +112,8 @@ class TensorLoader:
 
 
 def class_balanced_split(labels: np.ndarray, val_split: float = 0.2):
+    if labels.ndim == 2 and labels.shape[1] > 1:
+        return _multilabel_split(labels, val_split)
     val = []
     for c in dict.fromkeys(labels.tolist()):                 # classes in order of first appearance, like Counter
         idx = np.where(labels == c)[0]
@@ -120,10 +123,41 @@ def class_balanced_split(labels: np.ndarray, val_split: float = 0.2):
     return train_idx, sorted(val_idx)
 
 
+def _multilabel_split(labels: np.ndarray, val_split: float):
+    """feature.py:150-163: count = ceil(column sums * val_split); while some class still has count > 0, the lowest such class
+    sends its lowest-index sample not yet taken to validation, and that sample's label row is subtracted from count."""
+    y = np.asarray(labels) > 0
+    count = np.ceil(y.sum(axis=0) * val_split)
+    taken = np.zeros(len(y), dtype=bool)
+    val = []
+    while True:
+        need = np.flatnonzero(count > 0)
+        if need.size == 0:
+            break
+        i = int(np.flatnonzero(y[:, need[0]] & ~taken)[0])
+        taken[i] = True
+        val.append(i)
+        count -= y[i]
+    return np.flatnonzero(~taken).tolist(), sorted(val)
+
+
 def few_shot_subset(labels: np.ndarray, shots: int, seed: int):
     """``shots`` samples per class, drawn with a seeded generator (the hub's sample_few_shot_subset uses its own
-    RNG stream, so the *selection* differs from the reference's for the same seed; the sizes do not)."""
+    RNG stream, so the *selection* differs from the reference's for the same seed; the sizes do not).
+
+    (N, C) multi-hot labels: the samples are visited in one seeded permutation, and a sample is kept while one of its positive
+    classes has fewer than ``shots`` kept samples; a sample with no positive class is never kept.  Every class with at least
+    ``shots`` samples ends with ``shots`` or more.  This selection is this build's own, not the hub's."""
     rng = np.random.default_rng(seed)
+    if labels.ndim == 2 and labels.shape[1] > 1:
+        y = np.asarray(labels) > 0
+        have = np.zeros(y.shape[1], dtype=np.int64)
+        keep = []
+        for i in rng.permutation(len(y)):
+            if (have[y[i]] < shots).any():
+                keep.append(i)
+                have += y[i]
+        return np.sort(np.asarray(keep, dtype=np.int64))
     keep = []
     for c in np.unique(labels):
         idx = np.where(labels == c)[0]
@@ -143,7 +177,10 @@ def _tensors(images, labels, config):
             x = (x.float() / 255.0 - mean) / std
     else:
         x = x.float()
-    return x.contiguous(), torch.as_tensor(np.asarray(labels)).long()
+    y = np.asarray(labels)
+    if y.ndim == 2 and y.shape[1] > 1:                       # multi-hot (N, C): float32 targets of BCEWithLogitsLoss
+        return x.contiguous(), torch.as_tensor(y.astype(np.float32)).contiguous()
+    return x.contiguous(), torch.as_tensor(y).long()
 
 
 def _synthetic(config):
