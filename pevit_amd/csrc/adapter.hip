@@ -445,26 +445,25 @@ int pevit_launch_prep_adapter(const float* w_down, const float* w_up, Bottleneck
     LAUNCH_OK("prep_adapter_kernel");
     return 0;
 }
-int pevit_launch_prep_compacter(const float* rule, const float* dWl, const float* dWr, const float* uWl, const float* uWr,
-                                BottleneckPanels pan, int E, int layers, LayerStrides st, hipStream_t s, int f32) {
+int pevit_launch_prep_compacter(const PrepCompacterArgs& a, hipStream_t s) {
+    const int E = a.E;
     if (E % 4) { pevit_set_error("prep_compacter: width %d not divisible by 4", E); return -1; }
-    if (f32) hipLaunchKernelGGL(prep_compacter_kernel<float>, dim3(ceil_div(64 * E, 256), layers), dim3(256), 0, s, rule, dWl, dWr, uWl, uWr,
-                                pan, E, st);
-    else hipLaunchKernelGGL(prep_compacter_kernel<bf16>, dim3(ceil_div(64 * E, 256), layers), dim3(256), 0, s, rule, dWl, dWr, uWl, uWr,
-                            pan, E, st);
+    if (a.f32) hipLaunchKernelGGL(prep_compacter_kernel<float>, dim3(ceil_div(64 * E, 256), a.layers), dim3(256), 0, s, a.rule, a.dWl, a.dWr, a.uWl,
+                                  a.uWr, a.pan, E, a.st);
+    else hipLaunchKernelGGL(prep_compacter_kernel<bf16>, dim3(ceil_div(64 * E, 256), a.layers), dim3(256), 0, s, a.rule, a.dWl, a.dWr, a.uWl,
+                            a.uWr, a.pan, E, a.st);
     LAUNCH_OK("prep_compacter_kernel");
     return 0;
 }
-int pevit_launch_tn_gemm64(const bf16* X, int ldx, const bf16* Y, int ldy, float* partial, float* csx, float* csy, int T, int E,
-                           hipStream_t s) {
-    if (E % 64 || (ldx % 8) || (ldy % 8)) { pevit_set_error("tn_gemm64: bad shape E=%d ldx=%d ldy=%d", E, ldx, ldy); return -1; }
-    hipLaunchKernelGGL(tn_gemm64_kernel, dim3(ceil_div(T, TG_ROWS) * (E / 64)), dim3(256), 0, s, X, ldx, Y, ldy, partial, csx,
-                       csy, T, E);
+int pevit_launch_tn_gemm64(const TnGemm64Args& a, hipStream_t s) {
+    if (a.E % 64 || (a.ldx % 8) || (a.ldy % 8)) { pevit_set_error("tn_gemm64: bad shape E=%d ldx=%d ldy=%d", a.E, a.ldx, a.ldy); return -1; }
+    hipLaunchKernelGGL(tn_gemm64_kernel, dim3(ceil_div(a.T, TG_ROWS) * (a.E / 64)), dim3(256), 0, s, a.X, a.ldx, a.Y, a.ldy, a.partial, a.csx,
+                       a.csy, a.T, a.E);
     LAUNCH_OK("tn_gemm64_kernel");
     return 0;
 }
-int pevit_launch_ln_bwd_affine(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                               const float* dres, float* dx, bf16* dx_bf16, float* partial, int rows, int E, hipStream_t s, int f32) {
+int pevit_launch_ln_bwd_affine(const LnBwdAffineArgs& a, hipStream_t s) {
+    const int rows = a.rows, E = a.E;
     if (E % 4 || E > 256 * LNA_MAXV) { pevit_set_error("ln_bwd_affine: unsupported width %d", E); return -1; }
     const size_t lds = (size_t)(LNA_WAVES - 1) * 3 * E * sizeof(float);      // 64.5 KiB at E = 768
     static bool attr_set = false;
@@ -474,10 +473,10 @@ int pevit_launch_ln_bwd_affine(const float* dy, const float* x, const float* mea
         HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_affine_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
         attr_set = true;
     }
-    if (f32) hipLaunchKernelGGL(ln_bwd_affine_kernel<float>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, dy, x, mean, rstd,
-                                gamma, dres, dx, dx_bf16, partial, rows, E);
-    else hipLaunchKernelGGL(ln_bwd_affine_kernel<bf16>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, dy, x, mean, rstd,
-                            gamma, dres, dx, dx_bf16, partial, rows, E);
+    if (a.f32) hipLaunchKernelGGL(ln_bwd_affine_kernel<float>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, a.dy, a.x, a.mean, a.rstd,
+                                  a.gamma, a.dres, a.dx, a.dx_bf16, a.partial, rows, E);
+    else hipLaunchKernelGGL(ln_bwd_affine_kernel<bf16>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, a.dy, a.x, a.mean, a.rstd,
+                            a.gamma, a.dres, a.dx, a.dx_bf16, a.partial, rows, E);
     LAUNCH_OK("ln_bwd_affine_kernel");
     return 0;
 }
@@ -488,10 +487,9 @@ int pevit_launch_colsum_reduce(const float* partial, int chunks, int n, float* o
     LAUNCH_OK("colsum_reduce_kernel");
     return 0;
 }
-int pevit_launch_colsum_reduce3(const float* partial, int chunks, int n, float* o0, float* o1, float* o2, int layers,
-                                size_t partial_layer, size_t out_layer, hipStream_t s) {
-    hipLaunchKernelGGL(colsum_reduce3_kernel, dim3(ceil_div(3 * n, CR_COLS), layers), dim3(256), 0, s, partial, chunks, n, o0, o1, o2,
-                       partial_layer, out_layer);
+int pevit_launch_colsum_reduce3(const ColsumReduce3Args& a, hipStream_t s) {
+    hipLaunchKernelGGL(colsum_reduce3_kernel, dim3(ceil_div(3 * a.n, CR_COLS), a.layers), dim3(256), 0, s, a.partial, a.chunks, a.n, a.o0, a.o1, a.o2,
+                       a.partial_layer, a.out_layer);
     LAUNCH_OK("colsum_reduce3_kernel");
     return 0;
 }
@@ -502,11 +500,9 @@ int pevit_launch_chain_adapter(const float* Gd, const float* Gu, float* g_down, 
     LAUNCH_OK("chain_adapter_kernel");
     return 0;
 }
-int pevit_launch_chain_compacter(const float* Gd, const float* Gu, const float* rule, const float* params, float* grads, int E,
-                                 int layers, size_t g_layer, size_t param_layer, size_t off_dWl, size_t off_dWr, size_t off_uWl,
-                                 size_t off_uWr, hipStream_t s) {
-    hipLaunchKernelGGL(chain_compacter_kernel, dim3(4, layers), dim3(64 * CC_WAVES), 0, s, Gd, Gu, rule, params, grads, E, g_layer,
-                       param_layer, off_dWl, off_dWr, off_uWl, off_uWr);
+int pevit_launch_chain_compacter(const ChainCompacterArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(chain_compacter_kernel, dim3(4, a.layers), dim3(64 * CC_WAVES), 0, s, a.Gd, a.Gu, a.rule, a.params, a.grads, a.E, a.g_layer,
+                       a.param_layer, a.off_dWl, a.off_dWr, a.off_uWl, a.off_uWr);
     LAUNCH_OK("chain_compacter_kernel");
     return 0;
 }

@@ -653,9 +653,8 @@ bool pevit_adapter_fused_ok(int E) { return E % 256 == 0 && E <= 256 * AF_MAXV &
 static int af_rows_per_wg(int T) { (void)T; return AF_ROWS; }
 int pevit_adapter_blocks(int T) { return ceil_div(T, af_rows_per_wg(T)); }
 
-int pevit_launch_adapter_fwd(int act_kind, const float* hraw, const float* bpr, const float* x_mid, const float* gamma, const float* beta,
-                             const bf16* wd, const float* b_down, const bf16* wu, const float* b_up, bf16* z, float* mean_a,
-                             float* rstd_a, bf16* act, bf16* apre, float* x_out, int T, int E, hipStream_t s) {
+int pevit_launch_adapter_fwd(const AdapterFwdArgs& a, hipStream_t s) {
+    const int T = a.T, E = a.E;
     if (af_check(T, E, "adapter_fwd")) return -1;
     const AfLds L = af_layout(E);
     const int lds = L.colred;
@@ -664,11 +663,11 @@ int pevit_launch_adapter_fwd(int act_kind, const float* hraw, const float* bpr, 
     static bool attr[2][AF_MAXV] = {};
     auto go = [&](auto kern, int slot, int nv) -> int {
         if (!attr[slot][nv - 1]) { if (af_attr(kern, 160 * 1024, "adapter_fwd")) return -1; attr[slot][nv - 1] = true; }
-        hipLaunchKernelGGL(kern, grid, block, lds, s, hraw, bpr, x_mid, gamma, beta, wd, b_down, wu, b_up, z, mean_a, rstd_a, act, apre, x_out, T, E, rb);
+        hipLaunchKernelGGL(kern, grid, block, lds, s, a.hraw, a.bpr, a.x_mid, a.gamma, a.beta, a.wd, a.b_down, a.wu, a.b_up, a.z, a.mean_a, a.rstd_a, a.act, a.apre, a.x_out, T, E, rb);
         return 0;
     };
     int rc = -1;
-    switch (4 * (act_kind != 0) + E / 256 - 1) {
+    switch (4 * (a.act_kind != 0) + E / 256 - 1) {
         case 0: rc = go(adapter_fwd_kernel<0, 1>, 0, 1); break;
         case 1: rc = go(adapter_fwd_kernel<0, 2>, 0, 2); break;
         case 2: rc = go(adapter_fwd_kernel<0, 3>, 0, 3); break;
@@ -683,37 +682,32 @@ int pevit_launch_adapter_fwd(int act_kind, const float* hraw, const float* bpr, 
     return 0;
 }
 
-// tn_*: the contraction range of the launch (see af_tn_range); tn_x1 = nullptr / tn_x2 = nullptr leave a product out.
-//   product 1: partial1[chunk][E][64] = sum over the chunk's rows of x1[r][e] y1[r][j]             (x1: [T][E] bf16, y1: [T][64] bf16)
-//   product 2: the same for x2, y2 -> partial2, and csy2[chunk][64] = column sums of y2
-int pevit_launch_adapter_bwd(int act_kind, const bf16* dyb, const float* dres, const bf16* wuT, const bf16* saved, const bf16* wdT,
-                             const float* hraw, const float* bpr, const float* mean_a, const float* rstd_a, const float* gamma,
-                             bf16* dpre, bf16* dh_bf16, float* partial, int T, int E, hipStream_t s, const bf16* tn_x1,
-                             const bf16* tn_y1, float* tn_partial1, const bf16* tn_x2, const bf16* tn_y2, float* tn_partial2,
-                             float* tn_csy2, int tn_blocks) {
+// tn_*: the contraction range of the launch (see af_tn_range and AdapterBwdArgs)
+int pevit_launch_adapter_bwd(const AdapterBwdArgs& a, hipStream_t s) {
+    const int T = a.T, E = a.E;
     if (af_check(T, E, "adapter_bwd")) return -1;
-    if (tn_x2 && tn_y2 == dpre) { pevit_set_error("adapter_bwd: the deferred contraction reads the d pre buffer this launch writes"); return -1; }
+    if (a.tn_x2 && a.tn_y2 == a.dpre) { pevit_set_error("adapter_bwd: the deferred contraction reads the d pre buffer this launch writes"); return -1; }
     const AfLds L = af_layout(E);
     const int rb = af_rows_per_wg(T);
     const int nb = ceil_div(T, rb), units = ceil_div(T, TN_CHUNK) * (E / 64);
     AfTn tn;
-    tn.X1 = tn_x1; tn.Y1 = tn_y1; tn.P1 = tn_partial1; tn.n1 = tn_x1 ? units : 0;
-    tn.X2 = tn_x2; tn.Y2 = tn_y2; tn.P2 = tn_partial2; tn.csy2 = tn_csy2; tn.n2 = tn_x2 ? units : 0;
+    tn.X1 = a.tn_x1; tn.Y1 = a.tn_y1; tn.P1 = a.tn_partial1; tn.n1 = a.tn_x1 ? units : 0;
+    tn.X2 = a.tn_x2; tn.Y2 = a.tn_y2; tn.P2 = a.tn_partial2; tn.csy2 = a.tn_csy2; tn.n2 = a.tn_x2 ? units : 0;
     // workgroups of the contraction range: one per unit pair.  (Measured, Adapter ViT-B/32 batch 128, same box: no folding 4.92 ms per
     // step; 40 / 80 persistent workgroups walking the pairs 4.96; 112: 4.78; one per pair (300): 4.72 -- a unit is a latency chain
     // (requests -> LDS -> matrix core -> stores), so more of them in flight beats fewer, longer-lived ones.)
-    const int ntn = min(ceil_div(tn.n1 + tn.n2, 2), tn_blocks > 0 ? tn_blocks : (1 << 30));
+    const int ntn = min(ceil_div(tn.n1 + tn.n2, 2), a.tn_blocks > 0 ? a.tn_blocks : (1 << 30));
     const int lds = ntn ? max(L.total_bwd, 2 * TNH_BYTES) : L.total_bwd;
     const dim3 grid(nb + ntn), block(64 * AF_WAVES);
     static bool attr[4][AF_MAXV] = {};
     // dres == nullptr: the bf16 gradient stream (round 5) -- dx_out is read from dyb wherever the f32 copy was
     auto go = [&](auto kern, int slot, int nv) -> int {
         if (!attr[slot][nv - 1]) { if (af_attr(kern, 160 * 1024, "adapter_bwd")) return -1; attr[slot][nv - 1] = true; }
-        hipLaunchKernelGGL(kern, grid, block, lds, s, dyb, dres, wuT, saved, wdT, hraw, bpr, mean_a, rstd_a, gamma, dpre, dh_bf16, partial, T, E, rb, nb, tn);
+        hipLaunchKernelGGL(kern, grid, block, lds, s, a.dyb, a.dres, a.wuT, a.saved, a.wdT, a.hraw, a.bpr, a.mean_a, a.rstd_a, a.gamma, a.dpre, a.dh_bf16, a.partial, T, E, rb, nb, tn);
         return 0;
     };
     int rc = -1;
-    const int slot = 2 * (act_kind != 0) + (dres ? 0 : 1);
+    const int slot = 2 * (a.act_kind != 0) + (a.dres ? 0 : 1);
 #define AF_BWD_CASE(A, R, N) case 4 * (2 * A + R) + N - 1: rc = go(adapter_bwd_kernel<A, R != 0, N>, 2 * A + R, N); break;
     switch (4 * slot + E / 256 - 1) {
         AF_BWD_CASE(0, 0, 1) AF_BWD_CASE(0, 0, 2) AF_BWD_CASE(0, 0, 3) AF_BWD_CASE(0, 0, 4)

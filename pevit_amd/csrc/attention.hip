@@ -639,8 +639,10 @@ int launch_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* out, int
 #define ATT_NW_MID_F 4
 #endif
 
-int pevit_launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, bf16* out, int ldo, float* lse, int B, int H,
-                          int N, hipStream_t s, unsigned char* out8) {
+int pevit_launch_attn_fwd(const AttnArgs& a, hipStream_t s) {
+    const bf16 *q = a.q, *k = a.k, *v = a.v;
+    bf16* out = a.out; float* lse = a.lse; unsigned char* out8 = a.out_fp8;
+    const int ldo = a.ldo, B = a.B, H = a.H, N = a.N;
     if (N < 1 || N > 288) { pevit_set_error("attn_fwd: tokens per image N=%d outside [1,288]", N); return -1; }
     if (ldo % 8) { pevit_set_error("attn_fwd: ldo must be a multiple of 8"); return -1; }
     if (N <= 64) return launch_fwd<2, 4, ATT_LD_FWD>(q, k, v, out, ldo, lse, B, H, N, s, out8);
@@ -650,8 +652,10 @@ int pevit_launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, bf16* out
     return launch_fwd<9, ATT_NW_BIG_F, ATT_LD_FWD>(q, k, v, out, ldo, lse, B, H, N, s, out8);
 }
 
-int pevit_launch_attn_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* out, int ldo, const bf16* dout,
-                          int lddo, const float* lse, bf16* dqkv, int ld, int B, int H, int N, hipStream_t s, int dout_cls_only) {
+int pevit_launch_attn_bwd(const AttnArgs& a, hipStream_t s) {
+    const bf16 *q = a.q, *k = a.k, *v = a.v, *out = a.out, *dout = a.dout;
+    const float* lse = a.lse; bf16* dqkv = a.dqkv;
+    const int ldo = a.ldo, lddo = a.lddo, ld = a.ld, B = a.B, H = a.H, N = a.N, dout_cls_only = a.dout_cls_only;
     if (N < 1 || N > 288) { pevit_set_error("attn_bwd: tokens per image N=%d outside [1,288]", N); return -1; }
     if ((ldo % 8) || (lddo % 8) || (ld % 8)) { pevit_set_error("attn_bwd: leading dims must be multiples of 8"); return -1; }
     // N <= 64: all four operands LDS-resident; above, the loop side of each pass

@@ -299,9 +299,9 @@ int pevit_attn_delta_hpw(int B, int H, int N) {
     return hpw;
 }
 
-int pevit_launch_attn_fwd_delta(bf16* q, const bf16* k, bf16* v, const float* t, const bf16* q16, const float* bias,
-                                float ascale, bf16* out, int ldo, float* lse, int B, int H, int N, hipStream_t s) {
+int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s) {
     constexpr int HPW = 6, NW = 12, PER = 4;
+    const int ldo = a.ldo, B = a.B, H = a.H, N = a.N;
     if (pevit_attn_delta_hpw(B, H, N) != HPW) { pevit_set_error("attn_fwd_delta: no fused form for H=%d N=%d", H, N); return -1; }
     if (ldo % 8) { pevit_set_error("attn_fwd_delta: ldo must be a multiple of 8"); return -1; }
     const int bytes = 3 * ((HPW - 1) * N + (N + 16 > 64 ? N + 16 : 64)) * AFD_LDR * 2;
@@ -315,7 +315,7 @@ int pevit_launch_attn_fwd_delta(bf16* q, const bf16* k, bf16* v, const float* t,
             }
             attr[slot] = true;
         }
-        hipLaunchKernelGGL(kern, dim3(ceil_div(B * H, HPW)), dim3(64 * NW), bytes, s, q, k, v, t, q16, bias, ascale, out, ldo, lse, B, H, N, g_timeline);
+        hipLaunchKernelGGL(kern, dim3(ceil_div(B * H, HPW)), dim3(64 * NW), bytes, s, a.q, a.k, a.v, a.t, a.q16, a.bias, a.ascale, a.out, ldo, a.lse, B, H, N, g_timeline);
         return 0;
     };
     const int rc = (H == 12 && N == 50) ? go(attn_fwd_delta_kernel<HPW, NW, PER, 12, 50>, 1) : go(attn_fwd_delta_kernel<HPW, NW, PER, 0, 0>, 0);

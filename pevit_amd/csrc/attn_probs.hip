@@ -100,8 +100,8 @@ int launch(const bf16* q, const bf16* k, const float* lse, float* out, int B, in
 
 }  // namespace
 
-int pevit_launch_attn_probs(const bf16* q, const bf16* k, const float* lse, float* out, int B, int H, int N, int average, hipStream_t s) {
-    if (N < 1 || N > 384) { pevit_set_error("attn_probs: N=%d outside [1,384]", N); return -1; }
-    if (B < 1 || H < 1) { pevit_set_error("attn_probs: bad B=%d / H=%d", B, H); return -1; }
-    return average ? launch<true>(q, k, lse, out, B, H, N, s) : launch<false>(q, k, lse, out, B, H, N, s);
+int pevit_launch_attn_probs(const AttnArgs& a, hipStream_t s) {
+    if (a.N < 1 || a.N > 384) { pevit_set_error("attn_probs: N=%d outside [1,384]", a.N); return -1; }
+    if (a.B < 1 || a.H < 1) { pevit_set_error("attn_probs: bad B=%d / H=%d", a.B, a.H); return -1; }
+    return a.average ? launch<true>(a.q, a.k, a.lse, a.probs, a.B, a.H, a.N, s) : launch<false>(a.q, a.k, a.lse, a.probs, a.B, a.H, a.N, s);
 }

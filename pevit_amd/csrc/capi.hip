@@ -159,6 +159,8 @@ inline bool attention_site(const pevit_ctx* c) {
     return c->d.method == PEVIT_KADAPTATION || c->d.method == PEVIT_LORA;
 }
 inline bool post_mlp(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER || c->d.method == PEVIT_COMPACTER; }
+// activation of the post-MLP bottleneck as the fused kernels take it: 0 = ReLU (Adapter), 1 = gelu_new (Compacter)
+inline int act_kind(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER ? 0 : 1; }
 
 // the launch paths of a step of batch B: a pure function of the context's dims, weight format and knobs, the batch and the CU count
 StepPlan plan_step(const pevit_ctx* c, int B) {
@@ -560,20 +562,28 @@ int prep_adapters(pevit_ctx* c, hipStream_t s) {
     const float* lp = c->params + c->p_layer0;
     if (c->d.method == PEVIT_KADAPTATION) {
         const float* r = c->params;
-        CHECK(pevit_launch_prep_kadapt(r, r + 1024, r + 2048, r + 3072, lp, lp + E, panels(c, 0), c->E, c->ascale, c->L, st, s, c->f32));
+        PrepKadaptArgs a;
+        a.rule1_l = r; a.rule1_r = r + 1024; a.rule2_l = r + 2048; a.rule2_r = r + 3072; a.q_left = lp; a.q_right = lp + E;
+        a.pan = panels(c, 0); a.E = c->E; a.ascale = c->ascale; a.layers = c->L; a.st = st; a.f32 = c->f32;
+        CHECK(pevit_launch_prep_kadapt(a, s));
     } else if (c->d.method == PEVIT_LORA) {
         const size_t rE = (size_t)c->d.lora_rank * E;
-        CHECK(pevit_launch_prep_lora(lp, lp + rE, lp + 2 * rE, lp + 3 * rE, c->d.lora_rank, panels(c, 0), c->E, c->ascale,
-                                     c->L, st, s, c->f32));
+        PrepLoraArgs a;
+        a.a1q = lp; a.a2q = lp + rE; a.a1v = lp + 2 * rE; a.a2v = lp + 3 * rE; a.r = c->d.lora_rank;
+        a.pan = panels(c, 0); a.E = c->E; a.ascale = c->ascale; a.layers = c->L; a.st = st; a.f32 = c->f32;
+        CHECK(pevit_launch_prep_lora(a, s));
     } else if (post_mlp(c)) {
         const BlockArena& b0 = c->blk[0];
         BottleneckPanels bp{at<bf16>(c->arena, b0.wd), at<bf16>(c->arena, b0.wdT), at<bf16>(c->arena, b0.wu),
                             at<bf16>(c->arena, b0.wuT)};
-        if (c->d.method == PEVIT_ADAPTER)
+        if (c->d.method == PEVIT_ADAPTER) {
             CHECK(pevit_launch_prep_adapter(lp + c->o_dw, lp + c->o_uw, bp, c->E, c->L, st, s, c->f32));
-        else
-            CHECK(pevit_launch_prep_compacter(at<float>(c->arena, c->a_phm), lp + c->o_dWl, lp + c->o_dWr, lp + c->o_uWl,
-                                              lp + c->o_uWr, bp, c->E, c->L, st, s, c->f32));
+        } else {
+            PrepCompacterArgs a;
+            a.rule = at<float>(c->arena, c->a_phm); a.dWl = lp + c->o_dWl; a.dWr = lp + c->o_dWr; a.uWl = lp + c->o_uWl; a.uWr = lp + c->o_uWr;
+            a.pan = bp; a.E = c->E; a.layers = c->L; a.st = st; a.f32 = c->f32;
+            CHECK(pevit_launch_prep_compacter(a, s));
+        }
     }
     return 0;
 }
@@ -641,6 +651,18 @@ GemmParams gpw(const pevit_ctx* c, const bf16* A, int lda, size_t w_off, int ldb
     return p;
 }
 
+// operands of the attention core of layer l as its forward left them in the saved slots: q / k / v planes (head layout), attn_out, lse
+AttnArgs attn_args(const pevit_ctx* c, int B, int l) {
+    const LayerSaved& v = c->lay.sav[l];
+    const bf16* qkv = at<bf16>(c->ws, v.qkv);
+    const size_t plane = (size_t)B * c->N * c->E;
+    AttnArgs a;
+    a.q = qkv; a.k = eadv(c, qkv, plane); a.v = eadv(c, qkv, 2 * plane);
+    a.out = at<bf16>(c->ws, v.attn_out); a.ldo = c->E; a.lse = at<float>(c->ws, v.lse);
+    a.B = B; a.H = c->H; a.N = c->N;
+    return a;
+}
+
 // The attention half of block l between ln_1 and out_proj (MultiheadAttention.forward, model.py:612-812): the QKV product with the
 // adapter columns t of the attention-site methods, delta-add and the attention core.  Reads the layer's xn1 (or its e4m3 copy a8),
 // leaves q / k / v in the head layout, lse and attn_out in the layer's saved slots.  Shared by the block walk and the attention seam.
@@ -680,22 +702,25 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
     const float* dbias = nullptr;
     if (c->d.method == PEVIT_KADAPTATION) dbias = c->params + c->p_layer0 + c->p_layer_stride * l + 4 * (size_t)E;
     if (pl.attn_delta) {
+        AttnFwdDeltaArgs a;
+        a.q = qkv; a.k = qkv + plane; a.v = qkv + 2 * plane; a.t = at<float>(W, v.t); a.q16 = at<bf16>(A, b.q16); a.bias = dbias;
+        a.ascale = c->ascale; a.out = at<bf16>(W, v.attn_out); a.ldo = E; a.lse = at<float>(W, v.lse); a.B = B; a.H = H; a.N = N;
         PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T, (double)T * E * (3 + 2 + 1) * 2 + (double)T * 64 * 4 + (double)B * H * N * 4,   // q, k, v in; q', v', out
-             pevit_launch_attn_fwd_delta(qkv, qkv + plane, qkv + 2 * plane, at<float>(W, v.t), at<bf16>(A, b.q16), dbias, c->ascale,
-                                         at<bf16>(W, v.attn_out), E, at<float>(W, v.lse), B, H, N, s));
+             pevit_launch_attn_fwd_delta(a, s));
     } else {
         if (site) {
+            DeltaAddArgs a;
+            a.qbuf = qkv; a.vbuf = eadv(c, qkv, 2 * plane); a.t = at<float>(W, v.t); a.q32 = at<float>(A, b.q32); a.q16 = at<bf16>(A, b.q16);
+            a.bias = dbias; a.ascale = c->ascale; a.B = B; a.N = N; a.E = E; a.f32 = c->f32;
             PROF(c, s, PEVIT_PROF_DELTA_ADD, T, (double)T * E * 4 * c->es + (double)T * 64 * 4,     // q and v read + written, t read
-                 pevit_launch_delta_add(qkv, eadv(c, qkv, 2 * plane), at<float>(W, v.t), at<float>(A, b.q32), at<bf16>(A, b.q16), dbias,
-                                        c->ascale, B, N, E, s, c->f32));
+                 pevit_launch_delta_add(a, s));
         }
+        AttnArgs a = attn_args(c, B, l);
+        a.out_fp8 = attn8;
         if (c->f32)
-            CHECK(pevit_launch_attn_fwd_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), (const float*)eadv(c, qkv, 2 * plane),
-                                            at<float>(W, v.attn_out), E, at<float>(W, v.lse), B, H, N, s));
+            CHECK(pevit_launch_attn_fwd_f32(a, s));
         else
-            PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2 + (double)B * H * N * 4,
-                 pevit_launch_attn_fwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<float>(W, v.lse), B,
-                                       H, N, s, attn8));
+            PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2 + (double)B * H * N * 4, pevit_launch_attn_fwd(a, s));
     }
     return 0;
 }
@@ -720,9 +745,12 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
         // x = x + attn(ln_1(x))                                         model.py:973
         unsigned char* a8 = c->fp8act ? at<unsigned char>(W, c->lay.w_a8) : nullptr;
         unsigned char* attn8 = c->fp8act ? at<unsigned char>(W, c->lay.w_attn8) : nullptr;
-        PROF(c, s, PEVIT_PROF_LN_FWD, T, (double)T * E * (4 + c->es),
-             pevit_launch_ln_fwd(x_in, at<float>(A, b.ln1w), at<float>(A, b.ln1b), T, E, at<bf16>(W, v.xn1), nullptr,
-                                 at<float>(W, v.mean1), at<float>(W, v.rstd1), s, 0, c->f32, a8));
+        {
+            LnFwdArgs a;
+            a.x = x_in; a.gamma = at<float>(A, b.ln1w); a.beta = at<float>(A, b.ln1b); a.rows = T; a.E = E; a.y_bf16 = at<bf16>(W, v.xn1);
+            a.mean = at<float>(W, v.mean1); a.rstd = at<float>(W, v.rstd1); a.f32 = c->f32; a.y_fp8 = a8;
+            PROF(c, s, PEVIT_PROF_LN_FWD, T, (double)T * E * (4 + c->es), pevit_launch_ln_fwd(a, s));
+        }
         CHECK(attn_core_fwd(c, s, B, pl, l, a8, attn8));
         // rows of the tail of this block: all T, or (last block, cls_only) the B class-token rows, which
         // sit N*E elements apart in every [T][E] buffer
@@ -736,9 +764,12 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
             CHECK(gemm(c, EPI_BIAS_RESID_F32, p, s));
         }
         // x = x + mlp(ln_2(x))                                          model.py:974
-        PROF(c, s, PEVIT_PROF_LN_FWD, R, (double)R * E * (4 + c->es),
-             pevit_launch_ln_fwd(x_mid, at<float>(A, b.ln2w), at<float>(A, b.ln2b), R, E, at<bf16>(W, c->lay.w_xn2), nullptr,
-                                 at<float>(W, v.mean2), at<float>(W, v.rstd2), s, (size_t)rs, c->f32, a8));
+        {
+            LnFwdArgs a;
+            a.x = x_mid; a.gamma = at<float>(A, b.ln2w); a.beta = at<float>(A, b.ln2b); a.rows = R; a.E = E; a.y_bf16 = at<bf16>(W, c->lay.w_xn2);
+            a.mean = at<float>(W, v.mean2); a.rstd = at<float>(W, v.rstd2); a.xstride = (size_t)rs; a.f32 = c->f32; a.y_fp8 = a8;
+            PROF(c, s, PEVIT_PROF_LN_FWD, R, (double)R * E * (4 + c->es), pevit_launch_ln_fwd(a, s));
+        }
         {
             GemmParams p = gpw(c, at<bf16>(W, c->lay.w_xn2), E, b.wfc, E, 4 * E, R, 4 * E, E, b.sfc);
             if (a8) { p.A = reinterpret_cast<const bf16*>(a8); p.a_fp8 = 1; p.out2_fp8 = 1; }     // gelu(h) leaves as e4m3 codes
@@ -761,11 +792,12 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
             GemmParams p = gp(at<bf16>(W, c->lay.w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
             p.outf = at<float>(W, v.hf32); p.ldo = E;
             CHECK(gemm(c, EPI_F32, p, s));
-            PROF(c, s, PEVIT_PROF_ADAPTER_FWD, T, (double)T * E * (4 + 4 + 4 + 2) + (double)T * 64 * 4,
-                 pevit_launch_adapter_fwd(c->d.method == PEVIT_ADAPTER ? 0 : 1, at<float>(W, v.hf32), at<float>(A, b.bpr), x_mid, lp + c->o_nw,
-                                          lp + c->o_nb, at<bf16>(A, b.wd), lp + c->o_db, at<bf16>(A, b.wu), lp + c->o_ub, at<bf16>(W, v.z),
-                                          at<float>(W, v.mean_a), at<float>(W, v.rstd_a), at<bf16>(W, v.act), at<bf16>(W, v.apre), x_out,
-                                          T, E, s));
+            AdapterFwdArgs a;
+            a.act_kind = act_kind(c); a.hraw = at<float>(W, v.hf32); a.bpr = at<float>(A, b.bpr); a.x_mid = x_mid;
+            a.gamma = lp + c->o_nw; a.beta = lp + c->o_nb; a.wd = at<bf16>(A, b.wd); a.b_down = lp + c->o_db; a.wu = at<bf16>(A, b.wu);
+            a.b_up = lp + c->o_ub; a.z = at<bf16>(W, v.z); a.mean_a = at<float>(W, v.mean_a); a.rstd_a = at<float>(W, v.rstd_a);
+            a.act = at<bf16>(W, v.act); a.apre = at<bf16>(W, v.apre); a.x_out = x_out; a.T = T; a.E = E;
+            PROF(c, s, PEVIT_PROF_ADAPTER_FWD, T, (double)T * E * (4 + 4 + 4 + 2) + (double)T * 64 * 4, pevit_launch_adapter_fwd(a, s));
             continue;
         }
         float* ytmp = at<float>(W, c->lay.w_dxn);           // x_mid + h ; scratch that is free during the forward pass
@@ -775,8 +807,12 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
             p.outf2 = at<float>(W, v.hf32); p.ldo2 = E;
             CHECK(gemm(c, EPI_BIAS_RESID_KEEP, p, s));
         }
-        CHECK(pevit_launch_ln_fwd(at<float>(W, v.hf32), lp + c->o_nw, lp + c->o_nb, T, E, at<bf16>(W, v.z), nullptr,
-                                  at<float>(W, v.mean_a), at<float>(W, v.rstd_a), s, 0, c->f32));
+        {
+            LnFwdArgs a;
+            a.x = at<float>(W, v.hf32); a.gamma = lp + c->o_nw; a.beta = lp + c->o_nb; a.rows = T; a.E = E; a.y_bf16 = at<bf16>(W, v.z);
+            a.mean = at<float>(W, v.mean_a); a.rstd = at<float>(W, v.rstd_a); a.f32 = c->f32;
+            CHECK(pevit_launch_ln_fwd(a, s));
+        }
         {
             GemmParams p = gp(at<bf16>(W, v.z), E, at<bf16>(A, b.wd), E, 64, T, 64, E);
             p.bias = lp + c->o_db;
@@ -813,10 +849,8 @@ int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
     const int chunks = pevit_lowrank_chunks(T);
     const BlockArena& b = c->blk[l];
     const LayerSaved& v = c->lay.sav[l];
-    bf16* qkv = at<bf16>(W, v.qkv);
     bf16* dqkv = at<bf16>(W, c->lay.w_dqkv);
     bf16* dyb = at<bf16>(W, c->lay.w_dyb);
-    const size_t plane = (size_t)T * E;
     const int R = cls ? B : T;
     const int rs = cls ? N * E : E;            // row stride of [T][E] buffers
     {
@@ -824,38 +858,41 @@ int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
         p.outb = at<bf16>(W, c->lay.w_dO); p.ldob = rs;
         CHECK(gemm(c, EPI_BF16, p, s));
     }
-    if (c->f32)
-        CHECK(pevit_launch_attn_bwd_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), (const float*)eadv(c, qkv, 2 * plane),
-                                        at<float>(W, v.attn_out), E, at<float>(W, c->lay.w_dO), E, at<float>(W, v.lse), (float*)dqkv,
-                                        c->NQ, B, H, N, s));
-    else
-        PROF(c, s, PEVIT_PROF_ATTN_BWD, T, (double)T * E * (N <= 64 ? 7 : 8) * 2 + (double)B * H * N * 4,     // q, k, v, (out: N > 64 only), dout in; dq, dk, dv out
-             pevit_launch_attn_bwd(qkv, qkv + plane, qkv + 2 * plane, at<bf16>(W, v.attn_out), E, at<bf16>(W, c->lay.w_dO), E,
-                                   at<float>(W, v.lse), dqkv, c->NQ, B, H, N, s, (cls && N <= 64) ? 1 : 0));
-    float* partial = at<float>(W, c->lay.w_partial + (size_t)l * c->lay.partial_layer);
-    float* dbias = at<float>(W, c->lay.w_dbias + (size_t)l * c->lay.dbias_layer);
+    {
+        AttnArgs a = attn_args(c, B, l);
+        a.dout = at<bf16>(W, c->lay.w_dO); a.lddo = E; a.dqkv = dqkv; a.ld = c->NQ; a.dout_cls_only = (cls && N <= 64) ? 1 : 0;
+        if (c->f32)
+            CHECK(pevit_launch_attn_bwd_f32(a, s));
+        else
+            PROF(c, s, PEVIT_PROF_ATTN_BWD, T, (double)T * E * (N <= 64 ? 7 : 8) * 2 + (double)B * H * N * 4,     // q, k, v, (out: N > 64 only), dout in; dq, dk, dv out
+                 pevit_launch_attn_bwd(a, s));
+    }
+    if (!pl.site) return 0;
+    // the low-rank adapter gradients: u (f32, and bf16 into the 64 adapter columns of dqkv), dQ / d bias and dP partials of this layer
+    LowrankArgs a;
+    a.dqkv = dqkv; a.ld = c->NQ; a.qT = at<bf16>(A, b.qT); a.q32 = at<float>(A, b.q32); a.u_bf16_cols = eadv(c, dqkv, 3 * (size_t)E);
+    a.t = at<float>(W, v.t); a.ldx = E; a.B = B; a.H = H; a.N = N; a.E = E;
+    a.partial = at<float>(W, c->lay.w_partial + (size_t)l * c->lay.partial_layer);
+    a.dbias_partial = at<float>(W, c->lay.w_dbias + (size_t)l * c->lay.dbias_layer);
     if (pl.lowrank_combo) {
         // u, dQ_q, dQ_v, d bias of this layer and the dP of the layer before it in ONE launch (lowrank.hip lowrank_combo_kernel)
-        float* u_cur = at<float>(W, w.u_par ? c->lay.w_u32b : c->lay.w_u32);
-        const LayerSaved* pv = w.prev_layer >= 0 ? &c->lay.sav[w.prev_layer] : nullptr;
+        a.this_layer = 1; a.u32 = at<float>(W, w.u_par ? c->lay.w_u32b : c->lay.w_u32);
+        if (w.prev_layer >= 0) {
+            a.prev = 1; a.xn_prev = at<bf16>(W, c->lay.sav[w.prev_layer].xn1); a.u32_prev = w.u_last;
+            a.partial_prev = at<float>(W, c->lay.w_partial + (size_t)w.prev_layer * c->lay.partial_layer);
+        }
         PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 3 * 2 + (double)T * 64 * 14 + (double)chunks * 4 * E * 32 * 4,
-             pevit_launch_lowrank_combo(1, pv ? 1 : 0, dqkv, c->NQ, at<bf16>(A, b.qT), u_cur, dqkv + 3 * E, at<float>(W, v.t), partial, dbias,
-                                        pv ? at<bf16>(W, pv->xn1) : nullptr, E, w.u_last,
-                                        pv ? at<float>(W, c->lay.w_partial + (size_t)w.prev_layer * c->lay.partial_layer) : nullptr, B, H, N, E, s));
-        w.u_last = u_cur; w.prev_layer = l; w.u_par ^= 1;
-    } else if (pl.site) {
-        float* u32 = at<float>(W, c->lay.w_u32);
+             pevit_launch_lowrank_combo(a, s));
+        w.u_last = a.u32; w.prev_layer = l; w.u_par ^= 1;
+    } else {
+        a.u32 = at<float>(W, c->lay.w_u32); a.xn = at<bf16>(W, v.xn1); a.chunks = chunks; a.xcd_order = pl.lowrank_xcd;
         if (c->f32) {
-            CHECK(pevit_launch_lowrank_u_f32((const float*)dqkv, c->NQ, at<float>(A, b.q32), u32, (float*)eadv(c, dqkv, 3 * (size_t)E), B, H,
-                                             N, E, s));
-            CHECK(pevit_launch_lowrank_grad_f32(at<float>(W, v.xn1), E, u32, (const float*)dqkv, c->NQ, at<float>(W, v.t), partial, dbias,
-                                                chunks, B, H, N, E, s));
+            CHECK(pevit_launch_lowrank_u_f32(a, s));
+            CHECK(pevit_launch_lowrank_grad_f32(a, s));
         } else {
-            PROF(c, s, PEVIT_PROF_LOWRANK_U, T, (double)T * E * 2 * 2 + (double)T * 64 * 6,
-                 pevit_launch_lowrank_u(dqkv, c->NQ, at<bf16>(A, b.qT), u32, dqkv + 3 * E, B, H, N, E, s));
+            PROF(c, s, PEVIT_PROF_LOWRANK_U, T, (double)T * E * 2 * 2 + (double)T * 64 * 6, pevit_launch_lowrank_u(a, s));
             PROF(c, s, PEVIT_PROF_LOWRANK_GRAD, T, (double)T * E * 3 * 2 + (double)T * 64 * 8 + (double)chunks * 4 * E * 32 * 4,
-                 pevit_launch_lowrank_grad(at<bf16>(W, v.xn1), E, u32, dqkv, c->NQ, at<float>(W, v.t), partial, dbias, chunks, B, H, N, E, s,
-                                           pl.lowrank_xcd));
+                 pevit_launch_lowrank_grad(a, s));
         }
     }
     return 0;
@@ -876,15 +913,27 @@ int attn_qkv_dx(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, f
 // end of a walk: the deferred dP of the last layer walked (lowrank_combo)
 int attn_walk_end(pevit_ctx* c, hipStream_t s, int B, AttnGradWalk& w) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
-    if (w.prev_layer >= 0)
-        PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 2 + (double)T * 64 * 4,
-             pevit_launch_lowrank_combo(0, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at<bf16>(c->ws, c->lay.sav[w.prev_layer].xn1), E,
-                                        w.u_last, at<float>(c->ws, c->lay.w_partial + (size_t)w.prev_layer * c->lay.partial_layer), B, H, N, E, s));
+    if (w.prev_layer >= 0) {
+        LowrankArgs a;      // this_layer stays 0: only the "previous layer" operands are read
+        a.prev = 1; a.xn_prev = at<bf16>(c->ws, c->lay.sav[w.prev_layer].xn1); a.ldx = E; a.u32_prev = w.u_last;
+        a.partial_prev = at<float>(c->ws, c->lay.w_partial + (size_t)w.prev_layer * c->lay.partial_layer);
+        a.B = B; a.H = H; a.N = N; a.E = E;
+        PROF(c, s, PEVIT_PROF_LOWRANK_BWD, T, (double)T * E * 2 + (double)T * 64 * 4, pevit_launch_lowrank_combo(a, s));
+    }
     w.prev_layer = -1;
     return 0;
 }
 
 int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l_lo, int l_hi);
+
+// post-MLP adapters: a token-contracted weight-gradient product G = X^T Y of layer l into its per-chunk partials (X: [T][E], Y: [T][64])
+int tn_product(pevit_ctx* c, hipStream_t s, int T, const bf16* X, const bf16* Y, size_t w_partial, int l, bool csy) {
+    TnGemm64Args a;
+    a.X = X; a.ldx = c->E; a.Y = Y; a.ldy = 64; a.partial = at<float>(c->ws, w_partial + (size_t)l * c->lay.tn_layer);
+    if (csy) a.csy = at<float>(c->ws, c->lay.w_csy + (size_t)l * c->lay.csy_layer);
+    a.T = T; a.E = c->E;
+    return c->f32 ? pevit_launch_tn_gemm64_f32(a, s) : pevit_launch_tn_gemm64(a, s);
+}
 
 // backward of the blocks.  On entry ws+w_dxa holds dL/dx_final (f32) and ws+w_dyb its bf16 copy (StepPlan::gstream16: only
 // the bf16 copy is read).
@@ -904,6 +953,11 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool
     const bool gs16 = pl.gstream16;
     // bytes LayerNorm backward moves per row element: dy (stored type or f32) + x + residual gradient read, gradient written
     const size_t ln_bwd_bytes = (pl.dx_stored ? c->es : 4) + 4 + (gs16 ? c->es : 4 + 4) + c->es;
+    // what both LayerNorm backward launches of every block share: the LN-input gradient of the dX GEMM before them in dxn, the bf16
+    // copy of the result (the next dX GEMM's operand) in dyb
+    LnBwdArgs ln_bwd_base;
+    ln_bwd_base.dy = dxn; ln_bwd_base.dx_bf16 = dyb; ln_bwd_base.E = E; ln_bwd_base.f32 = c->f32; ln_bwd_base.dy_stored = pl.dx_stored;
+    ln_bwd_base.res16 = gs16;
     AttnGradWalk walk;
     int tn_pend = -1, tn_par = 0;          // post-MLP adapters: layer whose d W_down product is still owed, and the d pre buffer in turn
     const bf16* tn_pend_dpre = nullptr;
@@ -917,26 +971,26 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool
             const bool fold = pl.tn_fold;      // both weight-gradient products inside the backward launch
             bf16* dpre = at<bf16>(W, (fold && tn_par) ? c->lay.w_dpre2 : c->lay.w_dpre);
             // d W_up[e][j] = sum_r dx_out[r][e] act[r][j] ; d b_up = colsum(dx_out)
-            if (fold) {}
-            else if (c->f32)
-                CHECK(pevit_launch_tn_gemm64_f32((const float*)dyb, E, at<float>(W, v.act), 64, at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer),
-                                                 nullptr, nullptr, T, E, s));
-            else
-                CHECK(pevit_launch_tn_gemm64(dyb, E, at<bf16>(W, v.act), 64, at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer),
-                                             nullptr, nullptr, T, E, s));
+            if (!fold) CHECK(tn_product(c, s, T, dyb, at<bf16>(W, v.act), c->lay.w_tnU, l, false));
             if (pl.adapter_fused) {
                 const int dwl = tn_pend >= 0 ? tn_pend : l;       // the layer whose d W_down product this launch carries (if any)
                 // d pre, d z and the LayerNorm backward with its affine-gradient column sums in one launch (adapter_fused.hip); the
                 // forward pass left the c_proj accumulators WITHOUT their bias in hf32
-                PROF(c, s, PEVIT_PROF_ADAPTER_BWD, T, (double)T * E * (2 + 4 + 4 + 2) + (double)T * 64 * 4,
-                     pevit_launch_adapter_bwd(c->d.method == PEVIT_ADAPTER ? 0 : 1, dyb, gs16 ? nullptr : dxa, at<bf16>(A, b.wuT),
-                                              c->d.method == PEVIT_ADAPTER ? at<bf16>(W, v.act) : at<bf16>(W, v.apre), at<bf16>(A, b.wdT),
-                                              at<float>(W, v.hf32), at<float>(A, b.bpr), at<float>(W, v.mean_a), at<float>(W, v.rstd_a),
-                                              lp + c->o_nw, dpre, at<bf16>(W, c->lay.w_dhb), at<float>(W, c->lay.w_lnp + (size_t)l * c->lay.lnp_layer), T, E, s,
-                                              fold ? dyb : nullptr, at<bf16>(W, v.act), at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer),
-                                              (fold && tn_pend >= 0) ? at<bf16>(W, c->lay.sav[dwl].z) : nullptr, tn_pend_dpre,
-                                              at<float>(W, c->lay.w_tnD + (size_t)dwl * c->lay.tn_layer), at<float>(W, c->lay.w_csy + (size_t)dwl * c->lay.csy_layer),
-                                              pl.tn_fold_wgs));
+                AdapterBwdArgs a;
+                a.act_kind = act_kind(c); a.dyb = dyb; a.wuT = at<bf16>(A, b.wuT); a.wdT = at<bf16>(A, b.wdT);
+                if (!gs16) a.dres = dxa;
+                a.saved = at<bf16>(W, a.act_kind == 0 ? v.act : v.apre);
+                a.hraw = at<float>(W, v.hf32); a.bpr = at<float>(A, b.bpr); a.mean_a = at<float>(W, v.mean_a); a.rstd_a = at<float>(W, v.rstd_a);
+                a.gamma = lp + c->o_nw; a.dpre = dpre; a.dh_bf16 = at<bf16>(W, c->lay.w_dhb);
+                a.partial = at<float>(W, c->lay.w_lnp + (size_t)l * c->lay.lnp_layer); a.T = T; a.E = E;
+                if (fold) { a.tn_x1 = dyb; a.tn_y1 = at<bf16>(W, v.act); a.tn_partial1 = at<float>(W, c->lay.w_tnU + (size_t)l * c->lay.tn_layer); }
+                if (fold && tn_pend >= 0) {
+                    a.tn_x2 = at<bf16>(W, c->lay.sav[dwl].z); a.tn_y2 = tn_pend_dpre;
+                    a.tn_partial2 = at<float>(W, c->lay.w_tnD + (size_t)dwl * c->lay.tn_layer);
+                    a.tn_csy2 = at<float>(W, c->lay.w_csy + (size_t)dwl * c->lay.csy_layer);
+                }
+                a.tn_blocks = pl.tn_fold_wgs;
+                PROF(c, s, PEVIT_PROF_ADAPTER_BWD, T, (double)T * E * (2 + 4 + 4 + 2) + (double)T * 64 * 4, pevit_launch_adapter_bwd(a, s));
                 if (fold) { tn_pend = l; tn_pend_dpre = dpre; tn_par ^= 1; }
             } else {
                 {   // d act = dx_out W_up ; d pre = d act * act'(pre)
@@ -952,18 +1006,15 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool
                 }
             }
             // d W_down[j][e] = sum_r d pre[r][j] z[r][e] ; d b_down = colsum(d pre)
-            if (fold) {}
-            else if (c->f32)
-                CHECK(pevit_launch_tn_gemm64_f32(at<float>(W, v.z), E, (const float*)dpre, 64, at<float>(W, c->lay.w_tnD + (size_t)l * c->lay.tn_layer),
-                                                 nullptr, at<float>(W, c->lay.w_csy + (size_t)l * c->lay.csy_layer), T, E, s));
-            else
-                CHECK(pevit_launch_tn_gemm64(at<bf16>(W, v.z), E, dpre, 64, at<float>(W, c->lay.w_tnD + (size_t)l * c->lay.tn_layer), nullptr,
-                                             at<float>(W, c->lay.w_csy + (size_t)l * c->lay.csy_layer), T, E, s));
+            if (!fold) CHECK(tn_product(c, s, T, at<bf16>(W, v.z), dpre, c->lay.w_tnD, l, true));
             // d h = dx_out + LN_a-backward(d z) ; partial sums for d gamma_a, d beta_a
-            if (!pl.adapter_fused)
-                CHECK(pevit_launch_ln_bwd_affine(dxn, at<float>(W, v.hf32), at<float>(W, v.mean_a), at<float>(W, v.rstd_a), lp + c->o_nw,
-                                                 dxa, nullptr, at<bf16>(W, c->lay.w_dhb),
-                                                 at<float>(W, c->lay.w_lnp + (size_t)l * c->lay.lnp_layer), T, E, s, c->f32));
+            if (!pl.adapter_fused) {
+                LnBwdAffineArgs a;
+                a.dy = dxn; a.x = at<float>(W, v.hf32); a.mean = at<float>(W, v.mean_a); a.rstd = at<float>(W, v.rstd_a); a.gamma = lp + c->o_nw;
+                a.dres = dxa; a.dx_bf16 = at<bf16>(W, c->lay.w_dhb); a.partial = at<float>(W, c->lay.w_lnp + (size_t)l * c->lay.lnp_layer);
+                a.rows = T; a.E = E; a.f32 = c->f32;
+                CHECK(pevit_launch_ln_bwd_affine(a, s));
+            }
             mlp_dy = at<bf16>(W, c->lay.w_dhb);
             if (l == 0 && !need_dx0) break;     // nothing trainable below the first block's adapter
         }
@@ -987,31 +1038,38 @@ int blocks_backward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool
         }
         // fp8: the bf16 copy feeds the out-projection backward, whose contraction runs over out_proj's output channels.
         // gs16: the residual gradient is the bf16 copy dyb itself, read and rewritten in place (no f32 pair dxa / dxb)
-        PROF(c, s, PEVIT_PROF_LN_BWD, R, (double)R * E * ln_bwd_bytes,
-             pevit_launch_ln_bwd(dxn, at<float>(W, v.x_mid), at<float>(W, v.mean2), at<float>(W, v.rstd2), at<float>(A, b.ln2w),
-                                 gs16 ? reinterpret_cast<const float*>(dyb) : dxa, gs16 ? nullptr : dxb, dyb, R, E, s, (size_t)rs,
-                                 c->fp8 ? at<float>(A, b.so) : nullptr, c->f32, pl.dx_stored, 0, gs16,
-                                 gs16 && c->fp8 ? at<float>(A, b.spr) : nullptr));
+        {
+            LnBwdArgs a = ln_bwd_base;
+            a.x = at<float>(W, v.x_mid); a.mean = at<float>(W, v.mean2); a.rstd = at<float>(W, v.rstd2); a.gamma = at<float>(A, b.ln2w);
+            a.dres = gs16 ? reinterpret_cast<const float*>(dyb) : dxa;
+            if (!gs16) a.dx_out = dxb;
+            a.rows = R; a.xstride = (size_t)rs;
+            if (c->fp8) a.bf16_colscale = at<float>(A, b.so);
+            if (gs16 && c->fp8) a.res_colscale = at<float>(A, b.spr);
+            PROF(c, s, PEVIT_PROF_LN_BWD, R, (double)R * E * ln_bwd_bytes, pevit_launch_ln_bwd(a, s));
+        }
         // ---- attention branch
         CHECK(attn_core_bwd(c, s, B, pl, l, cls, walk));
         if (l > 0 || need_dx0) {
             CHECK(attn_qkv_dx(c, s, B, pl, l, nullptr));
             // fp8: this bf16 copy is the upstream gradient of layer l-1's c_proj backward.  gs16: the f32 copy only where the caller
             // asked for dx (the lowest block walked).  Last block, class-token pruning: the residual gradient sits on the class rows only
-            float* dx_out = gs16 ? ((need_dx0 && l == l_lo) ? dxa : nullptr) : dxa;
-            PROF(c, s, PEVIT_PROF_LN_BWD, T, (double)T * E * ln_bwd_bytes,
-                 pevit_launch_ln_bwd(dxn, at<float>(W, v.x_in), at<float>(W, v.mean1), at<float>(W, v.rstd1), at<float>(A, b.ln1w),
-                                     gs16 ? reinterpret_cast<const float*>(dyb) : dxb, dx_out, dyb, T, E, s, 0,
-                                     (c->fp8 && l > 0) ? at<float>(A, c->blk[l - 1].spr) : nullptr, c->f32, pl.dx_stored, cls ? N : 0, gs16,
-                                     gs16 && c->fp8 ? at<float>(A, b.so) : nullptr));
+            LnBwdArgs a = ln_bwd_base;
+            a.x = at<float>(W, v.x_in); a.mean = at<float>(W, v.mean1); a.rstd = at<float>(W, v.rstd1); a.gamma = at<float>(A, b.ln1w);
+            a.dres = gs16 ? reinterpret_cast<const float*>(dyb) : dxb;
+            if (!gs16 || (need_dx0 && l == l_lo)) a.dx_out = dxa;
+            a.rows = T;
+            if (c->fp8 && l > 0) a.bf16_colscale = at<float>(A, c->blk[l - 1].spr);
+            if (cls) a.res_period = N;
+            if (gs16 && c->fp8) a.res_colscale = at<float>(A, b.so);
+            PROF(c, s, PEVIT_PROF_LN_BWD, T, (double)T * E * ln_bwd_bytes, pevit_launch_ln_bwd(a, s));
         }
     }
     // (the deferred dP belongs to the attention-site methods, the owed d W_down product to the post-MLP ones: at most one of the
     // two below has work)
     CHECK(attn_walk_end(c, s, B, walk));
     if (tn_pend >= 0)                   // the d W_down product of the last adapter walked
-        CHECK(pevit_launch_tn_gemm64(at<bf16>(W, c->lay.sav[tn_pend].z), E, tn_pend_dpre, 64, at<float>(W, c->lay.w_tnD + (size_t)tn_pend * c->lay.tn_layer),
-                                     nullptr, at<float>(W, c->lay.w_csy + (size_t)tn_pend * c->lay.csy_layer), T, E, s));
+        CHECK(tn_product(c, s, T, at<bf16>(W, c->lay.sav[tn_pend].z), tn_pend_dpre, c->lay.w_tnD, tn_pend, true));
     return reduce_adapter_grads(c, s, B, pl, l_lo, l_hi);
 }
 
@@ -1025,17 +1083,22 @@ int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl,
     const size_t pl0 = c->p_layer0 + c->p_layer_stride * l_lo;          // first float of layer l_lo's parameters
     if (nl <= 0) return 0;
     if (c->d.method == PEVIT_KADAPTATION) {
-        CHECK(pevit_launch_chain_kadapt(at<float>(W, c->lay.w_partial + (size_t)l_lo * c->lay.partial_layer), c->lay.partial_layer / 4,
-                                        at<float>(W, c->lay.w_dbias + (size_t)l_lo * c->lay.dbias_layer), c->lay.dbias_layer / 4, chunks,
-                                        c->ascale, nl, at<float>(W, c->lay.w_G) + (size_t)l_lo * 4 * E * 32,
-                                        at<float>(W, c->lay.w_rule) + (size_t)l_lo * 4096, c->params, c->grads, pl0, c->p_layer_stride, E, s));
+        ChainKadaptArgs a;
+        a.partial = at<float>(W, c->lay.w_partial + (size_t)l_lo * c->lay.partial_layer); a.partial_layer = c->lay.partial_layer / 4;
+        a.dbias_partial = at<float>(W, c->lay.w_dbias + (size_t)l_lo * c->lay.dbias_layer); a.dbias_layer = c->lay.dbias_layer / 4;
+        a.chunks = chunks; a.ascale = c->ascale; a.layers = nl; a.G = at<float>(W, c->lay.w_G) + (size_t)l_lo * 4 * E * 32;
+        a.rule_scratch = at<float>(W, c->lay.w_rule) + (size_t)l_lo * 4096; a.params = c->params; a.grads = c->grads;
+        a.p_layer0 = pl0; a.p_layer_stride = c->p_layer_stride; a.E = E;
+        CHECK(pevit_launch_chain_kadapt(a, s));
         // the shared rule factors collect from every layer: each range adds its own layers (top first, one running sum), so a
         // backward that never reaches block 0 keeps its rule contributions and a walk in ranges equals the one-call backward
         CHECK(pevit_launch_rule_sum(at<float>(W, c->lay.w_rule), c->grads, l_lo, l_hi, s));
     } else if (c->d.method == PEVIT_LORA) {
-        CHECK(pevit_launch_chain_lora(at<float>(W, c->lay.w_partial + (size_t)l_lo * c->lay.partial_layer), c->lay.partial_layer / 4, chunks,
-                                      c->ascale, c->d.lora_rank, nl, at<float>(W, c->lay.w_G) + (size_t)l_lo * 4 * E * 32, c->grads, pl0,
-                                      c->p_layer_stride, E, s));
+        ChainLoraArgs a;
+        a.partial = at<float>(W, c->lay.w_partial + (size_t)l_lo * c->lay.partial_layer); a.partial_layer = c->lay.partial_layer / 4;
+        a.chunks = chunks; a.ascale = c->ascale; a.r = c->d.lora_rank; a.layers = nl; a.G = at<float>(W, c->lay.w_G) + (size_t)l_lo * 4 * E * 32;
+        a.grads = c->grads; a.p_layer0 = pl0; a.p_layer_stride = c->p_layer_stride; a.E = E;
+        CHECK(pevit_launch_chain_lora(a, s));
     } else if (pl.post_mlp) {
         const int tch = pevit_tn_chunks(T), lnb = pl.adapter_fused ? pevit_adapter_blocks(T) : pevit_lna_blocks(T);
         const size_t ps = c->p_layer_stride, gl = (size_t)E * 64;
@@ -1050,13 +1113,19 @@ int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl,
         // d b_up from the f32 column sums of the upstream gradient (third plane of the LN partials)
         CHECK(pevit_launch_colsum_reduce(at<float>(W, c->lay.w_csy + (size_t)l_lo * c->lay.csy_layer), tch, 64, g0 + c->o_db, nl,
                                          c->lay.csy_layer / 4, ps, s));
-        CHECK(pevit_launch_colsum_reduce3(at<float>(W, c->lay.w_lnp + (size_t)l_lo * c->lay.lnp_layer), lnb, E, g0 + c->o_nw, g0 + c->o_nb,
-                                          g0 + c->o_ub, nl, c->lay.lnp_layer / 4, ps, s));
+        {
+            ColsumReduce3Args a;
+            a.partial = at<float>(W, c->lay.w_lnp + (size_t)l_lo * c->lay.lnp_layer); a.chunks = lnb; a.n = E;
+            a.o0 = g0 + c->o_nw; a.o1 = g0 + c->o_nb; a.o2 = g0 + c->o_ub; a.layers = nl; a.partial_layer = c->lay.lnp_layer / 4; a.out_layer = ps;
+            CHECK(pevit_launch_colsum_reduce3(a, s));
+        }
         if (c->d.method == PEVIT_ADAPTER) {
             CHECK(pevit_launch_chain_adapter(Gd, Gu, g0 + c->o_dw, g0 + c->o_uw, E, nl, gl, ps, s));
         } else {
-            CHECK(pevit_launch_chain_compacter(Gd, Gu, at<float>(c->arena, c->a_phm), c->params + pl0, g0, E, nl, gl, ps, c->o_dWl,
-                                               c->o_dWr, c->o_uWl, c->o_uWr, s));
+            ChainCompacterArgs a;
+            a.Gd = Gd; a.Gu = Gu; a.rule = at<float>(c->arena, c->a_phm); a.params = c->params + pl0; a.grads = g0; a.E = E; a.layers = nl;
+            a.g_layer = gl; a.param_layer = ps; a.off_dWl = c->o_dWl; a.off_dWr = c->o_dWr; a.off_uWl = c->o_uWl; a.off_uWr = c->o_uWr;
+            CHECK(pevit_launch_chain_compacter(a, s));
         }
     }
     return 0;
@@ -1133,13 +1202,9 @@ extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, co
     if (pl.site) CHECK(prep_adapters(c, s));
     CHECK(attn_core_fwd(c, s, B, pl, layer, nullptr, nullptr));
     if (weights) {
-        const bf16* qkv = at<bf16>(W, v.qkv);
-        const size_t plane = (size_t)T * E;
-        if (c->f32)
-            CHECK(pevit_launch_attn_probs_f32((const float*)qkv, (const float*)eadv(c, qkv, plane), at<float>(W, v.lse), weights, B, c->H,
-                                              N, average_weights ? 1 : 0, s));
-        else
-            CHECK(pevit_launch_attn_probs(qkv, qkv + plane, at<float>(W, v.lse), weights, B, c->H, N, average_weights ? 1 : 0, s));
+        AttnArgs a = attn_args(c, B, layer);
+        a.probs = weights; a.average = average_weights ? 1 : 0;
+        CHECK(c->f32 ? pevit_launch_attn_probs_f32(a, s) : pevit_launch_attn_probs(a, s));
     }
     {
         GemmParams p = gpw(c, at<bf16>(W, v.attn_out), E, b.wo, E, E, T, E, E, b.so);
@@ -1197,8 +1262,12 @@ extern "C" int pevit_sgd_step(pevit_ctx* c, void* stream, float lr, float moment
     unsigned* poison = (c->ws && c->sk_slots) ? at<unsigned>(c->ws, c->lay.w_skflag) + c->sk_slots : nullptr;
     unsigned* skipped = poison ? at<unsigned>(c->ws, c->lay.w_skflag) + PEVIT_SK_MAX_SLOTS + 1 : nullptr;
     float* loss_slot = c->last_loss; c->last_loss = nullptr;
-    return pevit_launch_sgd(c->params, c->grads, c->mom, c->grad_mask, c->n_total, lr, momentum, wd, flags,
-                            grad_scale, (hipStream_t)stream, poison, skipped, c->ext_poison, (poison || c->ext_poison) ? loss_slot : nullptr);
+    SgdArgs a;
+    a.p = c->params; a.g = c->grads; a.mom = c->mom; a.has_grad = c->grad_mask; a.n = c->n_total;
+    a.lr = lr; a.momentum = momentum; a.wd = wd; a.first_step = flags; a.grad_scale = grad_scale;
+    a.poison = poison; a.skipped = skipped; a.poison2 = c->ext_poison;
+    if (poison || c->ext_poison) a.loss_slot = loss_slot;
+    return pevit_launch_sgd(a, (hipStream_t)stream);
 }
 
 // a device word owned by the caller (e.g. pevit_ar_error_word) that, while non-zero, makes pevit_sgd_step withhold the update --
@@ -1280,11 +1349,12 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
     char* W = c->ws; char* A = c->arena;
     const int E = c->E, N = c->N, T = B * N;
     float* xpre = at<float>(W, c->lay.w_dxn);               // scratch, free during the forward pass
-    if (u8)
-        PROF(c, s, PEVIT_PROF_IM2COL, B, (double)B * 3 * c->R * c->R * 1 + (double)B * c->G2 * c->Kpatch * c->es,
-             pevit_launch_im2col_u8((const unsigned char*)images_any, c->img_mean, c->img_std, at<bf16>(W, c->lay.w_patches), B, c->R, c->P,
-                                    c->Kpatch, s, c->f32));
-    else
+    if (u8) {
+        Im2colU8Args a;
+        a.img = (const unsigned char*)images_any; a.mean3 = c->img_mean; a.std3 = c->img_std; a.out = at<bf16>(W, c->lay.w_patches);
+        a.B = B; a.R = c->R; a.P = c->P; a.Kp = c->Kpatch; a.f32 = c->f32;
+        PROF(c, s, PEVIT_PROF_IM2COL, B, (double)B * 3 * c->R * c->R * 1 + (double)B * c->G2 * c->Kpatch * c->es, pevit_launch_im2col_u8(a, s));
+    } else
         PROF(c, s, PEVIT_PROF_IM2COL, B, (double)B * 3 * c->R * c->R * 4 + (double)B * c->G2 * c->Kpatch * c->es,
              pevit_launch_im2col(images, at<bf16>(W, c->lay.w_patches), B, c->R, c->P, c->Kpatch, s, c->f32));
     CHECK(pevit_launch_cls_row(at<float>(A, c->a_cls), at<float>(A, c->a_pos), xpre, B, N, E, s));
@@ -1293,8 +1363,12 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
         p.resid = at<float>(A, c->a_pos); p.ldr = E; p.outf = xpre; p.ldo = E; p.Ntok = N;
         CHECK(gemm(c, EPI_PATCH_EMBED, p, s));
     }
-    CHECK(pevit_launch_ln_fwd(xpre, at<float>(A, c->a_lnpre_w), at<float>(A, c->a_lnpre_b), T, E, nullptr,
-                              at<float>(W, c->lay.sav[0].x_in), nullptr, nullptr, s));
+    {
+        LnFwdArgs a;     // ln_pre: f32 out, no statistics kept (nothing below the first block is trainable)
+        a.x = xpre; a.gamma = at<float>(A, c->a_lnpre_w); a.beta = at<float>(A, c->a_lnpre_b); a.rows = T; a.E = E;
+        a.y_f32 = at<float>(W, c->lay.sav[0].x_in);
+        CHECK(pevit_launch_ln_fwd(a, s));
+    }
     if (c->gate_now) {                                  // fused step with a gate (pevit_set_step_gate): parameters and gradient buffer from here on
         c->gate_now = false;
         HIP_OK(hipStreamWaitEvent(s, c->step_gate, 0));
@@ -1302,9 +1376,13 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
     }
     CHECK(blocks_forward(c, s, B, pl, pl.cls_prune));
     // ln_post on the class token of every image (row b*N), then @ proj
-    CHECK(pevit_launch_ln_fwd(at<float>(W, c->lay.w_xfinal), at<float>(A, c->a_lnpost_w), at<float>(A, c->a_lnpost_b), B, E,
-                              at<bf16>(W, c->lay.w_xpost), nullptr, at<float>(W, c->lay.w_pmean), at<float>(W, c->lay.w_prstd), s,
-                              (size_t)N * E, c->f32));
+    {
+        LnFwdArgs a;
+        a.x = at<float>(W, c->lay.w_xfinal); a.gamma = at<float>(A, c->a_lnpost_w); a.beta = at<float>(A, c->a_lnpost_b); a.rows = B; a.E = E;
+        a.y_bf16 = at<bf16>(W, c->lay.w_xpost); a.mean = at<float>(W, c->lay.w_pmean); a.rstd = at<float>(W, c->lay.w_prstd);
+        a.xstride = (size_t)N * E; a.f32 = c->f32;
+        CHECK(pevit_launch_ln_fwd(a, s));
+    }
     {
         GemmParams p = gp(at<bf16>(W, c->lay.w_xpost), E, at<bf16>(A, c->a_proj), E, c->D, B, c->D, E);
         p.outf = feat ? feat : at<float>(W, c->lay.w_feat); p.ldo = c->D;
@@ -1348,10 +1426,12 @@ extern "C" int pevit_visual_backward_part(pevit_ctx* c, void* stream, const floa
             if (!pl.gstream16) CHECK(pevit_launch_zero(W + c->lay.w_dxa, (size_t)T * E * 4, s));      // (the bf16 stream never reads the f32 copy)
             CHECK(pevit_launch_zero(W + c->lay.w_dyb, (size_t)T * E * c->es, s));
         }
-        CHECK(pevit_launch_ln_bwd(at<float>(W, c->lay.w_dxpost), at<float>(W, c->lay.w_xfinal), at<float>(W, c->lay.w_pmean),
-                                  at<float>(W, c->lay.w_prstd), at<float>(A, c->a_lnpost_w), nullptr, at<float>(W, c->lay.w_dxa),
-                                  at<bf16>(W, c->lay.w_dyb), B, E, s, (size_t)N * E,
-                                  c->fp8 ? at<float>(A, c->blk[c->L - 1].spr) : nullptr, c->f32));
+        LnBwdArgs a;     // ln_post backward on the class-token rows: no residual gradient joins here
+        a.dy = at<float>(W, c->lay.w_dxpost); a.x = at<float>(W, c->lay.w_xfinal); a.mean = at<float>(W, c->lay.w_pmean);
+        a.rstd = at<float>(W, c->lay.w_prstd); a.gamma = at<float>(A, c->a_lnpost_w); a.dx_out = at<float>(W, c->lay.w_dxa);
+        a.dx_bf16 = at<bf16>(W, c->lay.w_dyb); a.rows = B; a.E = E; a.xstride = (size_t)N * E; a.f32 = c->f32;
+        if (c->fp8) a.bf16_colscale = at<float>(A, c->blk[c->L - 1].spr);
+        CHECK(pevit_launch_ln_bwd(a, s));
     }
     CHECK(blocks_backward(c, s, B, pl, false, cls, l_hi, l_lo));
     return 0;
@@ -1380,10 +1460,13 @@ static int head_fb_impl(pevit_ctx* c, void* stream, const float* feat, const int
     // only inside the fused step (train_fb_impl): there nobody can touch dfeat between the head and the tower backward
     bf16* dfb = (c->in_fused_step && dfeat && has_loss && !c->f32) ? at<bf16>(W, c->lay.w_dfeatb) : nullptr;
     c->dfeatb_of = dfb ? dfeat : nullptr;
-    return pevit_launch_head(feat, labels, targets, c->params + c->p_head_w, c->params + c->p_head_b,
-                             has_loss ? c->grads + c->p_head_w : nullptr, has_loss ? c->grads + c->p_head_b : nullptr,
-                             running_mean, running_var, bn_training, at<float>(W, c->lay.w_ybn), at<float>(W, c->lay.w_bnrstd),
-                             logits, at<float>(W, c->lay.w_dlogits), at<float>(W, c->lay.w_dybn), loss, dfeat, B, c->D, c->C, s, dfb);
+    HeadArgs a;
+    a.feat = feat; a.labels = labels; a.targets = targets; a.W = c->params + c->p_head_w; a.bias = c->params + c->p_head_b;
+    if (has_loss) { a.gW = c->grads + c->p_head_w; a.gb = c->grads + c->p_head_b; }
+    a.running_mean = running_mean; a.running_var = running_var; a.training = bn_training;
+    a.ybn = at<float>(W, c->lay.w_ybn); a.rstd = at<float>(W, c->lay.w_bnrstd); a.logits = logits; a.dlogits = at<float>(W, c->lay.w_dlogits);
+    a.dybn = at<float>(W, c->lay.w_dybn); a.loss = loss; a.dfeat = dfeat; a.B = B; a.D = c->D; a.Cc = c->C; a.dfeat_bf16 = dfb;
+    return pevit_launch_head(a, s);
 }
 extern "C" int pevit_head_forward_backward(pevit_ctx* c, void* stream, const float* feat, const int64_t* labels,
                                            float* running_mean, float* running_var, int bn_training, float* logits,
@@ -1588,38 +1671,50 @@ extern "C" int pevit_op_dequant_fp8(void* stream, const void* codes, const float
 }
 extern "C" int pevit_op_ln_fwd(void* stream, const float* x, const float* gamma, const float* beta, int rows, int E,
                                void* y_bf16, float* y_f32, float* mean, float* rstd) {
-    return pevit_launch_ln_fwd(x, gamma, beta, rows, E, (bf16*)y_bf16, y_f32, mean, rstd, (hipStream_t)stream);
-}
-extern "C" int pevit_op_ln_bwd(void* stream, const float* dy, const float* x, const float* mean, const float* rstd,
-                               const float* gamma, const float* dres, float* dx, void* dx_bf16, int rows, int E) {
-    return pevit_launch_ln_bwd(dy, x, mean, rstd, gamma, dres, dx, (bf16*)dx_bf16, rows, E, (hipStream_t)stream);
+    LnFwdArgs a;
+    a.x = x; a.gamma = gamma; a.beta = beta; a.rows = rows; a.E = E; a.y_bf16 = (bf16*)y_bf16; a.y_f32 = y_f32; a.mean = mean; a.rstd = rstd;
+    return pevit_launch_ln_fwd(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_ln_bwd_scaled(void* stream, const float* dy, const float* x, const float* mean, const float* rstd,
                                       const float* gamma, const float* dres, float* dx, void* dx_bf16, int rows, int E,
                                       const float* bf16_colscale) {
-    return pevit_launch_ln_bwd(dy, x, mean, rstd, gamma, dres, dx, (bf16*)dx_bf16, rows, E, (hipStream_t)stream, 0, bf16_colscale);
+    LnBwdArgs a;
+    a.dy = dy; a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dres = dres; a.dx_out = dx; a.dx_bf16 = (bf16*)dx_bf16;
+    a.rows = rows; a.E = E; a.bf16_colscale = bf16_colscale;
+    return pevit_launch_ln_bwd(a, (hipStream_t)stream);
+}
+extern "C" int pevit_op_ln_bwd(void* stream, const float* dy, const float* x, const float* mean, const float* rstd,
+                               const float* gamma, const float* dres, float* dx, void* dx_bf16, int rows, int E) {
+    return pevit_op_ln_bwd_scaled(stream, dy, x, mean, rstd, gamma, dres, dx, dx_bf16, rows, E, nullptr);
 }
 extern "C" int pevit_op_attn_fwd(void* stream, const void* q, const void* k, const void* v, void* out, int ldo,
                                  float* lse, int B, int H, int N) {
-    return pevit_launch_attn_fwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, ldo, lse, B, H, N,
-                                 (hipStream_t)stream);
+    AttnArgs a;
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.ldo = ldo; a.lse = lse; a.B = B; a.H = H; a.N = N;
+    return pevit_launch_attn_fwd(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_attn_bwd(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
                                  const void* dout, int lddo, const float* lse, void* dqkv, int ld, int B, int H, int N) {
-    return pevit_launch_attn_bwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)out, ldo,
-                                 (const bf16*)dout, lddo, lse, (bf16*)dqkv, ld, B, H, N, (hipStream_t)stream);
+    AttnArgs a;      // (out and lse are only read by the backward)
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)const_cast<void*>(out); a.ldo = ldo;
+    a.lse = const_cast<float*>(lse); a.B = B; a.H = H; a.N = N; a.dout = (const bf16*)dout; a.lddo = lddo; a.dqkv = (bf16*)dqkv; a.ld = ld;
+    return pevit_launch_attn_bwd(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_cast_bf16(void* stream, const float* src, void* dst, size_t n, float scale) {
     return pevit_launch_cast_bf16(src, (bf16*)dst, n, scale, (hipStream_t)stream);
 }
 extern "C" int pevit_op_delta_add(void* stream, void* qbuf, void* vbuf, const float* t, const void* q16,
                                   const float* bias, float ascale, int B, int N, int E) {
-    return pevit_launch_delta_add((bf16*)qbuf, (bf16*)vbuf, t, nullptr, (const bf16*)q16, bias, ascale, B, N, E, (hipStream_t)stream);
+    DeltaAddArgs a;
+    a.qbuf = (bf16*)qbuf; a.vbuf = (bf16*)vbuf; a.t = t; a.q16 = (const bf16*)q16; a.bias = bias; a.ascale = ascale; a.B = B; a.N = N; a.E = E;
+    return pevit_launch_delta_add(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_attn_fwd_delta(void* stream, void* q, const void* k, void* v, const float* t, const void* q16, const float* bias,
                                        float ascale, void* out, int ldo, float* lse, int B, int H, int N) {
-    return pevit_launch_attn_fwd_delta((bf16*)q, (const bf16*)k, (bf16*)v, t, (const bf16*)q16, bias, ascale, (bf16*)out, ldo, lse, B, H, N,
-                                       (hipStream_t)stream);
+    AttnFwdDeltaArgs a;
+    a.q = (bf16*)q; a.k = (const bf16*)k; a.v = (bf16*)v; a.t = t; a.q16 = (const bf16*)q16; a.bias = bias; a.ascale = ascale;
+    a.out = (bf16*)out; a.ldo = ldo; a.lse = lse; a.B = B; a.H = H; a.N = N;
+    return pevit_launch_attn_fwd_delta(a, (hipStream_t)stream);
 }
 extern "C" int pevit_debug_occupy(void* stream, int workgroups, int lds_bytes, double microseconds) {
     return pevit_launch_occupy(workgroups, lds_bytes, microseconds, (hipStream_t)stream);
@@ -1628,17 +1723,22 @@ extern "C" int pevit_debug_timeline(void* buf) { pevit_attn_delta_set_timeline(b
 extern "C" int pevit_op_attn_delta_hpw(int B, int H, int N) { return pevit_attn_delta_hpw(B, H, N); }
 extern "C" int pevit_op_attn_probs(void* stream, const void* q, const void* k, const float* lse, float* out, int B, int H, int N,
                                    int average) {
-    return pevit_launch_attn_probs((const bf16*)q, (const bf16*)k, lse, out, B, H, N, average, (hipStream_t)stream);
+    AttnArgs a;      // (lse is only read)
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.lse = const_cast<float*>(lse); a.probs = out; a.B = B; a.H = H; a.N = N; a.average = average;
+    return pevit_launch_attn_probs(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_lowrank_u(void* stream, const void* dqkv, int ld, const void* qT, float* u32, void* u_cols, int B,
                                   int H, int N, int E) {
-    return pevit_launch_lowrank_u((const bf16*)dqkv, ld, (const bf16*)qT, u32, (bf16*)u_cols, B, H, N, E,
-                                  (hipStream_t)stream);
+    LowrankArgs a;
+    a.dqkv = (const bf16*)dqkv; a.ld = ld; a.qT = (const bf16*)qT; a.u32 = u32; a.u_bf16_cols = (bf16*)u_cols; a.B = B; a.H = H; a.N = N; a.E = E;
+    return pevit_launch_lowrank_u(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_lowrank_grad(void* stream, const void* xn, int ldx, const float* u32, const void* dqkv, int ld,
                                      const float* t, float* partial, float* dbias_partial, int B, int H, int N, int E) {
-    return pevit_launch_lowrank_grad((const bf16*)xn, ldx, u32, (const bf16*)dqkv, ld, t, partial, dbias_partial,
-                                     pevit_lowrank_chunks(B * N), B, H, N, E, (hipStream_t)stream);
+    LowrankArgs a;      // (u32 is only read by this kernel)
+    a.xn = (const bf16*)xn; a.ldx = ldx; a.u32 = const_cast<float*>(u32); a.dqkv = (const bf16*)dqkv; a.ld = ld; a.t = t; a.partial = partial;
+    a.dbias_partial = dbias_partial; a.chunks = pevit_lowrank_chunks(B * N); a.B = B; a.H = H; a.N = N; a.E = E;
+    return pevit_launch_lowrank_grad(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_lowrank_chunks(int T) { return pevit_lowrank_chunks(T); }
 // ---- post-MLP adapter kernels (adapter.hip), one layer at a time
@@ -1646,18 +1746,25 @@ extern "C" int pevit_op_tn_chunks(int T) { return pevit_tn_chunks(T); }
 extern "C" int pevit_op_lna_blocks(int rows) { return pevit_lna_blocks(rows); }
 extern "C" int pevit_op_tn_gemm64(void* stream, const void* X, int ldx, const void* Y, int ldy, float* partial, float* csx,
                                   float* csy, int T, int E) {
-    return pevit_launch_tn_gemm64((const bf16*)X, ldx, (const bf16*)Y, ldy, partial, csx, csy, T, E, (hipStream_t)stream);
+    TnGemm64Args a;
+    a.X = (const bf16*)X; a.ldx = ldx; a.Y = (const bf16*)Y; a.ldy = ldy; a.partial = partial; a.csx = csx; a.csy = csy; a.T = T; a.E = E;
+    return pevit_launch_tn_gemm64(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_ln_bwd_affine(void* stream, const float* dy, const float* x, const float* mean, const float* rstd,
                                       const float* gamma, const float* dres, float* dx, void* dx_bf16, float* partial,
                                       int rows, int E) {
-    return pevit_launch_ln_bwd_affine(dy, x, mean, rstd, gamma, dres, dx, (bf16*)dx_bf16, partial, rows, E, (hipStream_t)stream);
+    LnBwdAffineArgs a;
+    a.dy = dy; a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dres = dres; a.dx = dx; a.dx_bf16 = (bf16*)dx_bf16; a.partial = partial;
+    a.rows = rows; a.E = E;
+    return pevit_launch_ln_bwd_affine(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_colsum_reduce(void* stream, const float* partial, int chunks, int n, float* out0, float* out1,
                                       float* out2) {
     if (out1 || out2) {
         if (!out1 || !out2) { pevit_set_error("colsum_reduce: give one output or three"); return -1; }
-        return pevit_launch_colsum_reduce3(partial, chunks, n, out0, out1, out2, 1, 0, 0, (hipStream_t)stream);
+        ColsumReduce3Args a;
+        a.partial = partial; a.chunks = chunks; a.n = n; a.o0 = out0; a.o1 = out1; a.o2 = out2; a.layers = 1;
+        return pevit_launch_colsum_reduce3(a, (hipStream_t)stream);
     }
     return pevit_launch_colsum_reduce(partial, chunks, n, out0, 1, 0, 0, (hipStream_t)stream);
 }
@@ -1666,7 +1773,11 @@ extern "C" int pevit_op_prep_bottleneck(void* stream, int method, const float* r
     BottleneckPanels pan{(bf16*)wd, (bf16*)wdT, (bf16*)wu, (bf16*)wuT};
     LayerStrides st{0, 0};
     if (method == PEVIT_ADAPTER) return pevit_launch_prep_adapter(p0, p1, pan, E, 1, st, (hipStream_t)stream);
-    if (method == PEVIT_COMPACTER) return pevit_launch_prep_compacter(rule, p0, p1, p2, p3, pan, E, 1, st, (hipStream_t)stream);
+    if (method == PEVIT_COMPACTER) {
+        PrepCompacterArgs a;
+        a.rule = rule; a.dWl = p0; a.dWr = p1; a.uWl = p2; a.uWr = p3; a.pan = pan; a.E = E; a.layers = 1; a.st = st;
+        return pevit_launch_prep_compacter(a, (hipStream_t)stream);
+    }
     pevit_set_error("prep_bottleneck: method %d is not a post-MLP adapter", method);
     return -1;
 }
@@ -1675,14 +1786,20 @@ extern "C" int pevit_op_chain_bottleneck(void* stream, int method, const float* 
                                          size_t off3) {
     if (method == PEVIT_ADAPTER)
         return pevit_launch_chain_adapter(Gd, Gu, grads + off0, grads + off1, E, 1, 0, 0, (hipStream_t)stream);
-    if (method == PEVIT_COMPACTER)
-        return pevit_launch_chain_compacter(Gd, Gu, rule, params, grads, E, 1, 0, 0, off0, off1, off2, off3, (hipStream_t)stream);
+    if (method == PEVIT_COMPACTER) {
+        ChainCompacterArgs a;
+        a.Gd = Gd; a.Gu = Gu; a.rule = rule; a.params = params; a.grads = grads; a.E = E; a.layers = 1;
+        a.off_dWl = off0; a.off_dWr = off1; a.off_uWl = off2; a.off_uWr = off3;
+        return pevit_launch_chain_compacter(a, (hipStream_t)stream);
+    }
     pevit_set_error("chain_bottleneck: method %d is not a post-MLP adapter", method);
     return -1;
 }
 extern "C" int pevit_op_im2col_u8(void* stream, const uint8_t* images, const float* mean3, const float* std3, void* patches_bf16, int B,
                                   int R, int P, int Kpad) {
-    return pevit_launch_im2col_u8(images, mean3, std3, (bf16*)patches_bf16, B, R, P, Kpad, (hipStream_t)stream);
+    Im2colU8Args a;
+    a.img = images; a.mean3 = mean3; a.std3 = std3; a.out = (bf16*)patches_bf16; a.B = B; a.R = R; a.P = P; a.Kp = Kpad;
+    return pevit_launch_im2col_u8(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_im2col(void* stream, const float* images, void* patches_bf16, int B, int R, int P, int Kpad) {
     return pevit_launch_im2col(images, (bf16*)patches_bf16, B, R, P, Kpad, (hipStream_t)stream);

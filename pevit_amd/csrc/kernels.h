@@ -1,4 +1,7 @@
 // Internal launcher interface between the C-ABI layer (capi.hip) and the kernel files.
+// Convention: a launcher with many operands takes ONE parameter struct (GemmParams, XxxArgs) plus the stream, filled by name at the
+// call site.  Every XxxArgs member is default-initialised and an unset member means "absent / off".  The f32 verification twins
+// (verify.hip, *_f32) take the SAME struct as their production sibling and reinterpret its bf16-declared members as f32 inside.
 #pragma once
 #include "common.h"
 
@@ -84,38 +87,61 @@ bool pevit_gemm_mixed_ok(const GemmParams& p, const GemmTune& t);   // does pevi
 
 // ---- norm.hip --------------------------------------------------------------------
 // y = LN(x) * gamma + beta over the last dim (eps 1e-5, f32 statistics: model.py:154-160)
-int pevit_launch_ln_fwd(const float* x, const float* gamma, const float* beta, int rows, int E,
-                        bf16* y_bf16, float* y_f32, float* mean, float* rstd, hipStream_t s,
-                        size_t xstride = 0, int f32 = 0, unsigned char* y_fp8 = nullptr);   // y_fp8: k-permuted e4m3 copy [rows][E]
+struct LnFwdArgs {
+    const float* x = nullptr; const float* gamma = nullptr; const float* beta = nullptr;
+    int rows = 0, E = 0;
+    bf16* y_bf16 = nullptr; float* y_f32 = nullptr; float* mean = nullptr; float* rstd = nullptr;
+    size_t xstride = 0;                 // elements between the rows of x (0: E)
+    int f32 = 0;
+    unsigned char* y_fp8 = nullptr;     // k-permuted e4m3 copy [rows][E]
+};
+int pevit_launch_ln_fwd(const LnFwdArgs& a, hipStream_t s);
 // dx_out = dres + LN-backward(dy)   (gamma/beta frozen: no parameter grads).  dy is f32, or (dy_stored) in the activation
 // storage type -- bf16 in production -- when it is the output of a dX GEMM
-int pevit_launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd,
-                        const float* gamma, const float* dres, float* dx_out, bf16* dx_bf16, int rows, int E,
-                        hipStream_t s, size_t xstride = 0, const float* bf16_colscale = nullptr, int f32 = 0, int dy_stored = 0,
-                        int res_period = 0,       // res_period > 0: dres is read on rows that are multiples of it only (zero elsewhere)
-                        int res16 = 0,            // dres points at bf16 values (may be dx_bf16 itself: in place); dx_out may then be null
-                        const float* res_colscale = nullptr);   // res16 + fp8 weights: the power-of-two column scales folded into dres (taken out exactly)
+struct LnBwdArgs {
+    const void* dy = nullptr; const float* x = nullptr; const float* mean = nullptr; const float* rstd = nullptr;
+    const float* gamma = nullptr; const float* dres = nullptr; float* dx_out = nullptr; bf16* dx_bf16 = nullptr;
+    int rows = 0, E = 0;
+    size_t xstride = 0;                        // elements between the rows of x and of the gradients (0: E)
+    const float* bf16_colscale = nullptr;      // fp8 weights: per-column (power-of-two) factors folded into the bf16 output
+    int f32 = 0, dy_stored = 0;
+    int res_period = 0;                        // > 0: dres is read on rows that are multiples of it only (zero elsewhere)
+    int res16 = 0;                             // dres points at bf16 values (may be dx_bf16 itself: in place); dx_out may then be null
+    const float* res_colscale = nullptr;       // res16 + fp8 weights: the power-of-two column scales folded into dres (taken out exactly)
+};
+int pevit_launch_ln_bwd(const LnBwdArgs& a, hipStream_t s);
 
-// ---- attention.hip ---------------------------------------------------------------
+// ---- attention.hip / attn_probs.hip ----------------------------------------------
 // q,k,v: (B*H, N, 64) bf16 (q pre-scaled by 1/8, deltas already added); out: rows (b*N+n), cols h*64+d
-int pevit_launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, bf16* out, int ldo,
-                          float* lse, int B, int H, int N, hipStream_t s, unsigned char* out_fp8 = nullptr);   // + e4m3 copy, row pitch ldo codes
-// dqkv: row layout [T][ld]: cols [0,E) dq, [E,2E) dk, [2E,3E) dv
-int pevit_launch_attn_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* out, int ldo,
-                          const bf16* dout, int lddo, const float* lse, bf16* dqkv, int ld,
-                          int B, int H, int N, hipStream_t s, int dout_cls_only = 0);   // dout_cls_only (N <= 64): dout is zero except on token 0 of every image; the other rows are not read
-
-// ---- attn_probs.hip ---------------------------------------------------------------
-// softmax probabilities P = exp(q k^T - lse) of the attention core (q, k: (B*H, N, 64) bf16 as attn_fwd takes them, lse as it
-// wrote it): average = 1 -> out (B, N, N) f32 = mean over the H heads; 0 -> out (B, H, N, N) f32
-int pevit_launch_attn_probs(const bf16* q, const bf16* k, const float* lse, float* out, int B, int H, int N, int average, hipStream_t s);
+struct AttnArgs {
+    const bf16* q = nullptr; const bf16* k = nullptr; const bf16* v = nullptr;
+    bf16* out = nullptr; int ldo = 0;       // written by attn_fwd, read by attn_bwd
+    float* lse = nullptr;                   // written by attn_fwd, read by attn_bwd and attn_probs
+    int B = 0, H = 0, N = 0;
+    unsigned char* out_fp8 = nullptr;       // attn_fwd: + e4m3 copy of out, row pitch ldo codes
+    // attn_bwd.  dqkv: row layout [T][ld]: cols [0,E) dq, [E,2E) dk, [2E,3E) dv
+    const bf16* dout = nullptr; int lddo = 0;
+    bf16* dqkv = nullptr; int ld = 0;
+    int dout_cls_only = 0;                  // (N <= 64): dout is zero except on token 0 of every image; the other rows are not read
+    // attn_probs: softmax probabilities P = exp(q k^T - lse) of the attention core (q, k as attn_fwd takes them, lse as it wrote
+    // it): average = 1 -> probs (B, N, N) f32 = mean over the H heads; 0 -> probs (B, H, N, N) f32
+    float* probs = nullptr; int average = 0;
+};
+int pevit_launch_attn_fwd(const AttnArgs& a, hipStream_t s);
+int pevit_launch_attn_bwd(const AttnArgs& a, hipStream_t s);
+int pevit_launch_attn_probs(const AttnArgs& a, hipStream_t s);
 
 // ---- attn_delta.hip (attention-site adapters fused with the attention core, N <= 64) --------------
 // heads per workgroup of the fused forms for this geometry, or 0 when there is none (the two-kernel path is used)
 int pevit_attn_delta_hpw(int B, int H, int N);
 // delta_add + attn_fwd in one launch: q, v (head layout) are rewritten with q + delta, v + delta (saved for backward)
-int pevit_launch_attn_fwd_delta(bf16* q, const bf16* k, bf16* v, const float* t, const bf16* q16, const float* bias,
-                                float ascale, bf16* out, int ldo, float* lse, int B, int H, int N, hipStream_t s);
+struct AttnFwdDeltaArgs {
+    bf16* q = nullptr; const bf16* k = nullptr; bf16* v = nullptr;
+    const float* t = nullptr; const bf16* q16 = nullptr; const float* bias = nullptr; float ascale = 0.f;
+    bf16* out = nullptr; int ldo = 0; float* lse = nullptr;
+    int B = 0, H = 0, N = 0;
+};
+int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s);
 
 void pevit_attn_delta_set_timeline(void* buf);      // measurement only: 8 s_memtime stamps per workgroup of the next fused launches (null = off)
 
@@ -131,38 +157,68 @@ struct AdapterPanels {      // per layer, rewritten every step from the f32 mast
 };
 struct LayerStrides { size_t arena_bytes; size_t param_floats; };   // per-layer pointer advance
 // KAdaptation: P[:,j] = s_j (x) l_j , Q[:,j] = t_j (x) r_j   (model.py:567-580); all layers
-int pevit_launch_prep_kadapt(const float* rule1_l, const float* rule1_r, const float* rule2_l,
-                             const float* rule2_r, const float* q_left, const float* q_right,
-                             AdapterPanels pan, int E, float ascale, int layers, LayerStrides st, hipStream_t s, int f32 = 0);
+struct PrepKadaptArgs {
+    const float* rule1_l = nullptr; const float* rule1_r = nullptr; const float* rule2_l = nullptr; const float* rule2_r = nullptr;
+    const float* q_left = nullptr; const float* q_right = nullptr;
+    AdapterPanels pan{}; int E = 0; float ascale = 0.f; int layers = 0; LayerStrides st{}; int f32 = 0;
+};
+int pevit_launch_prep_kadapt(const PrepKadaptArgs& a, hipStream_t s);
 // LoRA: P_q = A1q^T, Q_q = A2q (rank r zero-padded to 32)   (lora_model.py:490-514); all layers
-int pevit_launch_prep_lora(const float* a1q, const float* a2q, const float* a1v, const float* a2v,
-                           int r, AdapterPanels pan, int E, float ascale, int layers, LayerStrides st, hipStream_t s, int f32 = 0);
+struct PrepLoraArgs {
+    const float* a1q = nullptr; const float* a2q = nullptr; const float* a1v = nullptr; const float* a2v = nullptr; int r = 0;
+    AdapterPanels pan{}; int E = 0; float ascale = 0.f; int layers = 0; LayerStrides st{}; int f32 = 0;
+};
+int pevit_launch_prep_lora(const PrepLoraArgs& a, hipStream_t s);
 // q_buf_flat[rr*E+e] += ascale * t[row(rr)][0:32] . Q_q[e] + bias[e]   (and v with cols 32:64)
 // rr is the reference's (n*B+b) row index of the raw reshape (model.py:796-799); row(rr)=b*N+n.
-// q16: the bf16 panel [E][64] of Q (production operand); q32: the f32 panel (f32 verification mode)
-int pevit_launch_delta_add(bf16* qbuf, bf16* vbuf, const float* t, const float* q32, const bf16* q16,
-                           const float* bias, float ascale, int B, int N, int E, hipStream_t s, int f32 = 0);
-// u[row(rr)][0:32] = dDelta_q[rr] . Q_q ; [32:64] = dDelta_v[rr] . Q_v ; written f32 (u32) and
-// bf16 into dqkv[:, 3E:3E+64]
-int pevit_launch_lowrank_u(const bf16* dqkv, int ld, const bf16* qT, float* u32, bf16* u_bf16_cols,
-                           int B, int H, int N, int E, hipStream_t s);
-// partial[chunk][4][E][32]: dP_q, dP_v (= xn^T u), dQ_q, dQ_v (= dDelta^T t_ref); dbias partial[chunk][E]
-int pevit_launch_lowrank_grad(const bf16* xn, int ldx, const float* u32, const bf16* dqkv, int ld,
-                              const float* t, float* partial, float* dbias_partial, int chunks,
-                              int B, int H, int N, int E, hipStream_t s, int xcd_order = 1);   // xcd_order: XCD-contiguous workgroup order (measurement knob)
+struct DeltaAddArgs {
+    bf16* qbuf = nullptr; bf16* vbuf = nullptr; const float* t = nullptr;
+    const float* q32 = nullptr;     // the f32 panel [E][64] of Q (f32 verification mode)
+    const bf16* q16 = nullptr;      // the bf16 panel [E][64] of Q (production operand)
+    const float* bias = nullptr; float ascale = 0.f;
+    int B = 0, N = 0, E = 0, f32 = 0;
+};
+int pevit_launch_delta_add(const DeltaAddArgs& a, hipStream_t s);
+// The backward kernels of the attention-site adapters share their operands:
+//   lowrank_u:     u[row(rr)][0:32] = dDelta_q[rr] . Q_q ; [32:64] = dDelta_v[rr] . Q_v ; written f32 (u32) and bf16 into
+//                  u_bf16_cols = dqkv[:, 3E:3E+64]
+//   lowrank_grad:  partial[chunk][4][E][32]: dP_q, dP_v (= xn^T u), dQ_q, dQ_v (= dDelta^T t_ref); dbias_partial[chunk][E]
+//   lowrank_combo: u + dQ / d bias of this layer and the deferred dP of the previously processed layer in ONE launch
+//                  (lowrank_combo_kernel)
+struct LowrankArgs {
+    const bf16* dqkv = nullptr; int ld = 0;
+    const bf16* qT = nullptr;               // [64][E] panel of Q^T (production)
+    const float* q32 = nullptr;             // [E][64] f32 panel of Q (lowrank_u_f32 only)
+    float* u32 = nullptr; bf16* u_bf16_cols = nullptr;
+    const bf16* xn = nullptr; int ldx = 0;  // lowrank_grad: LayerNorm output of this layer ; ldx also the pitch of xn_prev
+    const float* t = nullptr;
+    float* partial = nullptr; float* dbias_partial = nullptr;
+    int chunks = 0;                         // lowrank_grad: pevit_lowrank_chunks(B * N)
+    int B = 0, H = 0, N = 0, E = 0;
+    int xcd_order = 1;                      // lowrank_grad: XCD-contiguous workgroup order (measurement knob; on unless cleared)
+    // lowrank_combo.  this_layer = 0: only the deferred dP of the previous layer (end of the layer loop); prev = 0: no deferred work
+    int this_layer = 0, prev = 0;
+    const bf16* xn_prev = nullptr; const float* u32_prev = nullptr; float* partial_prev = nullptr;
+};
+int pevit_launch_lowrank_u(const LowrankArgs& a, hipStream_t s);
+int pevit_launch_lowrank_grad(const LowrankArgs& a, hipStream_t s);
 int pevit_lowrank_chunks(int T);
-// u + dQ / d bias of this layer and the deferred dP of the previously processed layer in ONE launch (lowrank_combo_kernel)
-int pevit_launch_lowrank_combo(int this_layer, int prev, const bf16* dqkv, int ld, const bf16* qT, float* u32, bf16* ucols, const float* t,
-                               float* partial, float* dbias_partial, const bf16* xn_prev, int ldx, const float* u32_prev,
-                               float* partial_prev, int B, int H, int N, int E, hipStream_t s);
+int pevit_launch_lowrank_combo(const LowrankArgs& a, hipStream_t s);
 // reduce the per-chunk partials of all layers and apply the chain rule onto the reference's
 // parameter tensors (flat gradient buffer, accumulating)
-int pevit_launch_chain_kadapt(const float* partial, size_t partial_layer, const float* dbias_partial, size_t dbias_layer,
-                              int chunks, float ascale, int layers, float* G, float* rule_scratch, const float* params,
-                              float* grads, size_t p_layer0, size_t p_layer_stride, int E, hipStream_t s);
+struct ChainKadaptArgs {
+    const float* partial = nullptr; size_t partial_layer = 0; const float* dbias_partial = nullptr; size_t dbias_layer = 0;
+    int chunks = 0; float ascale = 0.f; int layers = 0;
+    float* G = nullptr; float* rule_scratch = nullptr; const float* params = nullptr; float* grads = nullptr;
+    size_t p_layer0 = 0, p_layer_stride = 0; int E = 0;
+};
+int pevit_launch_chain_kadapt(const ChainKadaptArgs& a, hipStream_t s);
 int pevit_launch_rule_sum(const float* rule_scratch, float* grads, int l_lo, int l_hi, hipStream_t s);
-int pevit_launch_chain_lora(const float* partial, size_t partial_layer, int chunks, float ascale, int r, int layers,
-                            float* G, float* grads, size_t p_layer0, size_t p_layer_stride, int E, hipStream_t s);
+struct ChainLoraArgs {
+    const float* partial = nullptr; size_t partial_layer = 0; int chunks = 0; float ascale = 0.f; int r = 0, layers = 0;
+    float* G = nullptr; float* grads = nullptr; size_t p_layer0 = 0, p_layer_stride = 0; int E = 0;
+};
+int pevit_launch_chain_lora(const ChainLoraArgs& a, hipStream_t s);
 
 // ---- misc.hip --------------------------------------------------------------------
 int pevit_launch_cast_bf16(const float* src, bf16* dst, size_t n, float scale, hipStream_t s, int f32 = 0);
@@ -173,10 +229,15 @@ int pevit_launch_permute_rows(const float* src, float* dst, int N, int B, int E,
                               hipStream_t s);
 int pevit_launch_scale_f32(float* p, size_t n, float scale, hipStream_t s);
 int pevit_launch_zero(void* ptr, size_t bytes, hipStream_t s);      // the step's memsets as a kernel (capturable in order into a HIP graph)
-int pevit_launch_sgd(float* p, const float* g, float* mom, const unsigned char* has_grad, size_t n,
-                     float lr, float momentum, float wd, int first_step, float grad_scale, hipStream_t s,
-                     const unsigned* poison = nullptr,    // device word: non-zero = skip the update (stream-K hand-off error)
-                     unsigned* skipped = nullptr, const unsigned* poison2 = nullptr, float* loss_slot = nullptr);        // device counter of the updates skipped that way
+struct SgdArgs {
+    float* p = nullptr; const float* g = nullptr; float* mom = nullptr; const unsigned char* has_grad = nullptr; size_t n = 0;
+    float lr = 0.f, momentum = 0.f, wd = 0.f; int first_step = 0; float grad_scale = 0.f;
+    const unsigned* poison = nullptr;     // device word: non-zero = skip the update (stream-K hand-off error)
+    unsigned* skipped = nullptr;          // device counter of the updates skipped that way
+    const unsigned* poison2 = nullptr;    // a second such word (the data-parallel exchange's)
+    float* loss_slot = nullptr;           // where the step's loss sits: NaN goes there when the update is withheld
+};
+int pevit_launch_sgd(const SgdArgs& a, hipStream_t s);
 
 int pevit_launch_occupy(int blocks, int lds_bytes, double micros, hipStream_t s);   // measurement only (pevit_debug_occupy)
 
@@ -190,68 +251,105 @@ int pevit_launch_cast_fp8(const float* src, unsigned char* dst, size_t rows, int
 int pevit_launch_dequant_rows_fp8(const unsigned char* codes, int ldc, const float* scale, int rows, int cols, float* out,
                                   hipStream_t s);
 
-// ---- verify.hip (f32-class verification mode: plain f32 kernels for the matrix-core contractions) -----------------
-int pevit_launch_gemm_f32(int epi, const GemmParams& p, hipStream_t s);      // A, B and the bf16-declared buffers hold f32
-int pevit_launch_attn_fwd_f32(const float* q, const float* k, const float* v, float* out, int ldo, float* lse, int B, int H, int N,
-                              hipStream_t s);
-int pevit_launch_attn_bwd_f32(const float* q, const float* k, const float* v, const float* out, int ldo, const float* dout,
-                              int lddo, const float* lse, float* dqkv, int ld, int B, int H, int N, hipStream_t s);
-int pevit_launch_attn_probs_f32(const float* q, const float* k, const float* lse, float* out, int B, int H, int N, int average,
-                                hipStream_t s);
-int pevit_launch_lowrank_u_f32(const float* dqkv, int ld, const float* q32, float* u32, float* ucols, int B, int H, int N, int E,
-                               hipStream_t s);
-// G[e][j] = sum_r X[r][e] Y[r][j], partial / column-sum layout of tn_gemm64 (adapter.hip)
-int pevit_launch_tn_gemm64_f32(const float* X, int ldx, const float* Y, int ldy, float* partial, float* csx, float* csy, int T, int E,
-                               hipStream_t s);
-int pevit_launch_lowrank_grad_f32(const float* xn, int ldx, const float* u32, const float* dqkv, int ld, const float* t,
-                                  float* partial, float* dbias_partial, int chunks, int B, int H, int N, int E, hipStream_t s);
-
-// ---- stem_head.hip -----------------------------------------------------------------
-int pevit_launch_im2col(const float* img, bf16* out, int B, int R, int P, int Kp, hipStream_t s, int f32 = 0);
-// uint8 pixels with ToTensor + Normalize folded in: x = (u8 / 255 - mean[c]) / std[c] (feature.py:537-542)
-int pevit_launch_im2col_u8(const unsigned char* img, const float* mean3, const float* std3, bf16* out, int B, int R, int P, int Kp,
-                           hipStream_t s, int f32 = 0);
-int pevit_launch_conv_weight(const float* w, bf16* out, int E, int K, int Kp, hipStream_t s, int f32 = 0);
-int pevit_launch_cls_row(const float* cls, const float* pos, float* x, int B, int N, int E, hipStream_t s);
-// labels (B) int64 -> cross-entropy; targets (B x C) f32 -> BCE with logits; both null -> forward only
-int pevit_launch_head(const float* feat, const int64_t* labels, const float* targets, const float* W, const float* bias, float* gW,
-                      float* gb, float* running_mean, float* running_var, int training, float* ybn, float* rstd, float* logits,
-                      float* dlogits, float* dybn, float* loss, float* dfeat, int B, int D, int Cc, hipStream_t s, bf16* dfeat_bf16 = nullptr);   // dfeat_bf16: bf16 copy of dfeat written by the BatchNorm backward (no cast launch)
-
 // ---- adapter.hip (post-MLP bottleneck adapters: Adapter, Compacter) -------------------------------
 struct BottleneckPanels { bf16* wd; bf16* wdT; bf16* wu; bf16* wuT; };   // [64][E], [E][64], [E][64], [64][E]
 int pevit_tn_chunks(int T);
 int pevit_lna_blocks(int rows);
 int pevit_launch_prep_adapter(const float* w_down, const float* w_up, BottleneckPanels pan, int E, int layers, LayerStrides st,
                               hipStream_t s, int f32 = 0);
-int pevit_launch_prep_compacter(const float* rule, const float* dWl, const float* dWr, const float* uWl, const float* uWr,
-                                BottleneckPanels pan, int E, int layers, LayerStrides st, hipStream_t s, int f32 = 0);
+struct PrepCompacterArgs {
+    const float* rule = nullptr; const float* dWl = nullptr; const float* dWr = nullptr; const float* uWl = nullptr;
+    const float* uWr = nullptr;
+    BottleneckPanels pan{}; int E = 0, layers = 0; LayerStrides st{}; int f32 = 0;
+};
+int pevit_launch_prep_compacter(const PrepCompacterArgs& a, hipStream_t s);
 // G[e][j] = sum_r X[r][e] Y[r][j] (per-chunk partials [chunk][E][64]); optional column sums of X / Y
-int pevit_launch_tn_gemm64(const bf16* X, int ldx, const bf16* Y, int ldy, float* partial, float* csx, float* csy, int T, int E,
-                           hipStream_t s);
-int pevit_launch_ln_bwd_affine(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                               const float* dres, float* dx, bf16* dx_bf16, float* partial, int rows, int E, hipStream_t s, int f32 = 0);
+struct TnGemm64Args {
+    const bf16* X = nullptr; int ldx = 0; const bf16* Y = nullptr; int ldy = 0;
+    float* partial = nullptr; float* csx = nullptr; float* csy = nullptr; int T = 0, E = 0;
+};
+int pevit_launch_tn_gemm64(const TnGemm64Args& a, hipStream_t s);
+struct LnBwdAffineArgs {
+    const float* dy = nullptr; const float* x = nullptr; const float* mean = nullptr; const float* rstd = nullptr;
+    const float* gamma = nullptr; const float* dres = nullptr; float* dx = nullptr; bf16* dx_bf16 = nullptr;
+    float* partial = nullptr; int rows = 0, E = 0, f32 = 0;
+};
+int pevit_launch_ln_bwd_affine(const LnBwdAffineArgs& a, hipStream_t s);
 // ---- adapter_fused.hip: the post-MLP adapter as one launch per direction (bf16 storage, E a multiple of 256) ----
 bool pevit_adapter_fused_ok(int E);
 int pevit_num_cus();                 // compute units of the current device (cached)
 int pevit_adapter_blocks(int T);     // workgroups (= blocks of LayerNorm-affine partials) of the fused backward
 // act_kind 0 = ReLU (Adapter), 1 = gelu_new (Compacter).  hraw = c_proj accumulators WITHOUT their bias (f32), bpr = that bias.
-int pevit_launch_adapter_fwd(int act_kind, const float* hraw, const float* bpr, const float* x_mid, const float* gamma, const float* beta,
-                             const bf16* wd, const float* b_down, const bf16* wu, const float* b_up, bf16* z, float* mean_a,
-                             float* rstd_a, bf16* act, bf16* apre, float* x_out, int T, int E, hipStream_t s);
+struct AdapterFwdArgs {
+    int act_kind = 0;
+    const float* hraw = nullptr; const float* bpr = nullptr; const float* x_mid = nullptr; const float* gamma = nullptr;
+    const float* beta = nullptr; const bf16* wd = nullptr; const float* b_down = nullptr; const bf16* wu = nullptr;
+    const float* b_up = nullptr;
+    bf16* z = nullptr; float* mean_a = nullptr; float* rstd_a = nullptr; bf16* act = nullptr; bf16* apre = nullptr;
+    float* x_out = nullptr; int T = 0, E = 0;
+};
+int pevit_launch_adapter_fwd(const AdapterFwdArgs& a, hipStream_t s);
 // saved = act (ReLU) / apre (gelu_new); partial: [pevit_lna_blocks(T)][3][E] like ln_bwd_affine
-int pevit_launch_adapter_bwd(int act_kind, const bf16* dyb, const float* dres, const bf16* wuT, const bf16* saved, const bf16* wdT,
-                             const float* hraw, const float* bpr, const float* mean_a, const float* rstd_a, const float* gamma,
-                             bf16* dpre, bf16* dh_bf16, float* partial, int T, int E, hipStream_t s, const bf16* tn_x1 = nullptr,
-                             const bf16* tn_y1 = nullptr, float* tn_partial1 = nullptr, const bf16* tn_x2 = nullptr,
-                             const bf16* tn_y2 = nullptr, float* tn_partial2 = nullptr, float* tn_csy2 = nullptr,
-                             int tn_blocks = 0);      // workgroups of the contraction range, 0 = one per unit pair
+struct AdapterBwdArgs {
+    int act_kind = 0;
+    const bf16* dyb = nullptr;
+    const float* dres = nullptr;        // null: the bf16 gradient stream -- dx_out is read from dyb wherever the f32 copy was
+    const bf16* wuT = nullptr; const bf16* saved = nullptr; const bf16* wdT = nullptr;
+    const float* hraw = nullptr; const float* bpr = nullptr; const float* mean_a = nullptr; const float* rstd_a = nullptr;
+    const float* gamma = nullptr;
+    bf16* dpre = nullptr; bf16* dh_bf16 = nullptr; float* partial = nullptr; int T = 0, E = 0;
+    // tn_*: the contraction range of the launch (adapter_fused.hip af_tn_range); tn_x1 / tn_x2 unset leave a product out.
+    //   product 1: tn_partial1[chunk][E][64] = sum over the chunk's rows of x1[r][e] y1[r][j]   (x1: [T][E] bf16, y1: [T][64] bf16)
+    //   product 2: the same for x2, y2 -> tn_partial2, and tn_csy2[chunk][64] = column sums of y2
+    const bf16* tn_x1 = nullptr; const bf16* tn_y1 = nullptr; float* tn_partial1 = nullptr;
+    const bf16* tn_x2 = nullptr; const bf16* tn_y2 = nullptr; float* tn_partial2 = nullptr; float* tn_csy2 = nullptr;
+    int tn_blocks = 0;                  // workgroups of the contraction range, 0 = one per unit pair
+};
+int pevit_launch_adapter_bwd(const AdapterBwdArgs& a, hipStream_t s);
 int pevit_launch_colsum_reduce(const float* partial, int chunks, int n, float* out, int layers, size_t partial_layer,
                                size_t out_layer, hipStream_t s);
-int pevit_launch_colsum_reduce3(const float* partial, int chunks, int n, float* o0, float* o1, float* o2, int layers,
-                                size_t partial_layer, size_t out_layer, hipStream_t s);
+struct ColsumReduce3Args {
+    const float* partial = nullptr; int chunks = 0, n = 0; float* o0 = nullptr; float* o1 = nullptr; float* o2 = nullptr;
+    int layers = 0; size_t partial_layer = 0, out_layer = 0;
+};
+int pevit_launch_colsum_reduce3(const ColsumReduce3Args& a, hipStream_t s);
 int pevit_launch_chain_adapter(const float* Gd, const float* Gu, float* g_down, float* g_up, int E, int layers, size_t g_layer,
                                size_t param_layer, hipStream_t s);
-int pevit_launch_chain_compacter(const float* Gd, const float* Gu, const float* rule, const float* params, float* grads, int E,
-                                 int layers, size_t g_layer, size_t param_layer, size_t off_dWl, size_t off_dWr, size_t off_uWl,
-                                 size_t off_uWr, hipStream_t s);
+struct ChainCompacterArgs {
+    const float* Gd = nullptr; const float* Gu = nullptr; const float* rule = nullptr; const float* params = nullptr;
+    float* grads = nullptr; int E = 0, layers = 0; size_t g_layer = 0, param_layer = 0;
+    size_t off_dWl = 0, off_dWr = 0, off_uWl = 0, off_uWr = 0;
+};
+int pevit_launch_chain_compacter(const ChainCompacterArgs& a, hipStream_t s);
+
+// ---- verify.hip (f32-class verification mode: plain f32 kernels for the matrix-core contractions) -----------------
+// Each twin takes its production sibling's struct; the members declared bf16 (and lowrank_grad's xn) hold f32 there.
+int pevit_launch_gemm_f32(int epi, const GemmParams& p, hipStream_t s);      // A, B and the bf16-declared buffers hold f32
+int pevit_launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s);             // (out_fp8 is not written)
+int pevit_launch_attn_bwd_f32(const AttnArgs& a, hipStream_t s);             // (every row of dout is read: dout_cls_only has no effect)
+int pevit_launch_attn_probs_f32(const AttnArgs& a, hipStream_t s);
+int pevit_launch_lowrank_u_f32(const LowrankArgs& a, hipStream_t s);         // reads the f32 panel q32, not qT
+// G[e][j] = sum_r X[r][e] Y[r][j], partial / column-sum layout of tn_gemm64 (adapter.hip)
+int pevit_launch_tn_gemm64_f32(const TnGemm64Args& a, hipStream_t s);
+int pevit_launch_lowrank_grad_f32(const LowrankArgs& a, hipStream_t s);      // (no workgroup-order knob)
+
+// ---- stem_head.hip -----------------------------------------------------------------
+int pevit_launch_im2col(const float* img, bf16* out, int B, int R, int P, int Kp, hipStream_t s, int f32 = 0);
+// uint8 pixels with ToTensor + Normalize folded in: x = (u8 / 255 - mean[c]) / std[c] (feature.py:537-542)
+struct Im2colU8Args {
+    const unsigned char* img = nullptr; const float* mean3 = nullptr; const float* std3 = nullptr; bf16* out = nullptr;
+    int B = 0, R = 0, P = 0, Kp = 0, f32 = 0;
+};
+int pevit_launch_im2col_u8(const Im2colU8Args& a, hipStream_t s);
+int pevit_launch_conv_weight(const float* w, bf16* out, int E, int K, int Kp, hipStream_t s, int f32 = 0);
+int pevit_launch_cls_row(const float* cls, const float* pos, float* x, int B, int N, int E, hipStream_t s);
+// labels (B) int64 -> cross-entropy; targets (B x C) f32 -> BCE with logits; both null -> forward only
+struct HeadArgs {
+    const float* feat = nullptr; const int64_t* labels = nullptr; const float* targets = nullptr;
+    const float* W = nullptr; const float* bias = nullptr; float* gW = nullptr; float* gb = nullptr;
+    float* running_mean = nullptr; float* running_var = nullptr; int training = 0;
+    float* ybn = nullptr; float* rstd = nullptr; float* logits = nullptr; float* dlogits = nullptr; float* dybn = nullptr;
+    float* loss = nullptr; float* dfeat = nullptr; int B = 0, D = 0, Cc = 0;
+    bf16* dfeat_bf16 = nullptr;     // bf16 copy of dfeat written by the BatchNorm backward (no cast launch)
+};
+int pevit_launch_head(const HeadArgs& a, hipStream_t s);

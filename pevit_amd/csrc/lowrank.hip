@@ -706,47 +706,44 @@ __global__ void chain_lora_kernel(const float* __restrict__ G, float ascale, int
 
 }  // namespace
 
-int pevit_launch_prep_kadapt(const float* rule1_l, const float* rule1_r, const float* rule2_l, const float* rule2_r,
-                             const float* q_left, const float* q_right, AdapterPanels pan, int E, float ascale,
-                             int layers, LayerStrides st, hipStream_t s, int f32) {
+int pevit_launch_prep_kadapt(const PrepKadaptArgs& a, hipStream_t s) {
+    const int E = a.E;
     if (E % 32) { pevit_set_error("prep_kadapt: width %d not divisible by phm_dim 32", E); return -1; }
-    if (f32) hipLaunchKernelGGL(prep_kadapt_kernel<float>, dim3(ceil_div(E * 32, 256), layers, 2), dim3(256), 0, s, rule1_l, rule1_r,
-                                rule2_l, rule2_r, q_left, q_right, pan, E, ascale, st);
-    else hipLaunchKernelGGL(prep_kadapt_kernel<bf16>, dim3(ceil_div(E * 32, 256), layers, 2), dim3(256), 0, s, rule1_l, rule1_r,
-                            rule2_l, rule2_r, q_left, q_right, pan, E, ascale, st);
+    if (a.f32) hipLaunchKernelGGL(prep_kadapt_kernel<float>, dim3(ceil_div(E * 32, 256), a.layers, 2), dim3(256), 0, s, a.rule1_l, a.rule1_r,
+                                  a.rule2_l, a.rule2_r, a.q_left, a.q_right, a.pan, E, a.ascale, a.st);
+    else hipLaunchKernelGGL(prep_kadapt_kernel<bf16>, dim3(ceil_div(E * 32, 256), a.layers, 2), dim3(256), 0, s, a.rule1_l, a.rule1_r,
+                            a.rule2_l, a.rule2_r, a.q_left, a.q_right, a.pan, E, a.ascale, a.st);
     LAUNCH_OK("prep_kadapt_kernel");
     return 0;
 }
 
-int pevit_launch_prep_lora(const float* a1q, const float* a2q, const float* a1v, const float* a2v, int r,
-                           AdapterPanels pan, int E, float ascale, int layers, LayerStrides st, hipStream_t s, int f32) {
-    if (r < 1 || r > 32) { pevit_set_error("prep_lora: rank %d outside [1,32]", r); return -1; }
-    if (f32) hipLaunchKernelGGL(prep_lora_kernel<float>, dim3(ceil_div(E * 32, 256), layers), dim3(256), 0, s, a1q, a2q, a1v, a2v, r,
-                                pan, E, ascale, st);
-    else hipLaunchKernelGGL(prep_lora_kernel<bf16>, dim3(ceil_div(E * 32, 256), layers), dim3(256), 0, s, a1q, a2q, a1v, a2v, r,
-                            pan, E, ascale, st);
+int pevit_launch_prep_lora(const PrepLoraArgs& a, hipStream_t s) {
+    if (a.r < 1 || a.r > 32) { pevit_set_error("prep_lora: rank %d outside [1,32]", a.r); return -1; }
+    if (a.f32) hipLaunchKernelGGL(prep_lora_kernel<float>, dim3(ceil_div(a.E * 32, 256), a.layers), dim3(256), 0, s, a.a1q, a.a2q, a.a1v, a.a2v, a.r,
+                                  a.pan, a.E, a.ascale, a.st);
+    else hipLaunchKernelGGL(prep_lora_kernel<bf16>, dim3(ceil_div(a.E * 32, 256), a.layers), dim3(256), 0, s, a.a1q, a.a2q, a.a1v, a.a2v, a.r,
+                            a.pan, a.E, a.ascale, a.st);
     LAUNCH_OK("prep_lora_kernel");
     return 0;
 }
 
-int pevit_launch_delta_add(bf16* qbuf, bf16* vbuf, const float* t, const float* q32, const bf16* q16, const float* bias, float ascale,
-                           int B, int N, int E, hipStream_t s, int f32) {
+int pevit_launch_delta_add(const DeltaAddArgs& a, hipStream_t s) {
+    const int B = a.B, N = a.N, E = a.E;
     if (E % DA_COLS) { pevit_set_error("delta_add: width %d must be a multiple of %d", E, DA_COLS); return -1; }
     const int T = B * N;
     const int waves = ceil_div(T, 16 * DA_RG) * (E / DA_COLS);
-    if (f32) hipLaunchKernelGGL(delta_add_kernel<float>, dim3(ceil_div(waves, 4), 2), dim3(256), 0, s, qbuf, vbuf, t, q32, q16, bias, ascale,
-                                B, N, E);
-    else hipLaunchKernelGGL(delta_add_kernel<bf16>, dim3(ceil_div(waves, 4), 2), dim3(256), 0, s, qbuf, vbuf, t, q32, q16, bias, ascale,
-                            B, N, E);
+    if (a.f32) hipLaunchKernelGGL(delta_add_kernel<float>, dim3(ceil_div(waves, 4), 2), dim3(256), 0, s, a.qbuf, a.vbuf, a.t, a.q32, a.q16, a.bias,
+                                  a.ascale, B, N, E);
+    else hipLaunchKernelGGL(delta_add_kernel<bf16>, dim3(ceil_div(waves, 4), 2), dim3(256), 0, s, a.qbuf, a.vbuf, a.t, a.q32, a.q16, a.bias,
+                            a.ascale, B, N, E);
     LAUNCH_OK("delta_add_kernel");
     return 0;
 }
 
-int pevit_launch_lowrank_u(const bf16* dqkv, int ld, const bf16* qT, float* u32, bf16* u_bf16_cols, int B, int H,
-                           int N, int E, hipStream_t s) {
-    const int T = B * N;
-    hipLaunchKernelGGL(lowrank_u_kernel, dim3(ceil_div(T, 16 * LU_RG)), dim3(64 * LU_WAVES), 0, s, dqkv, ld, qT, u32, u_bf16_cols, B, H,
-                       N, E);
+int pevit_launch_lowrank_u(const LowrankArgs& a, hipStream_t s) {
+    const int T = a.B * a.N;
+    hipLaunchKernelGGL(lowrank_u_kernel, dim3(ceil_div(T, 16 * LU_RG)), dim3(64 * LU_WAVES), 0, s, a.dqkv, a.ld, a.qT, a.u32, a.u_bf16_cols,
+                       a.B, a.H, a.N, a.E);
     LAUNCH_OK("lowrank_u_kernel");
     return 0;
 }
@@ -772,9 +769,8 @@ static int lg_pick_es(int E, int chunks, int kinds, int other_blocks) {
 }
 
 // see lowrank_combo_kernel.  this_layer = 0: only the deferred dP of the previous layer (end of the layer loop); prev = 0: no deferred work.
-int pevit_launch_lowrank_combo(int this_layer, int prev, const bf16* dqkv, int ld, const bf16* qT, float* u32, bf16* ucols, const float* t,
-                               float* partial, float* dbias_partial, const bf16* xn_prev, int ldx, const float* u32_prev,
-                               float* partial_prev, int B, int H, int N, int E, hipStream_t s) {
+int pevit_launch_lowrank_combo(const LowrankArgs& a, hipStream_t s) {
+    const int this_layer = a.this_layer, prev = a.prev, B = a.B, H = a.H, N = a.N, E = a.E;
     const int T = B * N, chunks = ceil_div(T, LG_ROWS);
     if (E % 64) { pevit_set_error("lowrank_combo: width %d must be a multiple of 64", E); return -1; }
     const int nu = this_layer ? ceil_div(T, 16 * LC_URG) : 0;
@@ -784,8 +780,8 @@ int pevit_launch_lowrank_combo(int this_layer, int prev, const bf16* dqkv, int l
     const int n12 = this_layer ? chunks * groups * 2 : 0, n0 = prev ? chunks * groups : 0;
     const int nu_pad = (nu + 7) & ~7, n12_pad = (n12 + 7) & ~7, n0_pad = (n0 + 7) & ~7;
     if (nu_pad + n12_pad + n0_pad == 0) return 0;
-#define LC_GO(HC, NC) hipLaunchKernelGGL((lowrank_combo_kernel<HC, NC>), dim3(nu_pad + n12_pad + n0_pad), dim3(256), 0, s, dqkv, ld, qT, u32, ucols, t, partial, \
-                                        dbias_partial, xn_prev, ldx, u32_prev, partial_prev, nu, nu_pad, n12, n12_pad, n0, B, H, N, E, es)
+#define LC_GO(HC, NC) hipLaunchKernelGGL((lowrank_combo_kernel<HC, NC>), dim3(nu_pad + n12_pad + n0_pad), dim3(256), 0, s, a.dqkv, a.ld, a.qT, a.u32, a.u_bf16_cols, a.t, a.partial, \
+                                        a.dbias_partial, a.xn_prev, a.ldx, a.u32_prev, a.partial_prev, nu, nu_pad, n12, n12_pad, n0, B, H, N, E, es)
     if (E != 64 * H) LC_GO(0, 0);
     else if (H == 12 && N == 50) LC_GO(12, 50);          // ViT-B/32
     else if (H == 12 && N == 197) LC_GO(12, 197);        // ViT-B/16
@@ -796,34 +792,32 @@ int pevit_launch_lowrank_combo(int this_layer, int prev, const bf16* dqkv, int l
     return 0;
 }
 
-int pevit_launch_lowrank_grad(const bf16* xn, int ldx, const float* u32, const bf16* dqkv, int ld, const float* t,
-                              float* partial, float* dbias_partial, int chunks, int B, int H, int N, int E,
-                              hipStream_t s, int xcd_order) {
-    const int T = B * N;
+int pevit_launch_lowrank_grad(const LowrankArgs& a, hipStream_t s) {
+    const int chunks = a.chunks, E = a.E;
+    const int T = a.B * a.N;
     if (chunks != ceil_div(T, LG_ROWS)) { pevit_set_error("lowrank_grad: chunks mismatch"); return -1; }
     if (E % 64) { pevit_set_error("lowrank_grad: width %d must be a multiple of 64", E); return -1; }
     const int es = lg_pick_es(E, chunks, 3, 0);
     if (!es) { pevit_set_error("lowrank_grad: no slab grouping for width %d", E); return -1; }
-    hipLaunchKernelGGL(lowrank_grad_kernel, dim3(chunks * (E / 64 / es) * 3), dim3(256), 0, s, xn, ldx, u32, dqkv, ld, t,
-                       partial, dbias_partial, B, H, N, E, xcd_order, es);
+    hipLaunchKernelGGL(lowrank_grad_kernel, dim3(chunks * (E / 64 / es) * 3), dim3(256), 0, s, a.xn, a.ldx, a.u32, a.dqkv, a.ld, a.t,
+                       a.partial, a.dbias_partial, a.B, a.H, a.N, E, a.xcd_order, es);
     LAUNCH_OK("lowrank_grad_kernel");
     return 0;
 }
 
 // partial: [layers][chunks+? ...] see capi.hip; G: [layers][4][E][32]; rule_scratch: [layers][4096]
-int pevit_launch_chain_kadapt(const float* partial, size_t partial_layer, const float* dbias_partial, size_t dbias_layer,
-                              int chunks, float ascale, int layers, float* G, float* rule_scratch, const float* params,
-                              float* grads, size_t p_layer0, size_t p_layer_stride, int E, hipStream_t s) {
+int pevit_launch_chain_kadapt(const ChainKadaptArgs& a, hipStream_t s) {
+    const int E = a.E;
     if (64 + 2 * (E / 32) > 256) { pevit_set_error("chain_kadapt: width %d too large", E); return -1; }
-    float* g_b = grads + p_layer0 + 4 * (size_t)E;
-    hipLaunchKernelGGL(lowrank_reduce_kernel, dim3(ceil_div(4 * E * 32, 4 * 256), layers), dim3(256), 0, s, partial,
-                       dbias_partial, chunks, G, g_b, E, partial_layer, dbias_layer, p_layer_stride);
+    float* g_b = a.grads + a.p_layer0 + 4 * (size_t)E;
+    hipLaunchKernelGGL(lowrank_reduce_kernel, dim3(ceil_div(4 * E * 32, 4 * 256), a.layers), dim3(256), 0, s, a.partial,
+                       a.dbias_partial, a.chunks, a.G, g_b, E, a.partial_layer, a.dbias_layer, a.p_layer_stride);
     LAUNCH_OK("lowrank_reduce_kernel");
-    const float* r = params;
-    const float* lp = params + p_layer0;
-    float* lg = grads + p_layer0;
-    hipLaunchKernelGGL(chain_kadapt_kernel, dim3(32, layers), dim3(256), 4 * E * sizeof(float), s, G, ascale, r, r + 1024,
-                       r + 2048, r + 3072, lp, lp + E, rule_scratch, lg, lg + E, E, p_layer_stride);
+    const float* r = a.params;
+    const float* lp = a.params + a.p_layer0;
+    float* lg = a.grads + a.p_layer0;
+    hipLaunchKernelGGL(chain_kadapt_kernel, dim3(32, a.layers), dim3(256), 4 * E * sizeof(float), s, a.G, a.ascale, r, r + 1024,
+                       r + 2048, r + 3072, lp, lp + E, a.rule_scratch, lg, lg + E, E, a.p_layer_stride);
     LAUNCH_OK("chain_kadapt_kernel");
     return 0;
 }
@@ -836,15 +830,15 @@ int pevit_launch_rule_sum(const float* rule_scratch, float* grads, int l_lo, int
     return 0;
 }
 
-int pevit_launch_chain_lora(const float* partial, size_t partial_layer, int chunks, float ascale, int r, int layers,
-                            float* G, float* grads, size_t p_layer0, size_t p_layer_stride, int E, hipStream_t s) {
-    hipLaunchKernelGGL(lowrank_reduce_kernel, dim3(ceil_div(4 * E * 32, 4 * 256), layers), dim3(256), 0, s, partial,
-                       (const float*)nullptr, chunks, G, (float*)nullptr, E, partial_layer, (size_t)0, (size_t)0);
+int pevit_launch_chain_lora(const ChainLoraArgs& a, hipStream_t s) {
+    const int E = a.E, r = a.r;
+    hipLaunchKernelGGL(lowrank_reduce_kernel, dim3(ceil_div(4 * E * 32, 4 * 256), a.layers), dim3(256), 0, s, a.partial,
+                       (const float*)nullptr, a.chunks, a.G, (float*)nullptr, E, a.partial_layer, (size_t)0, (size_t)0);
     LAUNCH_OK("lowrank_reduce_kernel");
     const size_t rE = (size_t)r * E;
-    float* lg = grads + p_layer0;
-    hipLaunchKernelGGL(chain_lora_kernel, dim3(ceil_div(E * r, 256), layers), dim3(256), 0, s, G, ascale, r, lg, lg + rE,
-                       lg + 2 * rE, lg + 3 * rE, E, p_layer_stride);
+    float* lg = a.grads + a.p_layer0;
+    hipLaunchKernelGGL(chain_lora_kernel, dim3(ceil_div(E * r, 256), a.layers), dim3(256), 0, s, a.G, a.ascale, r, lg, lg + rE,
+                       lg + 2 * rE, lg + 3 * rE, E, a.p_layer_stride);
     LAUNCH_OK("chain_lora_kernel");
     return 0;
 }

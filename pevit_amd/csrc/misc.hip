@@ -164,12 +164,10 @@ int pevit_launch_scale_f32(float* p, size_t n, float scale, hipStream_t s) {
     return 0;
 }
 
-int pevit_launch_sgd(float* p, const float* g, float* mom, const unsigned char* has_grad, size_t n, float lr,
-                     float momentum, float wd, int first_step, float grad_scale, hipStream_t s, const unsigned* poison,
-                     unsigned* skipped, const unsigned* poison2, float* loss_slot) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, mom, has_grad, n, lr,
-                       momentum, wd, first_step, grad_scale, poison, skipped, poison2, loss_slot);
+int pevit_launch_sgd(const SgdArgs& a, hipStream_t s) {
+    if (a.n == 0) return 0;
+    hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a.p, a.g, a.mom, a.has_grad, a.n, a.lr,
+                       a.momentum, a.wd, a.first_step, a.grad_scale, a.poison, a.skipped, a.poison2, a.loss_slot);
     LAUNCH_OK("sgd_kernel");
     return 0;
 }

@@ -177,11 +177,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
 
 }  // namespace
 
-int pevit_launch_ln_fwd(const float* x, const float* gamma, const float* beta, int rows, int E, bf16* y_bf16,
-                        float* y_f32, float* mean, float* rstd, hipStream_t s, size_t xstride, int f32, unsigned char* y_fp8) {
-    if (xstride == 0) xstride = (size_t)E;
+int pevit_launch_ln_fwd(const LnFwdArgs& a, hipStream_t s) {
+    const int rows = a.rows, E = a.E;
+    const size_t xstride = a.xstride ? a.xstride : (size_t)E;
     if (E % 4 != 0 || E > 256 * MAXV) { pevit_set_error("ln_fwd: unsupported width %d", E); return -1; }
-    if (y_fp8 && E % 128 != 0) { pevit_set_error("ln_fwd: the fp8 copy needs a width that is a multiple of 128"); return -1; }
+    if (a.y_fp8 && E % 128 != 0) { pevit_set_error("ln_fwd: the fp8 copy needs a width that is a multiple of 128"); return -1; }
     if (rows <= 0) return 0;
     // The E / 256 instances are NOT used by the forward kernel: measured on one box (scripts/experiments/gpu_r5_ln.sh) the generic
     // predicated form is the faster one here (7.2 against 7.5 us at E = 768, 10.3 against 10.9 at E = 1024) while the backward kernel
@@ -191,41 +191,39 @@ int pevit_launch_ln_fwd(const float* x, const float* gamma, const float* beta, i
 #else
     const int nv = 0;
 #endif
-#define LN_FWD_GO(ST, N) hipLaunchKernelGGL((ln_fwd_kernel<ST, N>), dim3(ceil_div(rows, 4)), dim3(256), 0, s, x, gamma, beta, rows, E, xstride, y_bf16, y_f32, mean, rstd, y_fp8)
+#define LN_FWD_GO(ST, N) hipLaunchKernelGGL((ln_fwd_kernel<ST, N>), dim3(ceil_div(rows, 4)), dim3(256), 0, s, a.x, a.gamma, a.beta, rows, E, xstride, a.y_bf16, a.y_f32, a.mean, a.rstd, a.y_fp8)
 #define LN_FWD_NV(ST) switch (nv) { case 1: LN_FWD_GO(ST, 1); break; case 2: LN_FWD_GO(ST, 2); break; case 3: LN_FWD_GO(ST, 3); break; \
                                     case 4: LN_FWD_GO(ST, 4); break; default: LN_FWD_GO(ST, 0); }
-    if (f32) { LN_FWD_NV(float) } else { LN_FWD_NV(bf16) }
+    if (a.f32) { LN_FWD_NV(float) } else { LN_FWD_NV(bf16) }
 #undef LN_FWD_NV
 #undef LN_FWD_GO
     LAUNCH_OK("ln_fwd_kernel");
     return 0;
 }
 
-int pevit_launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                        const float* dres, float* dx_out, bf16* dx_bf16, int rows, int E, hipStream_t s,
-                        size_t xstride, const float* bf16_colscale, int f32, int dy_stored, int res_period, int res16,
-                        const float* res_colscale) {
-    if (xstride == 0) xstride = (size_t)E;
+int pevit_launch_ln_bwd(const LnBwdArgs& a, hipStream_t s) {
+    const int rows = a.rows, E = a.E;
+    const size_t xstride = a.xstride ? a.xstride : (size_t)E;
     if (E % 4 != 0 || E > 256 * MAXV) { pevit_set_error("ln_bwd: unsupported width %d", E); return -1; }
     if (rows <= 0) return 0;
     const dim3 grid(ceil_div(rows, 4));
-    if (res16 && (f32 || !dy_stored || !dx_bf16)) { pevit_set_error("ln_bwd: the bf16 residual form needs bf16 storage on both sides"); return -1; }
-    if (res16 && !dres) { pevit_set_error("ln_bwd: the bf16 residual form reads its residual gradient from dres (null)"); return -1; }
+    if (a.res16 && (a.f32 || !a.dy_stored || !a.dx_bf16)) { pevit_set_error("ln_bwd: the bf16 residual form needs bf16 storage on both sides"); return -1; }
+    if (a.res16 && !a.dres) { pevit_set_error("ln_bwd: the bf16 residual form reads its residual gradient from dres (null)"); return -1; }
 #ifdef LN_NV_OFF
     const int nv = 0;                          // (A/B builds: the generic kernels)
 #else
     const int nv = E % 256 == 0 ? E / 256 : 0;
 #endif
-    const bool scl = bf16_colscale != nullptr || res_colscale != nullptr;
-#define LN_BWD_GO(ST, DYT, R, N) do { if (scl) hipLaunchKernelGGL((ln_bwd_kernel<ST, DYT, R, N, true>), grid, dim3(256), 0, s, dy, x, mean, rstd, gamma, dres, \
-                                                    dx_out, dx_bf16, rows, E, xstride, bf16_colscale, res_period, res_colscale); \
-                                      else hipLaunchKernelGGL((ln_bwd_kernel<ST, DYT, R, N, false>), grid, dim3(256), 0, s, dy, x, mean, rstd, gamma, dres, \
-                                                    dx_out, dx_bf16, rows, E, xstride, bf16_colscale, res_period, res_colscale); } while (0)
+    const bool scl = a.bf16_colscale != nullptr || a.res_colscale != nullptr;
+#define LN_BWD_GO(ST, DYT, R, N) do { if (scl) hipLaunchKernelGGL((ln_bwd_kernel<ST, DYT, R, N, true>), grid, dim3(256), 0, s, a.dy, a.x, a.mean, a.rstd, a.gamma, a.dres, \
+                                                    a.dx_out, a.dx_bf16, rows, E, xstride, a.bf16_colscale, a.res_period, a.res_colscale); \
+                                      else hipLaunchKernelGGL((ln_bwd_kernel<ST, DYT, R, N, false>), grid, dim3(256), 0, s, a.dy, a.x, a.mean, a.rstd, a.gamma, a.dres, \
+                                                    a.dx_out, a.dx_bf16, rows, E, xstride, a.bf16_colscale, a.res_period, a.res_colscale); } while (0)
 #define LN_BWD_NV(ST, DYT, R) switch (nv) { case 1: LN_BWD_GO(ST, DYT, R, 1); break; case 2: LN_BWD_GO(ST, DYT, R, 2); break; \
                                             case 3: LN_BWD_GO(ST, DYT, R, 3); break; case 4: LN_BWD_GO(ST, DYT, R, 4); break; default: LN_BWD_GO(ST, DYT, R, 0); }
-    if (res16) { LN_BWD_NV(bf16, bf16, true) }
-    else if (f32) { LN_BWD_NV(float, float, false) }
-    else if (dy_stored) { LN_BWD_NV(bf16, bf16, false) }
+    if (a.res16) { LN_BWD_NV(bf16, bf16, true) }
+    else if (a.f32) { LN_BWD_NV(float, float, false) }
+    else if (a.dy_stored) { LN_BWD_NV(bf16, bf16, false) }
     else { LN_BWD_NV(bf16, float, false) }
 #undef LN_BWD_NV
 #undef LN_BWD_GO

@@ -515,10 +515,11 @@ int pevit_launch_im2col(const float* img, bf16* out, int B, int R, int P, int Kp
     LAUNCH_OK("im2col_kernel");
     return 0;
 }
-int pevit_launch_im2col_u8(const unsigned char* img, const float* mean3, const float* std3, bf16* out, int B, int R, int P, int Kp,
-                           hipStream_t s, int f32) {
+int pevit_launch_im2col_u8(const Im2colU8Args& a, hipStream_t s) {
+    const unsigned char* img = a.img; bf16* out = a.out;
+    const int B = a.B, R = a.R, P = a.P, Kp = a.Kp, f32 = a.f32;
     PixelNorm nm;
-    for (int c = 0; c < 3; ++c) { nm.mean[c] = mean3[c]; nm.stdv[c] = std3[c]; }
+    for (int c = 0; c < 3; ++c) { nm.mean[c] = a.mean3[c]; nm.stdv[c] = a.std3[c]; }
     if (P % 8 == 0 && R % 8 == 0) {
         const size_t total8 = (size_t)B * (R / P) * (R / P) * (Kp / 8);
         const int blocks8 = (int)((total8 + 255) / 256 > 16384 ? 16384 : (total8 + 255) / 256);
@@ -546,14 +547,15 @@ int pevit_launch_cls_row(const float* cls, const float* pos, float* x, int B, in
     LAUNCH_OK("cls_row_kernel");
     return 0;
 }
-int pevit_launch_head(const float* feat, const int64_t* labels, const float* targets, const float* W, const float* bias, float* gW,
-                      float* gb, float* running_mean, float* running_var, int training, float* ybn, float* rstd, float* logits,
-                      float* dlogits, float* dybn, float* loss, float* dfeat, int B, int D, int Cc, hipStream_t s, bf16* dfeat_b16) {
-    hipLaunchKernelGGL(bn_fwd_kernel, dim3(ceil_div(D, 16)), dim3(256), 0, s, feat, ybn, rstd, running_mean, running_var,
+int pevit_launch_head(const HeadArgs& a, hipStream_t s) {
+    const int64_t* labels = a.labels; const float* targets = a.targets; const float* W = a.W;
+    float *ybn = a.ybn, *rstd = a.rstd, *logits = a.logits, *dlogits = a.dlogits, *dybn = a.dybn, *loss = a.loss;
+    const int training = a.training, B = a.B, D = a.D, Cc = a.Cc;
+    hipLaunchKernelGGL(bn_fwd_kernel, dim3(ceil_div(D, 16)), dim3(256), 0, s, a.feat, ybn, rstd, a.running_mean, a.running_var,
                        training, B, D);
     LAUNCH_OK("bn_fwd_kernel");
     {   // logits[b][c] = ybn[b] . W[c] + bias[c]
-        SmallGemm g{ybn, D, 1, W, 1, D, logits, Cc, bias, nullptr, B, Cc, D, 0};
+        SmallGemm g{ybn, D, 1, W, 1, D, logits, Cc, a.bias, nullptr, B, Cc, D, 0};
         hipLaunchKernelGGL(small_gemm_kernel, dim3(ceil_div(Cc, 32), ceil_div(B, 32)), dim3(256), 0, s, g);
         LAUNCH_OK("small_gemm_kernel");
     }
@@ -571,16 +573,16 @@ int pevit_launch_head(const float* feat, const int64_t* labels, const float* tar
         hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(64), 0, s, rowloss, labels, loss, B);
         LAUNCH_OK("loss_mean_kernel");
     }
-    if (gW) {   // gW[c][d] += sum_b dl[b][c] ybn[b][d] ; gb[c] += sum_b dl[b][c]
-        SmallGemm g{dlogits, 1, Cc, ybn, D, 1, gW, D, nullptr, gb, Cc, D, B, 1};
+    if (a.gW) {   // gW[c][d] += sum_b dl[b][c] ybn[b][d] ; gb[c] += sum_b dl[b][c]
+        SmallGemm g{dlogits, 1, Cc, ybn, D, 1, a.gW, D, nullptr, a.gb, Cc, D, B, 1};
         hipLaunchKernelGGL(small_gemm_kernel, dim3(ceil_div(D, 32), ceil_div(Cc, 32)), dim3(256), 0, s, g);
         LAUNCH_OK("small_gemm_kernel");
     }
-    if (dfeat) {   // dybn[b][d] = sum_c dl[b][c] W[c][d]
+    if (a.dfeat) {   // dybn[b][d] = sum_c dl[b][c] W[c][d]
         SmallGemm g{dlogits, Cc, 1, W, D, 1, dybn, D, nullptr, nullptr, B, D, Cc, 0};
         hipLaunchKernelGGL(small_gemm_kernel, dim3(ceil_div(D, 32), ceil_div(B, 32)), dim3(256), 0, s, g);
         LAUNCH_OK("small_gemm_kernel");
-        hipLaunchKernelGGL(bn_bwd_kernel, dim3(ceil_div(D, 16)), dim3(256), 0, s, dybn, ybn, rstd, dfeat, training, B, D, dfeat_b16);
+        hipLaunchKernelGGL(bn_bwd_kernel, dim3(ceil_div(D, 16)), dim3(256), 0, s, dybn, ybn, rstd, a.dfeat, training, B, D, a.dfeat_bf16);
         LAUNCH_OK("bn_bwd_kernel");
     }
     return 0;

@@ -280,12 +280,16 @@ __global__ __launch_bounds__(256) void tn_gemm64_f32_kernel(const float* __restr
     }
 }
 
+// the f32 twins take their production sibling's parameter struct: its bf16-declared members hold f32 in this mode
+inline const float* f32p(const bf16* p) { return reinterpret_cast<const float*>(p); }
+inline float* f32p(bf16* p) { return reinterpret_cast<float*>(p); }
+
 }  // namespace
 
-int pevit_launch_tn_gemm64_f32(const float* X, int ldx, const float* Y, int ldy, float* partial, float* csx, float* csy, int T, int E,
-                               hipStream_t s) {
-    if (E % 64) { pevit_set_error("tn_gemm64 (f32 verification): bad width %d", E); return -1; }
-    hipLaunchKernelGGL(tn_gemm64_f32_kernel, dim3(ceil_div(T, VT_ROWS) * (E / 64)), dim3(256), 0, s, X, ldx, Y, ldy, partial, csx, csy, T, E);
+int pevit_launch_tn_gemm64_f32(const TnGemm64Args& a, hipStream_t s) {
+    if (a.E % 64) { pevit_set_error("tn_gemm64 (f32 verification): bad width %d", a.E); return -1; }
+    hipLaunchKernelGGL(tn_gemm64_f32_kernel, dim3(ceil_div(a.T, VT_ROWS) * (a.E / 64)), dim3(256), 0, s, f32p(a.X), a.ldx, f32p(a.Y), a.ldy, a.partial,
+                       a.csx, a.csy, a.T, a.E);
     LAUNCH_OK("tn_gemm64_f32_kernel");
     return 0;
 }
@@ -314,43 +318,41 @@ int pevit_launch_gemm_f32(int epi, const GemmParams& p, hipStream_t s) {
     return -1;
 }
 
-int pevit_launch_attn_fwd_f32(const float* q, const float* k, const float* v, float* out, int ldo, float* lse, int B, int H, int N,
-                              hipStream_t s) {
-    if (N < 1 || N > 320) { pevit_set_error("attn_fwd (f32 verification): N=%d outside [1,320]", N); return -1; }
-    hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(B * H), dim3(256), 0, s, q, k, v, out, ldo, lse, H, N);
+int pevit_launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s) {
+    if (a.N < 1 || a.N > 320) { pevit_set_error("attn_fwd (f32 verification): N=%d outside [1,320]", a.N); return -1; }
+    hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(a.B * a.H), dim3(256), 0, s, f32p(a.q), f32p(a.k), f32p(a.v), f32p(a.out), a.ldo, a.lse, a.H, a.N);
     LAUNCH_OK("attn_fwd_f32_kernel");
     return 0;
 }
 
-int pevit_launch_attn_bwd_f32(const float* q, const float* k, const float* v, const float* out, int ldo, const float* dout,
-                              int lddo, const float* lse, float* dqkv, int ld, int B, int H, int N, hipStream_t s) {
-    if (N < 1 || N > 320) { pevit_set_error("attn_bwd (f32 verification): N=%d outside [1,320]", N); return -1; }
-    hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(B * H), dim3(256), 0, s, q, k, v, out, ldo, dout, lddo, lse, dqkv, ld, H, N);
+int pevit_launch_attn_bwd_f32(const AttnArgs& a, hipStream_t s) {
+    if (a.N < 1 || a.N > 320) { pevit_set_error("attn_bwd (f32 verification): N=%d outside [1,320]", a.N); return -1; }
+    hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(a.B * a.H), dim3(256), 0, s, f32p(a.q), f32p(a.k), f32p(a.v), f32p(a.out), a.ldo, f32p(a.dout), a.lddo,
+                       a.lse, f32p(a.dqkv), a.ld, a.H, a.N);
     LAUNCH_OK("attn_bwd_f32_kernel");
     return 0;
 }
 
-int pevit_launch_attn_probs_f32(const float* q, const float* k, const float* lse, float* out, int B, int H, int N, int average,
-                                hipStream_t s) {
-    if (N < 1 || N > 384) { pevit_set_error("attn_probs (f32 verification): N=%d outside [1,384]", N); return -1; }
-    const size_t n = (size_t)B * N * N;
-    hipLaunchKernelGGL(attn_probs_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, k, lse, out, B, H, N, average);
+int pevit_launch_attn_probs_f32(const AttnArgs& a, hipStream_t s) {
+    if (a.N < 1 || a.N > 384) { pevit_set_error("attn_probs (f32 verification): N=%d outside [1,384]", a.N); return -1; }
+    const size_t n = (size_t)a.B * a.N * a.N;
+    hipLaunchKernelGGL(attn_probs_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f32p(a.q), f32p(a.k), a.lse, a.probs, a.B, a.H, a.N,
+                       a.average);
     LAUNCH_OK("attn_probs_f32_kernel");
     return 0;
 }
 
-int pevit_launch_lowrank_u_f32(const float* dqkv, int ld, const float* q32, float* u32, float* ucols, int B, int H, int N, int E,
-                               hipStream_t s) {
-    hipLaunchKernelGGL(lowrank_u_f32_kernel, dim3(ceil_div(B * N * 64, 256)), dim3(256), 0, s, dqkv, ld, q32, u32, ucols, B, H, N, E);
+int pevit_launch_lowrank_u_f32(const LowrankArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(lowrank_u_f32_kernel, dim3(ceil_div(a.B * a.N * 64, 256)), dim3(256), 0, s, f32p(a.dqkv), a.ld, a.q32, a.u32, f32p(a.u_bf16_cols),
+                       a.B, a.H, a.N, a.E);
     LAUNCH_OK("lowrank_u_f32_kernel");
     return 0;
 }
 
-int pevit_launch_lowrank_grad_f32(const float* xn, int ldx, const float* u32, const float* dqkv, int ld, const float* t,
-                                  float* partial, float* dbias_partial, int chunks, int B, int H, int N, int E, hipStream_t s) {
-    if (chunks != ceil_div(B * N, VG_ROWS)) { pevit_set_error("lowrank_grad (f32 verification): chunks mismatch"); return -1; }
-    hipLaunchKernelGGL(lowrank_grad_f32_kernel, dim3(chunks * (E / 64) * 3), dim3(256), 0, s, xn, ldx, u32, dqkv, ld, t, partial,
-                       dbias_partial, B, H, N, E);
+int pevit_launch_lowrank_grad_f32(const LowrankArgs& a, hipStream_t s) {
+    if (a.chunks != ceil_div(a.B * a.N, VG_ROWS)) { pevit_set_error("lowrank_grad (f32 verification): chunks mismatch"); return -1; }
+    hipLaunchKernelGGL(lowrank_grad_f32_kernel, dim3(a.chunks * (a.E / 64) * 3), dim3(256), 0, s, f32p(a.xn), a.ldx, a.u32, f32p(a.dqkv), a.ld, a.t,
+                       a.partial, a.dbias_partial, a.B, a.H, a.N, a.E);
     LAUNCH_OK("lowrank_grad_f32_kernel");
     return 0;
 }

@@ -1,5 +1,6 @@
-import sys, time, torch
-sys.path.insert(0, '/root/repo')
+"""Host enqueue time per fused step (KAdaptation, ViT-B/32) at batch 128 / 64 / 16 / 4, with whatever library is at pevit_amd/libpevit_hip.so."""
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pevit_amd.engine import HipEngine
 from pevit_amd.synth import ARCHS, reference_init_, synth_batch, synth_state_dict
 arch = ARCHS["ViT-B/32"]
