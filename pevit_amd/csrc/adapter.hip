@@ -17,24 +17,12 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "mfma_frag.h"
 
 namespace {
 
 constexpr int TG_ROWS = 256;
 constexpr int TG_LD = 72;           // row stride (elements) of the row-major LDS tiles
-// MFMA fragment of the TRANSPOSE of a row-major LDS tile [token][TG_LD] by ds_read_b64_tr_b16 (see lowrank.hip lg_trfrag):
-// lane (m, g) gets column col0 + m for the tokens 32ks + 4g + 0..3 and 32ks + 16 + 4g + 0..3
-__device__ __forceinline__ bf16x8 tg_trfrag(const bf16* tile, int ks, int col0, int lane) {
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-    const int m = lane & 15, g = lane >> 4;
-    const bf16* src = tile + (32 * ks + 4 * g + (m >> 2)) * TG_LD + col0 + 4 * (m & 3);
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src + 16 * TG_LD));
-    bf16x8 o;
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-    o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-    return o;
-}
 
 // ---------------------------------------------------------------------------------------------
 // panels: wd [64][E] (B operand of the down GEMM), wdT [E][64] (d z GEMM), wu [E][64] (up GEMM),
@@ -136,9 +124,7 @@ __global__ __launch_bounds__(256) void tn_gemm64_kernel(const bf16* __restrict__
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        float a = sx[i], b = sy[i];
-        a += __shfl_xor(a, 8, 64); a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-        b += __shfl_xor(b, 8, 64); b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
+        const float a = rowlane_sum(sx[i]), b = rowlane_sum(sy[i]);
         if ((lane >> 3) == 0) { cs[0][wid][8 * c + i] = a; cs[1][wid][8 * c + i] = b; }
     }
     __syncthreads();
@@ -147,10 +133,10 @@ __global__ __launch_bounds__(256) void tn_gemm64_kernel(const bf16* __restrict__
     for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < TG_ROWS / 32; ++ks) {
-        const bf16x8 a = tg_trfrag(Xs, ks, 16 * wid, lane);
+        const bf16x8 a = trfrag<TG_LD>(Xs, ks, 16 * wid, lane);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, tg_trfrag(Ys, ks, 16 * nt, lane), acc[nt], 0, 0, 0);
+            acc[nt] = mfma16(a, trfrag<TG_LD>(Ys, ks, 16 * nt, lane), acc[nt]);
     }
     float* out = partial + (size_t)chunk * E * 64;
 #pragma unroll
@@ -462,23 +448,20 @@ int pevit_launch_tn_gemm64(const TnGemm64Args& a, hipStream_t s) {
     LAUNCH_OK("tn_gemm64_kernel");
     return 0;
 }
-int pevit_launch_ln_bwd_affine(const LnBwdAffineArgs& a, hipStream_t s) {
+template <typename ST>
+static int launch_ln_bwd_affine(const LnBwdAffineArgs& a, hipStream_t s) {
     const int rows = a.rows, E = a.E;
     if (E % 4 || E > 256 * LNA_MAXV) { pevit_set_error("ln_bwd_affine: unsupported width %d", E); return -1; }
     const size_t lds = (size_t)(LNA_WAVES - 1) * 3 * E * sizeof(float);      // 64.5 KiB at E = 768
-    static bool attr_set = false;
-    if (!attr_set) {
-        const int maxlds = (LNA_WAVES - 1) * 3 * 256 * LNA_MAXV * (int)sizeof(float);
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_affine_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_affine_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-        attr_set = true;
-    }
-    if (a.f32) hipLaunchKernelGGL(ln_bwd_affine_kernel<float>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, a.dy, a.x, a.mean, a.rstd,
-                                  a.gamma, a.dres, a.dx, a.dx_bf16, a.partial, rows, E);
-    else hipLaunchKernelGGL(ln_bwd_affine_kernel<bf16>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, a.dy, a.x, a.mean, a.rstd,
-                            a.gamma, a.dres, a.dx, a.dx_bf16, a.partial, rows, E);
+    constexpr int maxlds = (LNA_WAVES - 1) * 3 * 256 * LNA_MAXV * (int)sizeof(float);
+    if (reserve_lds<ln_bwd_affine_kernel<ST>, maxlds>("ln_bwd_affine")) return -1;
+    hipLaunchKernelGGL(ln_bwd_affine_kernel<ST>, dim3(ceil_div(rows, LNA_ROWS)), dim3(64 * LNA_WAVES), lds, s, a.dy, a.x, a.mean, a.rstd, a.gamma,
+                       a.dres, a.dx, a.dx_bf16, a.partial, rows, E);
     LAUNCH_OK("ln_bwd_affine_kernel");
     return 0;
+}
+int pevit_launch_ln_bwd_affine(const LnBwdAffineArgs& a, hipStream_t s) {
+    return a.f32 == 0 ? launch_ln_bwd_affine<bf16>(a, s) : launch_ln_bwd_affine<float>(a, s);      // (named in the order the code object lists them)
 }
 int pevit_launch_colsum_reduce(const float* partial, int chunks, int n, float* out, int layers, size_t partial_layer,
                                size_t out_layer, hipStream_t s) {

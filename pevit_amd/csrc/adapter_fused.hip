@@ -17,6 +17,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "mfma_frag.h"
 
 namespace {
 
@@ -121,7 +122,7 @@ __device__ __forceinline__ void af_first_product(const bf16* Xs, int ldx, const 
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s)
-                if (ks + 32 * s < kw) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s], b[s], acc, 0, 0, 0);
+                if (ks + 32 * s < kw) acc = mfma16(a[s], b[s], acc);
         }
         float* mine = red + kh * (AF_ROWS * AF_REDLD);
 #pragma unroll
@@ -217,7 +218,7 @@ __device__ __forceinline__ void af_second_product(const bf16* Ss, const bf16* __
                 if (f < nfrag) {
                     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s], b[u][s], acc, 0, 0, 0);
+                    for (int s = 0; s < 2; ++s) acc = mfma16(a[s], b[u][s], acc);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) U[(4 * kg + r) * (E + 4) + 16 * f + m] = acc[r];
                 }
@@ -371,18 +372,6 @@ struct AfTn {
     const bf16* X2; const bf16* Y2; float* P2; float* csy2; int n2;        // previous launch's layer: X = z, Y = d pre (+ its column sums)
 };
 
-__device__ __forceinline__ bf16x8 af_trfrag(const bf16* tile, int ks, int col0, int lane) {
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-    const int m = lane & 15, g = lane >> 4;
-    const bf16* src = tile + (32 * ks + 4 * g + (m >> 2)) * TNH_LD + col0 + 4 * (m & 3);
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src + 16 * TNH_LD));
-    bf16x8 o;
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-    o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-    return o;
-}
-
 // The contraction range: workgroup blk of nblk walks the unit pairs blk, blk + nblk, ... (its two halves take one unit each), with
 // sixteen 16-byte requests per thread in flight per unit.  The launcher's default is one workgroup per pair (a single trip); fewer,
 // walking workgroups measured slower (see the launcher), and since round 5 they no longer request the next unit under the current one:
@@ -436,7 +425,7 @@ __device__ __forceinline__ void af_tn_range(char* smem, int blk, int nblk, const
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            float b = sy[i];
+            float b = sy[i];                                 // rowlane_sum (mfma_frag.h), spelled out: through the call hipcc schedules this kernel differently
             b += __shfl_xor(b, 8, 64); b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
             if ((lane >> 3) == 0) cs[w][8 * c + i] = b;
         }
@@ -455,10 +444,10 @@ __device__ __forceinline__ void af_tn_range(char* smem, int blk, int nblk, const
             __syncthreads();
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 a = af_trfrag(Xs, ks, 16 * w, lane);
+                const bf16x8 a = trfrag<TNH_LD>(Xs, ks, 16 * w, lane);
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, af_trfrag(Ys, ks, 16 * nt, lane), acc[nt], 0, 0, 0);
+                    acc[nt] = mfma16(a, trfrag<TNH_LD>(Ys, ks, 16 * nt, lane), acc[nt]);
             }
         }
         float csv = 0.f;
@@ -636,11 +625,21 @@ int af_check(int T, int E, const char* who) {
     if (T <= 0 || !pevit_adapter_fused_ok(E)) { pevit_set_error("%s: unsupported shape T=%d E=%d (E a multiple of 256, <= 1024)", who, T, E); return -1; }
     return 0;
 }
-template <typename K>
-int af_attr(K kern, int bytes, const char* who) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-        pevit_set_error("%s: cannot reserve %d bytes of LDS", who, bytes); return -1;
-    }
+// one kernel instantiation onto the stream; the 160 KB dynamic-LDS limit is raised by its first launch
+template <auto KERN>
+int af_launch_fwd(const AdapterFwdArgs& a, int rb, int lds, hipStream_t s) {
+    if (reserve_lds<KERN, 160 * 1024>("adapter_fwd")) return -1;
+    hipLaunchKernelGGL(KERN, dim3(ceil_div(a.T, rb)), dim3(64 * AF_WAVES), lds, s, a.hraw, a.bpr, a.x_mid, a.gamma, a.beta, a.wd, a.b_down, a.wu, a.b_up,
+                       a.z, a.mean_a, a.rstd_a, a.act, a.apre, a.x_out, a.T, a.E, rb);
+    LAUNCH_OK("adapter_fwd_kernel");
+    return 0;
+}
+template <auto KERN>
+int af_launch_bwd(const AdapterBwdArgs& a, int rb, int nb, int ntn, const AfTn& tn, int lds, hipStream_t s) {
+    if (reserve_lds<KERN, 160 * 1024>("adapter_bwd")) return -1;
+    hipLaunchKernelGGL(KERN, dim3(nb + ntn), dim3(64 * AF_WAVES), lds, s, a.dyb, a.dres, a.wuT, a.saved, a.wdT, a.hraw, a.bpr, a.mean_a, a.rstd_a,
+                       a.gamma, a.dpre, a.dh_bf16, a.partial, a.T, a.E, rb, nb, tn);
+    LAUNCH_OK("adapter_bwd_kernel");
     return 0;
 }
 
@@ -659,27 +658,17 @@ int pevit_launch_adapter_fwd(const AdapterFwdArgs& a, hipStream_t s) {
     const AfLds L = af_layout(E);
     const int lds = L.colred;
     const int rb = af_rows_per_wg(T);
-    const dim3 grid(ceil_div(T, rb)), block(64 * AF_WAVES);
-    static bool attr[2][AF_MAXV] = {};
-    auto go = [&](auto kern, int slot, int nv) -> int {
-        if (!attr[slot][nv - 1]) { if (af_attr(kern, 160 * 1024, "adapter_fwd")) return -1; attr[slot][nv - 1] = true; }
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a.hraw, a.bpr, a.x_mid, a.gamma, a.beta, a.wd, a.b_down, a.wu, a.b_up, a.z, a.mean_a, a.rstd_a, a.act, a.apre, a.x_out, T, E, rb);
-        return 0;
-    };
-    int rc = -1;
     switch (4 * (a.act_kind != 0) + E / 256 - 1) {
-        case 0: rc = go(adapter_fwd_kernel<0, 1>, 0, 1); break;
-        case 1: rc = go(adapter_fwd_kernel<0, 2>, 0, 2); break;
-        case 2: rc = go(adapter_fwd_kernel<0, 3>, 0, 3); break;
-        case 3: rc = go(adapter_fwd_kernel<0, 4>, 0, 4); break;
-        case 4: rc = go(adapter_fwd_kernel<1, 1>, 1, 1); break;
-        case 5: rc = go(adapter_fwd_kernel<1, 2>, 1, 2); break;
-        case 6: rc = go(adapter_fwd_kernel<1, 3>, 1, 3); break;
-        case 7: rc = go(adapter_fwd_kernel<1, 4>, 1, 4); break;
+        case 0: return af_launch_fwd<adapter_fwd_kernel<0, 1>>(a, rb, lds, s);
+        case 1: return af_launch_fwd<adapter_fwd_kernel<0, 2>>(a, rb, lds, s);
+        case 2: return af_launch_fwd<adapter_fwd_kernel<0, 3>>(a, rb, lds, s);
+        case 3: return af_launch_fwd<adapter_fwd_kernel<0, 4>>(a, rb, lds, s);
+        case 4: return af_launch_fwd<adapter_fwd_kernel<1, 1>>(a, rb, lds, s);
+        case 5: return af_launch_fwd<adapter_fwd_kernel<1, 2>>(a, rb, lds, s);
+        case 6: return af_launch_fwd<adapter_fwd_kernel<1, 3>>(a, rb, lds, s);
+        case 7: return af_launch_fwd<adapter_fwd_kernel<1, 4>>(a, rb, lds, s);
     }
-    if (rc) return rc;
-    LAUNCH_OK("adapter_fwd_kernel");
-    return 0;
+    return -1;
 }
 
 // tn_*: the contraction range of the launch (see af_tn_range and AdapterBwdArgs)
@@ -698,17 +687,9 @@ int pevit_launch_adapter_bwd(const AdapterBwdArgs& a, hipStream_t s) {
     // (requests -> LDS -> matrix core -> stores), so more of them in flight beats fewer, longer-lived ones.)
     const int ntn = min(ceil_div(tn.n1 + tn.n2, 2), a.tn_blocks > 0 ? a.tn_blocks : (1 << 30));
     const int lds = ntn ? max(L.total_bwd, 2 * TNH_BYTES) : L.total_bwd;
-    const dim3 grid(nb + ntn), block(64 * AF_WAVES);
-    static bool attr[4][AF_MAXV] = {};
     // dres == nullptr: the bf16 gradient stream (round 5) -- dx_out is read from dyb wherever the f32 copy was
-    auto go = [&](auto kern, int slot, int nv) -> int {
-        if (!attr[slot][nv - 1]) { if (af_attr(kern, 160 * 1024, "adapter_bwd")) return -1; attr[slot][nv - 1] = true; }
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a.dyb, a.dres, a.wuT, a.saved, a.wdT, a.hraw, a.bpr, a.mean_a, a.rstd_a, a.gamma, a.dpre, a.dh_bf16, a.partial, T, E, rb, nb, tn);
-        return 0;
-    };
-    int rc = -1;
     const int slot = 2 * (a.act_kind != 0) + (a.dres ? 0 : 1);
-#define AF_BWD_CASE(A, R, N) case 4 * (2 * A + R) + N - 1: rc = go(adapter_bwd_kernel<A, R != 0, N>, 2 * A + R, N); break;
+#define AF_BWD_CASE(A, R, N) case 4 * (2 * A + R) + N - 1: return af_launch_bwd<adapter_bwd_kernel<A, R != 0, N>>(a, rb, nb, ntn, tn, lds, s);
     switch (4 * slot + E / 256 - 1) {
         AF_BWD_CASE(0, 0, 1) AF_BWD_CASE(0, 0, 2) AF_BWD_CASE(0, 0, 3) AF_BWD_CASE(0, 0, 4)
         AF_BWD_CASE(0, 1, 1) AF_BWD_CASE(0, 1, 2) AF_BWD_CASE(0, 1, 3) AF_BWD_CASE(0, 1, 4)
@@ -716,7 +697,5 @@ int pevit_launch_adapter_bwd(const AdapterBwdArgs& a, hipStream_t s) {
         AF_BWD_CASE(1, 1, 1) AF_BWD_CASE(1, 1, 2) AF_BWD_CASE(1, 1, 3) AF_BWD_CASE(1, 1, 4)
     }
 #undef AF_BWD_CASE
-    if (rc) return rc;
-    LAUNCH_OK("adapter_bwd_kernel");
-    return 0;
+    return -1;
 }

@@ -24,6 +24,7 @@
 // exchange for no cross-wave reductions and no atomics.)
 #include "common.h"
 #include "kernels.h"
+#include "mfma_frag.h"
 
 // LDS tiles are row-major [tokens][LD], in one of two layouts chosen per kernel instance (template parameter LD):
 //   LD = 64: unpadded 128-byte rows, the 16-byte chunks of a row XOR-swizzled by the row (chunk c of row r sits at c ^ ((r >> 1) & 7));
@@ -55,67 +56,12 @@
 // parameter NC; 0 = the runtime argument); the backward kernel does not (-2 % at N = 50, +5 % / +1.5 % at 197 / 257).
 namespace {
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// 16-byte row fragment: row `row` of a row-major [*, stride] bf16 matrix, elements 32*s+8*g..+7
-__device__ __forceinline__ bf16x8 rowfrag(const bf16* base, size_t stride, int row, int s, int g) {
-    return load_bf16x8(base + (size_t)row * stride + 32 * s + 8 * g);
-}
-
-// 16-byte row fragment of an LDS tile (swizzled chunks): row `row`, elements 32*s+8*g..+7
-template <int LD>
-__device__ __forceinline__ int att_swz(int r) { return LD == 64 ? (r >> 1) & 7 : 0; }
-template <int LD>
-__device__ __forceinline__ bf16x8 ldsfrag(const bf16* Ys, int row, int s, int g) {
-    return *reinterpret_cast<const bf16x8*>(Ys + row * LD + 8 * ((4 * s + g) ^ att_swz<LD>(row)));
-}
-// the same from either side: an LDS tile (LDS = true) or a row-major global matrix
+// a 16-byte row fragment (mfma_frag.h) from either side: an LDS tile (LDS = true) or a row-major global matrix
 template <bool LDS, int LD>
 __device__ __forceinline__ bf16x8 xfrag(const bf16* base, size_t stride, int row, int s, int g) {
     if constexpr (LDS) return ldsfrag<LD>(base, row, s, g);
     else return rowfrag(base, stride, row, s, g);
 }
-// 16-byte piece `c` of row `y` of an LDS tile (staging writes)
-template <int LD>
-__device__ __forceinline__ bf16x8* ldschunk(bf16* Ys, int y, int c) {
-    return reinterpret_cast<bf16x8*>(Ys + y * LD + 8 * (c ^ att_swz<LD>(y)));
-}
-
-// Fragment of the TRANSPOSE of a row-major tile Ys[y][LDR] (LDS), output row m -> d = 16*(m>>2) + 4*dt + (m&3), with gfx950's
-// transposing read: in each 16-lane
-// group, lane 4j+q passes the address of 4 consecutive d of token-row j, and lane i receives, as element j, element i&3
-// of the piece addressed by lane 4j + (i>>2) (measured: scripts/probe_tr_b16.hip).  Lane 4j+q therefore points at
-// Ys[32s + 4g + j][16q + 4dt ..+3], and lane m ends up with d = 16*(m>>2) + 4*dt + (m&3) for the tokens 32s+4g+0..3
-// (second read: +16 tokens) -- no transposed copy in LDS, no scattered 2-byte writes.
-template <int LDR>
-__device__ __forceinline__ bf16x8 tfrag_tr(const bf16* Ys, int dt, int s, int lane) {
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-    const int m = lane & 15, g = lane >> 4;
-    const int R = 32 * s + 4 * g + (m >> 2);                     // (row R + 16 has the same swizzle)
-    const bf16* src = Ys + R * LDR + 8 * ((2 * (m & 3) + (dt >> 1)) ^ att_swz<LDR>(R)) + 4 * (dt & 1);
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src + 16 * LDR));
-    bf16x8 o;
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-    o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-    return o;
-}
-
-__device__ __forceinline__ void store16(bf16* dst, const f32x4 o[4], float scale) {
-    bf16x8 a, b;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            a[dt * 4 + r] = f2bf(o[dt][r] * scale);
-            b[dt * 4 + r] = f2bf(o[dt + 2][r] * scale);
-        }
-    store_bf16x8(dst, a);
-    store_bf16x8(dst + 8, b);
-}
-
 // ------------------------------------------------------------------------------------
 template <int KT32, int NW, int LDK, int NC>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
@@ -584,14 +530,9 @@ template <int KT32, int NW, int LD, int NC = 0>
 int launch_fwd(const bf16* q, const bf16* k, const bf16* v, bf16* out, int ldo, float* lse, int B, int H, int N,
                hipStream_t s, unsigned char* out8) {
     constexpr int NPAD = 32 * KT32;
-    const int bytes = 2 * NPAD * LD * 2;
-    static bool attr = false;
-    if (!attr && bytes > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<KT32, NW, LD, NC>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-            pevit_set_error("attn_fwd: cannot reserve %d bytes of LDS", bytes); return -1;
-        }
-        attr = true;
+    constexpr int bytes = 2 * NPAD * LD * 2;
+    if constexpr (bytes > 48 * 1024) {
+        if (reserve_lds<attn_fwd_kernel<KT32, NW, LD, NC>, bytes>("attn_fwd")) return -1;
     }
     hipLaunchKernelGGL((attn_fwd_kernel<KT32, NW, LD, NC>), dim3(B * H), dim3(64 * NW), bytes, s, q, k, v, out, ldo, lse, H, N, out8);
     LAUNCH_OK("attn_fwd_kernel");
@@ -608,13 +549,8 @@ int launch_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* out, int
     const bool coop = !ALL4 && (ntile % NW) == 1 && ntile > NW && KT32 <= NW;
     const int bytes = 2 * NPAD * 4 + (ALL4 ? 4 : 2) * NPAD * LD * 2 + (coop ? KT32 * 64 * 16 * 4 : 0);
     constexpr int bytes_max = 2 * NPAD * 4 + (ALL4 ? 4 : 2) * NPAD * LD * 2 + (ALL4 ? 0 : KT32 * 64 * 16 * 4);   // the LIMIT set once; a launch passes what it uses
-    static bool attr = false;
-    if (!attr && bytes_max > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<KT32, ALL4, NW, LD>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes_max) != hipSuccess) {
-            pevit_set_error("attn_bwd: cannot reserve %d bytes of LDS", bytes_max); return -1;
-        }
-        attr = true;
+    if constexpr (bytes_max > 48 * 1024) {
+        if (reserve_lds<attn_bwd_kernel<KT32, ALL4, NW, LD>, bytes_max>("attn_bwd")) return -1;
     }
     hipLaunchKernelGGL((attn_bwd_kernel<KT32, ALL4, NW, LD>), dim3(B * H), dim3(64 * NW), bytes, s, q, k, v, out, ldo, dout, lddo, lse,
                        dqkv, ld, H, N, ALL4 ? dout_cls : 0);

@@ -16,52 +16,13 @@
 // MFMA order per 16-query tile.
 #include "common.h"
 #include "kernels.h"
+#include "mfma_frag.h"
 
 #ifndef AFD_LDR
 #define AFD_LDR 72          // LDS row stride (elements): 36 dwords, 16-byte aligned rows
 #endif
 
 namespace {
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 ldsfrag(const bf16* base, int row, int s, int g) {
-    return *reinterpret_cast<const bf16x8*>(base + row * AFD_LDR + 32 * s + 8 * g);
-}
-// lowrank.hip split_bf16v: f32 -> bf16 hi + bf16 lo
-__device__ __forceinline__ void split8(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        hi[i] = f2bf(v[i]);
-        lo[i] = f2bf(v[i] - bf2f(hi[i]));
-    }
-}
-// attention.hip tfrag_tr with this file's row stride
-__device__ __forceinline__ bf16x8 tfrag(const bf16* Ys, int dt, int s, int lane) {
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-    const int m = lane & 15, g = lane >> 4;
-    const bf16* src = Ys + (32 * s + 4 * g + (m >> 2)) * AFD_LDR + 16 * (m & 3) + 4 * dt;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src + 16 * AFD_LDR));
-    bf16x8 o;
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-    o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-    return o;
-}
-__device__ __forceinline__ void store16o(bf16* dst, const f32x4 o[4], float scale) {
-    bf16x8 a, b;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            a[dt * 4 + r] = f2bf(o[dt][r] * scale);
-            b[dt * 4 + r] = f2bf(o[dt + 2][r] * scale);
-        }
-    store_bf16x8(dst, a);
-    store_bf16x8(dst + 8, b);
-}
 
 // HPW heads per workgroup, NW waves, PER 32-column delta steps per wave (E / 32 <= PER * NW / 2).  LDS: q, k, v of the run as [(HPW-1)*N + max(N + 16, 64)][AFD_LDR] bf16 each (the rows behind the last
 // head are zero: the 64-row key / value tiles of a head run over into the next head's rows, which are finite and meet
@@ -119,7 +80,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
 #pragma unroll
     for (int kq = 0; kq < 2; ++kq) {
         const int rr = min(rr0 + 16 * kq + c16, T - 1);
-        const int n = rr / B, b = rr - n * B;
+        const int n = rr / B, b = rr - n * B;                   // row_of_ref (mfma_frag.h) in 64-bit: the address arithmetic this kernel was tuned with
         const float* src = t + ((size_t)b * N + n) * 64 + which * 32 + 8 * g;
         ta[kq][0] = *reinterpret_cast<const float4*>(src); ta[kq][1] = *reinterpret_cast<const float4*>(src + 4);
     }
@@ -151,16 +112,16 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
         if (idx < prow * 8) {
             const int y = idx >> 3, c = idx & 7;
             const bool live = idx < npc;
-            *reinterpret_cast<bf16x8*>(Qs + y * LDR + 8 * c) = live ? rq[it] : zero_bf16x8();
-            *reinterpret_cast<bf16x8*>(Vs + y * LDR + 8 * c) = live ? rv[it] : zero_bf16x8();
+            *ldschunk<LDR>(Qs, y, c) = live ? rq[it] : zero_bf16x8();
+            *ldschunk<LDR>(Vs, y, c) = live ? rv[it] : zero_bf16x8();
         }
     }
     // rows [PIECES*NT/8, prow) (only when the pieces do not cover the zero pad)
     for (int idx = tid + NT * PIECES; idx < prow * 8; idx += NT) {
         const int y = idx >> 3, c = idx & 7;
-        *reinterpret_cast<bf16x8*>(Qs + y * LDR + 8 * c) = zero_bf16x8();
-        *reinterpret_cast<bf16x8*>(Ks + y * LDR + 8 * c) = zero_bf16x8();
-        *reinterpret_cast<bf16x8*>(Vs + y * LDR + 8 * c) = zero_bf16x8();
+        *ldschunk<LDR>(Qs, y, c) = zero_bf16x8();
+        *ldschunk<LDR>(Ks, y, c) = zero_bf16x8();
+        *ldschunk<LDR>(Vs, y, c) = zero_bf16x8();
     }
     __syncthreads();
     stamp(2);
@@ -169,8 +130,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
     {
         bf16* Xs = which ? Vs : Qs;
         bf16x8 th[2], tlo[2];
-        split8(ta[0][0], ta[0][1], th[0], tlo[0]);
-        split8(ta[1][0], ta[1][1], th[1], tlo[1]);
+        split_bf16v(ta[0][0], ta[0][1], th[0], tlo[0]);
+        split_bf16v(ta[1][0], ta[1][1], th[1], tlo[1]);
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int st = wq + HW * i;                   // wave-uniform
@@ -212,7 +173,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
         const int idx = tid + NT * it;
         if (idx < prow * 8) {
             const int y = idx >> 3, c = idx & 7;
-            *reinterpret_cast<bf16x8*>(Ks + y * LDR + 8 * c) = idx < npc ? rk[it] : zero_bf16x8();
+            *ldschunk<LDR>(Ks, y, c) = idx < npc ? rk[it] : zero_bf16x8();
         }
     }
     __syncthreads();
@@ -221,8 +182,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
     // ---- q' and v' back to HBM (the backward pass recomputes the scores from them); the stores drain under the attention ----
     for (int idx = tid; idx < npc; idx += NT) {
         const int y = idx >> 3, c = idx & 7;
-        store_bf16x8(q + goff + (size_t)idx * 8, *reinterpret_cast<const bf16x8*>(Qs + y * LDR + 8 * c));
-        store_bf16x8(v + goff + (size_t)idx * 8, *reinterpret_cast<const bf16x8*>(Vs + y * LDR + 8 * c));
+        store_bf16x8(q + goff + (size_t)idx * 8, *ldschunk<LDR>(Qs, y, c));
+        store_bf16x8(v + goff + (size_t)idx * 8, *ldschunk<LDR>(Vs, y, c));
     }
 
     stamp(5);
@@ -236,14 +197,14 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
         const bf16* Vh = Vs + hh * N * LDR;
         const int xq = 16 * xt + c16;
         const int xs = xq < N ? xq : N - 1;
-        const bf16x8 qf0 = ldsfrag(Qh, xs, 0, g), qf1 = ldsfrag(Qh, xs, 1, g);
+        const bf16x8 qf0 = ldsfrag<LDR>(Qh, xs, 0, g), qf1 = ldsfrag<LDR>(Qh, xs, 1, g);
         f32x4 z[4];
         float m = -3.0e38f;
 #pragma unroll
         for (int yt = 0; yt < 4; ++yt) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = mfma16(ldsfrag(Kh, 16 * yt + c16, 0, g), qf0, acc);
-            acc = mfma16(ldsfrag(Kh, 16 * yt + c16, 1, g), qf1, acc);
+            acc = mfma16(ldsfrag<LDR>(Kh, 16 * yt + c16, 0, g), qf0, acc);
+            acc = mfma16(ldsfrag<LDR>(Kh, 16 * yt + c16, 1, g), qf1, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = 16 * yt + 4 * g + r;
@@ -274,10 +235,10 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
         for (int dt = 0; dt < 4; ++dt) {
             o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < 2; ++s) o[dt] = mfma16(tfrag(Vh, dt, s, lane), pf[s], o[dt]);
+            for (int s = 0; s < 2; ++s) o[dt] = mfma16(tfrag_tr<LDR>(Vh, dt, s, lane), pf[s], o[dt]);
         }
         if (xq < N) {
-            store16o(out + ((size_t)b * N + xq) * ldo + h * 64 + 16 * g, o, 1.0f / l);
+            store16(out + ((size_t)b * N + xq) * ldo + h * 64 + 16 * g, o, 1.0f / l);
             if (g == 0) lse[(size_t)bh * N + xq] = m + __logf(l);
         }
     }
@@ -286,6 +247,16 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
 }
 
 unsigned long long* g_timeline = nullptr;
+
+template <int HPW, int NW, int PER, int HC, int NC>
+int launch_fwd_delta(const AttnFwdDeltaArgs& a, int bytes, hipStream_t s) {
+    constexpr auto kern = attn_fwd_delta_kernel<HPW, NW, PER, HC, NC>;
+    if (reserve_lds<kern, 160 * 1024>("attn_fwd_delta")) return -1;
+    hipLaunchKernelGGL(kern, dim3(ceil_div(a.B * a.H, HPW)), dim3(64 * NW), bytes, s, a.q, a.k, a.v, a.t, a.q16, a.bias, a.ascale, a.out, a.ldo,
+                       a.lse, a.B, a.H, a.N, g_timeline);
+    LAUNCH_OK("attn_fwd_delta_kernel");
+    return 0;
+}
 }  // namespace
 
 void pevit_attn_delta_set_timeline(void* buf) { g_timeline = (unsigned long long*)buf; }
@@ -307,19 +278,6 @@ int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s) {
     const int bytes = 3 * ((HPW - 1) * N + (N + 16 > 64 ? N + 16 : 64)) * AFD_LDR * 2;
     static_assert(PER * (NW / 2) * 32 >= 768, "delta steps of the widest supported tower");
     if (bytes > 160 * 1024) { pevit_set_error("attn_fwd_delta: %d bytes of LDS", bytes); return -1; }
-    static bool attr[2] = {false, false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr[slot]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                pevit_set_error("attn_fwd_delta: cannot reserve LDS"); return -1;
-            }
-            attr[slot] = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(ceil_div(B * H, HPW)), dim3(64 * NW), bytes, s, a.q, a.k, a.v, a.t, a.q16, a.bias, a.ascale, a.out, ldo, a.lse, B, H, N, g_timeline);
-        return 0;
-    };
-    const int rc = (H == 12 && N == 50) ? go(attn_fwd_delta_kernel<HPW, NW, PER, 12, 50>, 1) : go(attn_fwd_delta_kernel<HPW, NW, PER, 0, 0>, 0);
-    if (rc) return rc;
-    LAUNCH_OK("attn_fwd_delta_kernel");
-    return 0;
+    if (H == 12 && N == 50) return launch_fwd_delta<HPW, NW, PER, 12, 50>(a, bytes, s);
+    return launch_fwd_delta<HPW, NW, PER, 0, 0>(a, bytes, s);
 }

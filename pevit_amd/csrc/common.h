@@ -38,6 +38,21 @@ extern "C" void pevit_set_error(const char* fmt, ...);
         }                                                                             \
     } while (0)
 
+// Raises the dynamic-LDS limit of one kernel instantiation to BYTES, once: a function-local static, so concurrent first launches
+// (the sweep drives two engine contexts from two threads) are safe, and a failure stays a failure for every later launch.
+template <auto KERN, int BYTES>
+hipError_t lds_limit() {
+    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
+    return e;
+}
+// the same for a launcher: 0, or -1 with the error text set
+template <auto KERN, int BYTES>
+int reserve_lds(const char* who) {
+    const hipError_t e = lds_limit<KERN, BYTES>();
+    if (e != hipSuccess) pevit_set_error("%s: cannot reserve %d bytes of LDS: %s", who, BYTES, hipGetErrorString(e));
+    return e == hipSuccess ? 0 : -1;
+}
+
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 __device__ __forceinline__ bf16 f2bf(float v) { return (bf16)v; }
 

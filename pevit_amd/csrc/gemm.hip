@@ -1857,11 +1857,10 @@ GemmPlan plan_gemm(int epi, const GemmParams& p, const GemmTune& t, int cus) {
 // ---- launchers: a plan onto its kernel instantiation
 const char* const kFamily[] = {"", "tile", "staggered 8-wave", "k-split", "phased k-split", "stream-K", "few rows", "two K slices per tile"};
 
-// The one launch of every family.  The dynamic-LDS limit of an instantiation is raised by its first launch, through a
-// function-local static (thread-safe; a failure stays a failure for every later call).
+// The one launch of every family.  The dynamic-LDS limit of an instantiation is raised by its first launch (lds_limit, common.h).
 template <auto KERN, int LDS, typename... Args>
 int launch_kernel(int epi, const GemmPlan& pl, int block, hipStream_t stream, Args... args) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    const hipError_t attr = lds_limit<KERN, LDS>();
     if (attr == hipSuccess) hipLaunchKernelGGL(KERN, dim3(pl.grid), dim3(block), LDS, stream, args...);
     const hipError_t e = attr != hipSuccess ? attr : hipGetLastError();
     if (e != hipSuccess) {

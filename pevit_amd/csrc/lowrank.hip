@@ -19,13 +19,9 @@
 // Internally rows are batch-major (row = b*N + n), hence row(rr) below.
 #include "common.h"
 #include "kernels.h"
+#include "mfma_frag.h"
 
 namespace {
-
-__device__ __forceinline__ int row_of_ref(int rr, int B, int N) {
-    const int n = rr / B, b = rr - n * B;
-    return b * N + n;
-}
 
 // ---------------------------------------------------------------------------------
 // blockIdx.y = layer: every per-layer pointer advances by a constant stride (LayerStrides)
@@ -104,25 +100,6 @@ __global__ void prep_lora_kernel(const float* __restrict__ a1q, const float* __r
 // forward t = xn P product and Q^T in the backward u = dDelta Q -- and the f32 t as bf16 hi + lo parts: Q*t_lo + Q*t_hi, two
 // MFMAs per 16x16 tile (round 4; before, Q was split as well: three MFMAs and twice the operand bytes, which is what bounds
 // the fused kernel of attn_delta.hip).  f32 verification mode: both operands split, hi*hi + hi*lo + lo*hi (error ~2^-17).
-__device__ __forceinline__ void split_bf16v(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        hi[i] = f2bf(v[i]);
-        lo[i] = f2bf(v[i] - bf2f(hi[i]));
-    }
-}
-__device__ __forceinline__ void split_bf16(const float* src, bf16x8& hi, bf16x8& lo) {
-    const float4 a = *reinterpret_cast<const float4*>(src);
-    const float4 b = *reinterpret_cast<const float4*>(src + 4);
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        hi[i] = f2bf(v[i]);
-        lo[i] = f2bf(v[i] - bf2f(hi[i]));
-    }
-}
-
 // A wave owns DA_RG groups of 16 reference rows and 64 columns of E (two steps of 32 = two 16x16 tiles whose
 // output rows are interleaved, tile 0: e = 8g+r, tile 1: e = 8g+4+r, so that a lane ends up with 8 consecutive e of
 // one row -> one 16-byte read-modify-write); the split Q fragments of a step are loaded once and reused for all
@@ -218,12 +195,12 @@ __global__ __launch_bounds__(256) void delta_add_kernel(bf16* qbuf, bf16* vbuf, 
 #pragma unroll
         for (int k = 0; k < DA_RG; ++k) {
             f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (!Q16) a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0l, th[k], a0, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0h, tl[k], a0, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0h, th[k], a0, 0, 0, 0);
-            if constexpr (!Q16) a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1l, th[k], a1, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1h, tl[k], a1, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1h, th[k], a1, 0, 0, 0);
+            if constexpr (!Q16) a0 = mfma16(q0l, th[k], a0);
+            a0 = mfma16(q0h, tl[k], a0);
+            a0 = mfma16(q0h, th[k], a0);
+            if constexpr (!Q16) a1 = mfma16(q1l, th[k], a1);
+            a1 = mfma16(q1h, tl[k], a1);
+            a1 = mfma16(q1h, th[k], a1);
             // lane: column rr, rows 4g+r of each tile -> e = eb + 8g + r (tile 0), eb + 8g + 4 + r (tile 1)
             float o[8];
 #pragma unroll
@@ -239,15 +216,6 @@ __global__ __launch_bounds__(256) void delta_add_kernel(bf16* qbuf, bf16* vbuf, 
 }
 
 // ---------------------------------------------------------------------------------
-// address of the 64-element head row that holds flat elements [rr*E + e0, +64) of dDelta
-__device__ __forceinline__ const bf16* ddelta_slab(const bf16* dqkv, int ld, int col0, int rr, int e0, int E,
-                                                   int H, int N) {
-    const int c = (int)(((long long)rr * E + e0) >> 6);
-    const int bh = c / N, n = c - bh * N;
-    const int b = bh / H, h = bh - b * H;
-    return dqkv + ((size_t)b * N + n) * ld + col0 + h * 64;
-}
-
 // u = dDelta . Q : block = 16*LU_RG reference rows, the LU_WAVES waves split E (contraction); LDS reduction.
 // Every wave requests all of its dDelta fragments (HBM) up front; each Q fragment (L2) is used by LU_RG row groups.
 #ifndef LU_RG
@@ -299,8 +267,8 @@ __device__ __forceinline__ void lowrank_u_body(float* red_raw, int blk, const bf
                     const bf16x8 bv = load_bf16x8(qT + (size_t)(32 + 16 * nt + c16) * E + ke);
 #pragma unroll
                     for (int k = 0; k < RG; ++k) {
-                        acc[k][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[i][k], bq, acc[k][nt], 0, 0, 0);
-                        acc[k][2 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i][k], bv, acc[k][2 + nt], 0, 0, 0);
+                        acc[k][nt] = mfma16(aq[i][k], bq, acc[k][nt]);
+                        acc[k][2 + nt] = mfma16(av[i][k], bv, acc[k][2 + nt]);
                     }
                 }
             }
@@ -359,18 +327,6 @@ __global__ __launch_bounds__(64 * LU_WAVES) void lowrank_u_kernel(const bf16* __
 #endif
 constexpr int LG_ROWS = 256;
 constexpr int LG_LD = 72;          // row stride (elements) of the LDS tiles: 36 dwords, 8 consecutive rows cover all banks
-
-__device__ __forceinline__ bf16x8 lg_trfrag(const bf16* tile, int ks, int col0, int lane) {
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-    const int m = lane & 15, g = lane >> 4;
-    const bf16* src = tile + (32 * ks + 4 * g + (m >> 2)) * LG_LD + col0 + 4 * (m & 3);
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(src + 16 * LG_LD));
-    bf16x8 o;
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-    o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-    return o;
-}
 
 // LDS of the body: Xs, Ys (LG_ROWS x LG_LD bf16 each) + 4 x 64 floats
 constexpr int LG_LDS_BYTES = 2 * LG_ROWS * LG_LD * 2 + 4 * 64 * 4;
@@ -449,7 +405,7 @@ __device__ __forceinline__ void lowrank_grad_body(char* smem, int bid, int kind_
     for (int ks = 0; ks < LG_ROWS / 32; ++ks)
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
-            bfr[ks][nt] = (nt < NT) ? lg_trfrag(Ys, ks, 16 * nt, lane) : zero_bf16x8();
+            bfr[ks][nt] = (nt < NT) ? trfrag<LG_LD>(Ys, ks, 16 * nt, lane) : zero_bf16x8();
 
     const size_t plane = (size_t)E * 32;
     float* base = partial + ((size_t)chunk * 4 + (kind == 0 ? 0 : kind + 1)) * plane;
@@ -470,8 +426,7 @@ __device__ __forceinline__ void lowrank_grad_body(char* smem, int bid, int kind_
         if (kind != 0) {     // column sums: reduce over the 8 row-lanes of this wave, then over waves
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                float a = colsum[i];
-                a += __shfl_xor(a, 8, 64); a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
+                const float a = rowlane_sum(colsum[i]);
                 if ((lane >> 3) == 0) cs[wid][8 * c + i] = a;
             }
         }
@@ -483,10 +438,10 @@ __device__ __forceinline__ void lowrank_grad_body(char* smem, int bid, int kind_
         for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < LG_ROWS / 32; ++ks) {
-            const bf16x8 a = lg_trfrag(Xs, ks, 16 * wid, lane);
+            const bf16x8 a = trfrag<LG_LD>(Xs, ks, 16 * wid, lane);
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
-                if (nt < NT) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[ks][nt], acc[nt], 0, 0, 0);
+                if (nt < NT) acc[nt] = mfma16(a, bfr[ks][nt], acc[nt]);
         }
         // the next slab's X panel (requested above) is in before this slab's stores go out: the compiler then knows that no load
         // is pending behind them and does not wait for the STORES when the panel is used (vmcnt counts both on gfx950)

@@ -105,13 +105,7 @@ __global__ __launch_bounds__(256) void occupy_kernel(unsigned long long ticks, u
 
 int pevit_launch_occupy(int blocks, int lds_bytes, double micros, hipStream_t s) {
     if (blocks <= 0) return 0;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(occupy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            pevit_set_error("occupy: cannot raise the LDS limit"); return -1;
-        }
-        attr = true;
-    }
+    if (reserve_lds<occupy_kernel, 160 * 1024>("occupy")) return -1;
     hipLaunchKernelGGL(occupy_kernel, dim3(blocks), dim3(256), (size_t)lds_bytes, s, (unsigned long long)(micros * 100.0), (unsigned*)nullptr);
     LAUNCH_OK("occupy_kernel");
     return 0;

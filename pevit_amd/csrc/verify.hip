@@ -15,6 +15,7 @@
 // softmax statistics, and the token-contracted low-rank adapter products.  All sums run in a fixed order (deterministic).
 #include "common.h"
 #include "kernels.h"
+#include "mfma_frag.h"
 #include "gemm_epilogue.h"
 
 namespace {
@@ -195,16 +196,6 @@ __global__ __launch_bounds__(256) void attn_bwd_f32_kernel(const float* __restri
 
 // ---------------------------------------------------------------------------------------------------------------
 // low-rank adapter products (lowrank.hip states the math and the flat addressing)
-__device__ __forceinline__ int vrow_of_ref(int rr, int B, int N) {
-    const int n = rr / B, b = rr - n * B;
-    return b * N + n;
-}
-__device__ __forceinline__ const float* vslab(const float* dqkv, int ld, int col0, int rr, int e0, int E, int H, int N) {
-    const int c = (int)(((long long)rr * E + e0) >> 6);
-    const int bh = c / N, n = c - bh * N;
-    const int b = bh / H, h = bh - b * H;
-    return dqkv + ((size_t)b * N + n) * ld + col0 + h * 64;
-}
 
 // u[row(rr)][j] = sum_e dDelta_{q|v}[rr][e] Q32[e][j]    thread = (rr, j)
 __global__ void lowrank_u_f32_kernel(const float* __restrict__ dqkv, int ld, const float* __restrict__ q32, float* __restrict__ u32,
@@ -216,10 +207,10 @@ __global__ void lowrank_u_f32_kernel(const float* __restrict__ dqkv, int ld, con
     const int col0 = j < 32 ? 0 : 2 * E;
     float s = 0.f;
     for (int e0 = 0; e0 < E; e0 += 64) {
-        const float* slab = vslab(dqkv, ld, col0, rr, e0, E, H, N);
+        const float* slab = ddelta_slab(dqkv, ld, col0, rr, e0, E, H, N);
         for (int d = 0; d < 64; ++d) s = fmaf(slab[d], q32[(size_t)(e0 + d) * 64 + j], s);
     }
-    const int row = vrow_of_ref(rr, B, N);
+    const int row = row_of_ref(rr, B, N);
     u32[(size_t)row * 64 + j] = s;
     ucols[(size_t)row * ld + j] = s;
 }
@@ -249,12 +240,12 @@ __global__ __launch_bounds__(256) void lowrank_grad_f32_kernel(const float* __re
             const int d = o >> 5, j = o & 31;
             float s = 0.f;
             for (int rr = r0; rr < r1; ++rr)
-                s = fmaf(vslab(dqkv, ld, col0, rr, e0, E, H, N)[d], t[(size_t)vrow_of_ref(rr, B, N) * 64 + toff + j], s);
+                s = fmaf(ddelta_slab(dqkv, ld, col0, rr, e0, E, H, N)[d], t[(size_t)row_of_ref(rr, B, N) * 64 + toff + j], s);
             partial[((size_t)chunk * 4 + kind + 1) * plane + (size_t)(e0 + d) * 32 + j] = s;
         }
         if (tid < 64) {
             float s = 0.f;
-            for (int rr = r0; rr < r1; ++rr) s += vslab(dqkv, ld, col0, rr, e0, E, H, N)[tid];
+            for (int rr = r0; rr < r1; ++rr) s += ddelta_slab(dqkv, ld, col0, rr, e0, E, H, N)[tid];
             dbias_partial[((size_t)chunk * 2 + (kind - 1)) * E + e0 + tid] = s;
         }
     }
