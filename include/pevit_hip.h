@@ -16,6 +16,8 @@
  *                                           (resblocks[i].attn), incl. the head-averaged / per-head weights
  *   pevit_visual_forward / _backward        VisionTransformer.forward      model.py:1034-1051
  *                                           (= CLIP.encode_image, model.py:1151-1152)
+ *   pevit_predict                           Classifier.forward in eval mode (validate's model(images)): images -> logits
+ *                                           kadaptation_clip.py:176-185, 395
  *   pevit_head_forward_backward             Classifier.forward tail + CrossEntropyLoss
  *                                           kadaptation_clip.py:128-132,176-185,276,351-352
  *   pevit_sgd_step                          optimizer.step()               kadaptation_clip.py:353,
@@ -180,6 +182,17 @@ int pevit_visual_forward_u8(pevit_ctx* ctx, void* stream, const uint8_t* images,
 int pevit_train_forward_backward_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const int64_t* labels,
                                     float* running_mean, float* running_var, int bn_training, float* logits,
                                     float* loss, int batch);
+/* ---- evaluation: images (B,3,R,R) -> logits (B x C) in one call.  stem -> blocks -> ln_post -> proj -> BatchNorm1d(affine=False) in
+ * EVAL mode on the caller's running statistics -> Linear.  The tower runs its inference forms: the kernels of pevit_visual_forward
+ * with every store left out that only a backward pass reads (q' / v', log-sum-exp, the MLP pre-activation, LayerNorm statistics) and
+ * one set of activation slots for all layers; features and logits are bit-identical to pevit_visual_forward(save_for_backward = 0)
+ * followed by pevit_head_forward_backward(labels = NULL, bn_training = 0).  Reads the parameters and the running statistics; writes
+ * logits, feat_or_null (B x D) and workspace scratch only -- not the gradient buffer, not the loss slot.  Like every forward it
+ * leaves no saved forward behind: a backward issued afterwards is refused.  batch in [1, max_batch] of the bound workspace. */
+int pevit_predict(pevit_ctx* ctx, void* stream, const float* images, const float* running_mean, const float* running_var,
+                  float* logits, float* feat_or_null, int batch);
+int pevit_predict_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const float* running_mean, const float* running_var,
+                     float* logits, float* feat_or_null, int batch);   /* needs pevit_set_input_norm */
 /* whole fine-tune step: zero_grad -> forward -> CE -> backward -> (caller all-reduces) -> SGD */
 int pevit_train_forward_backward(pevit_ctx* ctx, void* stream, const float* images, const int64_t* labels,
                                  float* running_mean, float* running_var, int bn_training, float* logits,
@@ -250,6 +263,7 @@ int pevit_op_ln_bwd(void* stream, const float* dy, const float* x, const float* 
 int pevit_op_ln_bwd_scaled(void* stream, const float* dy, const float* x, const float* mean, const float* rstd,
                            const float* gamma, const float* dres, float* dx, void* dx_bf16, int rows, int E,
                            const float* bf16_colscale);
+/* lse == NULL: the inference instance, which does not store the log-sum-exp (same out) */
 int pevit_op_attn_fwd(void* stream, const void* q, const void* k, const void* v, void* out, int ldo, float* lse,
                       int B, int H, int N);
 int pevit_op_attn_bwd(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
@@ -260,7 +274,8 @@ int pevit_op_delta_add(void* stream, void* qbuf, void* vbuf, const float* t, con
                        float ascale, int B, int N, int E);
 /* delta_add + attn_fwd as ONE launch (attn_delta.hip) for geometries where pevit_op_attn_delta_hpw(B, H, N) > 0 (runs of that
  * many heads own whole reference rows of the raw reshape, model.py:796-799; N <= 64): q and v are rewritten with q + delta,
- * v + delta; bit-identical to pevit_op_delta_add followed by pevit_op_attn_fwd */
+ * v + delta; bit-identical to pevit_op_delta_add followed by pevit_op_attn_fwd.  lse == NULL: the inference instance -- q and v are
+ * only read (q + delta, v + delta never leave the chip), no lse; the same out */
 int pevit_op_attn_fwd_delta(void* stream, void* q, const void* k, void* v, const float* t, const void* q16_bf16, const float* bias,
                             float ascale, void* out, int ldo, float* lse, int B, int H, int N);
 int pevit_op_attn_delta_hpw(int B, int H, int N);

@@ -54,6 +54,8 @@ SIGNATURES = {
     "pevit_visual_backward_part": (c_int, [P, P, P, c_int, c_int, c_int]),
     "pevit_param_layer_offset": (c_size_t, [P, c_int]),
     "pevit_head_forward_backward": (c_int, [P, P, P, P, P, P, c_int, P, P, P, c_int]),
+    "pevit_predict": (c_int, [P, P, P, P, P, P, P, c_int]),
+    "pevit_predict_u8": (c_int, [P, P, P, P, P, P, P, c_int]),
     "pevit_zero_grads": (c_int, [P, P]),
     "pevit_sgd_step": (c_int, [P, P, c_float, c_float, c_float, c_float, c_int]),
     "pevit_train_forward_backward": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),

@@ -63,7 +63,8 @@ __device__ __forceinline__ bf16x8 xfrag(const bf16* base, size_t stride, int row
     else return rowfrag(base, stride, row, s, g);
 }
 // ------------------------------------------------------------------------------------
-template <int KT32, int NW, int LDK, int NC>
+// LSE = false: the inference form -- the same `out`, the log-sum-exp (read by the backward pass and attn_probs only) is not stored
+template <int KT32, int NW, int LDK, int NC, bool LSE = true>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                                                        const bf16* __restrict__ v, bf16* __restrict__ out, int ldo,
                                                        float* __restrict__ lse, int H, int N_rt, unsigned char* __restrict__ out8) {
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const bf16* __restric
                 store8_fp8(rb, h * 64 + 16 * g, lo8);
                 store8_fp8(rb, h * 64 + 16 * g + 8, hi8);
             }
-            if (g == 0) lse[(size_t)bh * N + xq] = m + __logf(l);
+            if constexpr (LSE) { if (g == 0) lse[(size_t)bh * N + xq] = m + __logf(l); }
         }
     }
 }
@@ -526,15 +527,19 @@ __global__ __launch_bounds__(64 * NW, (ALL4 ? ATT_BWD_MINW : 1)) void attn_bwd_k
     }
 }
 
-template <int KT32, int NW, int LD, int NC = 0>
+// lse == nullptr: the instance without the log-sum-exp store (no backward pass and no attn_probs will ask for it)
+template <int KT32, int NW, int LD, int NC = 0, bool LSE = true>
 int launch_fwd(const bf16* q, const bf16* k, const bf16* v, bf16* out, int ldo, float* lse, int B, int H, int N,
                hipStream_t s, unsigned char* out8) {
+    if constexpr (LSE) {
+        if (!lse) return launch_fwd<KT32, NW, LD, NC, false>(q, k, v, out, ldo, lse, B, H, N, s, out8);
+    }
     constexpr int NPAD = 32 * KT32;
     constexpr int bytes = 2 * NPAD * LD * 2;
     if constexpr (bytes > 48 * 1024) {
-        if (reserve_lds<attn_fwd_kernel<KT32, NW, LD, NC>, bytes>("attn_fwd")) return -1;
+        if (reserve_lds<attn_fwd_kernel<KT32, NW, LD, NC, LSE>, bytes>("attn_fwd")) return -1;
     }
-    hipLaunchKernelGGL((attn_fwd_kernel<KT32, NW, LD, NC>), dim3(B * H), dim3(64 * NW), bytes, s, q, k, v, out, ldo, lse, H, N, out8);
+    hipLaunchKernelGGL((attn_fwd_kernel<KT32, NW, LD, NC, LSE>), dim3(B * H), dim3(64 * NW), bytes, s, q, k, v, out, ldo, lse, H, N, out8);
     LAUNCH_OK("attn_fwd_kernel");
     return 0;
 }

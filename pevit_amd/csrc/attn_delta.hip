@@ -29,7 +29,8 @@ namespace {
 // probabilities that are exactly 0).
 // HC, NC: heads and tokens per image as compile-time constants (0 = the runtime arguments).  Round 5: 20.5 -> 19.7 us at H = 12,
 // N = 50 (scripts/experiments/gpu_r5_fixn.sh) -- bounds, row strides and the head / row arithmetic fold.
-template <int HPW, int NW, int PER, int HC, int NC>
+// SAVE = false: the inference form -- q' and v' stay in LDS and lse is not stored (q and v are only read); the same `out`.
+template <int HPW, int NW, int PER, int HC, int NC, bool SAVE = true>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restrict__ q, const bf16* __restrict__ k, bf16* __restrict__ v,
                                                                  const float* __restrict__ t, const bf16* __restrict__ q16,
                                                                  const float* __restrict__ bias, float ascale,
@@ -180,10 +181,12 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
     stamp(4);
 
     // ---- q' and v' back to HBM (the backward pass recomputes the scores from them); the stores drain under the attention ----
-    for (int idx = tid; idx < npc; idx += NT) {
-        const int y = idx >> 3, c = idx & 7;
-        store_bf16x8(q + goff + (size_t)idx * 8, *ldschunk<LDR>(Qs, y, c));
-        store_bf16x8(v + goff + (size_t)idx * 8, *ldschunk<LDR>(Vs, y, c));
+    if constexpr (SAVE) {
+        for (int idx = tid; idx < npc; idx += NT) {
+            const int y = idx >> 3, c = idx & 7;
+            store_bf16x8(q + goff + (size_t)idx * 8, *ldschunk<LDR>(Qs, y, c));
+            store_bf16x8(v + goff + (size_t)idx * 8, *ldschunk<LDR>(Vs, y, c));
+        }
     }
 
     stamp(5);
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
         }
         if (xq < N) {
             store16(out + ((size_t)b * N + xq) * ldo + h * 64 + 16 * g, o, 1.0f / l);
-            if (g == 0) lse[(size_t)bh * N + xq] = m + __logf(l);
+            if constexpr (SAVE) { if (g == 0) lse[(size_t)bh * N + xq] = m + __logf(l); }
         }
     }
     stamp(6);
@@ -248,9 +251,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
 
 unsigned long long* g_timeline = nullptr;
 
-template <int HPW, int NW, int PER, int HC, int NC>
+template <int HPW, int NW, int PER, int HC, int NC, bool SAVE = true>
 int launch_fwd_delta(const AttnFwdDeltaArgs& a, int bytes, hipStream_t s) {
-    constexpr auto kern = attn_fwd_delta_kernel<HPW, NW, PER, HC, NC>;
+    constexpr auto kern = attn_fwd_delta_kernel<HPW, NW, PER, HC, NC, SAVE>;
     if (reserve_lds<kern, 160 * 1024>("attn_fwd_delta")) return -1;
     hipLaunchKernelGGL(kern, dim3(ceil_div(a.B * a.H, HPW)), dim3(64 * NW), bytes, s, a.q, a.k, a.v, a.t, a.q16, a.bias, a.ascale, a.out, a.ldo,
                        a.lse, a.B, a.H, a.N, g_timeline);
@@ -278,6 +281,7 @@ int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s) {
     const int bytes = 3 * ((HPW - 1) * N + (N + 16 > 64 ? N + 16 : 64)) * AFD_LDR * 2;
     static_assert(PER * (NW / 2) * 32 >= 768, "delta steps of the widest supported tower");
     if (bytes > 160 * 1024) { pevit_set_error("attn_fwd_delta: %d bytes of LDS", bytes); return -1; }
-    if (H == 12 && N == 50) return launch_fwd_delta<HPW, NW, PER, 12, 50>(a, bytes, s);
-    return launch_fwd_delta<HPW, NW, PER, 0, 0>(a, bytes, s);
+    if (!a.nosave && !a.lse) { pevit_set_error("attn_fwd_delta: lse is null (only the nosave form takes that)"); return -1; }
+    if (H == 12 && N == 50) return a.nosave ? launch_fwd_delta<HPW, NW, PER, 12, 50, false>(a, bytes, s) : launch_fwd_delta<HPW, NW, PER, 12, 50>(a, bytes, s);
+    return a.nosave ? launch_fwd_delta<HPW, NW, PER, 0, 0, false>(a, bytes, s) : launch_fwd_delta<HPW, NW, PER, 0, 0>(a, bytes, s);
 }

@@ -79,6 +79,7 @@ struct StepPlan {
     bool dx_stored = false;      // dX GEMMs hand the LN-input gradient to LayerNorm backward in the storage type
     bool lowrank_combo = false;  // u + dQ + d bias of a layer and the dP of the layer before it as one launch
     bool lowrank_xcd = false;    // lowrank_grad: XCD-contiguous workgroup order
+    bool infer = false;          // inference walk (pevit_predict): the kernel forms that store nothing for a backward pass, one set of activation slots for all layers
 };
 
 // which forward the saved activations belong to
@@ -163,8 +164,9 @@ inline bool post_mlp(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER |
 inline int act_kind(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER ? 0 : 1; }
 
 // the launch paths of a step of batch B: a pure function of the context's dims, weight format and knobs, the batch and the CU count
-StepPlan plan_step(const pevit_ctx* c, int B) {
+StepPlan plan_step(const pevit_ctx* c, int B, bool infer = false) {
     StepPlan p;
+    p.infer = infer;
     p.site = attention_site(c);
     p.post_mlp = post_mlp(c);
     p.cls_prune = !p.post_mlp;
@@ -189,7 +191,10 @@ StepPlan plan_step(const pevit_ctx* c, int B) {
     return p;
 }
 
-WsLayout layout_workspace(const pevit_ctx* c, int B) {
+// infer: the layout of the inference walk -- no layer keeps anything, so ONE set of activation slots serves every layer and the f32
+// residual stream alternates between two input buffers (+ x_mid + w_xfinal: four [T][E] buffers whatever the layer count); the
+// pre-activation h and the LayerNorm statistics have no slot at all.  Never larger than the training layout of the same batch.
+WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer = false) {
     Carver cv;
     const size_t T = (size_t)B * c->N, E = c->E, es = c->es;
     WsLayout w{};
@@ -197,22 +202,32 @@ WsLayout layout_workspace(const pevit_ctx* c, int B) {
     w.w_skflag = cv.take((size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4);     // + error word + skipped-update counter
     w.w_skslab = cv.take((size_t)c->sk_slots * PEVIT_SK_SLAB_FLOATS * 4);
     w.sav.resize(c->L);
-    for (LayerSaved& s : w.sav) {
-        s = LayerSaved{};
+    auto carve_layer = [&]() {
+        LayerSaved s{};
         s.x_in = cv.take(T * E * 4);
         s.x_mid = cv.take(T * E * 4);
-        s.mean1 = cv.take(T * 4); s.rstd1 = cv.take(T * 4);
-        s.mean2 = cv.take(T * 4); s.rstd2 = cv.take(T * 4);
+        if (!infer) {
+            s.mean1 = cv.take(T * 4); s.rstd1 = cv.take(T * 4);
+            s.mean2 = cv.take(T * 4); s.rstd2 = cv.take(T * 4);
+        }
         s.xn1 = cv.take(T * E * es);
         s.qkv = cv.take(3 * T * E * es);
         s.t = cv.take(T * 64 * 4);
         s.lse = cv.take((size_t)B * c->H * c->N * 4);
         s.attn_out = cv.take(T * E * es);
-        s.h = cv.take(T * 4 * E * es);
+        if (!infer) s.h = cv.take(T * 4 * E * es);
         if (post_mlp(c)) {
             s.hf32 = cv.take(T * E * 4); s.mean_a = cv.take(T * 4); s.rstd_a = cv.take(T * 4);
             s.z = cv.take(T * E * es); s.apre = cv.take(T * 64 * es); s.act = cv.take(T * 64 * es);
         }
+        return s;
+    };
+    if (infer) {
+        const LayerSaved s0 = carve_layer();
+        const size_t x_alt = cv.take(T * E * 4);
+        for (int l = 0; l < c->L; ++l) { w.sav[l] = s0; if (l & 1) w.sav[l].x_in = x_alt; }
+    } else {
+        for (LayerSaved& s : w.sav) s = carve_layer();
     }
     const int chunks = pevit_lowrank_chunks((int)T);
     w.w_xfinal = cv.take(T * E * 4);
@@ -666,6 +681,8 @@ AttnArgs attn_args(const pevit_ctx* c, int B, int l) {
 // The attention half of block l between ln_1 and out_proj (MultiheadAttention.forward, model.py:612-812): the QKV product with the
 // adapter columns t of the attention-site methods, delta-add and the attention core.  Reads the layer's xn1 (or its e4m3 copy a8),
 // leaves q / k / v in the head layout, lse and attn_out in the layer's saved slots.  Shared by the block walk and the attention seam.
+// Inference walk (pl.infer): the forms without the q' / v' write-back and without lse (f32 verification mode: the saving kernels, on
+// the shared slots).
 int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, unsigned char* a8, unsigned char* attn8) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
     char* W = c->ws; char* A = c->arena;
@@ -705,7 +722,9 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
         AttnFwdDeltaArgs a;
         a.q = qkv; a.k = qkv + plane; a.v = qkv + 2 * plane; a.t = at<float>(W, v.t); a.q16 = at<bf16>(A, b.q16); a.bias = dbias;
         a.ascale = c->ascale; a.out = at<bf16>(W, v.attn_out); a.ldo = E; a.lse = at<float>(W, v.lse); a.B = B; a.H = H; a.N = N;
-        PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T, (double)T * E * (3 + 2 + 1) * 2 + (double)T * 64 * 4 + (double)B * H * N * 4,   // q, k, v in; q', v', out
+        if (pl.infer) { a.nosave = 1; a.lse = nullptr; }
+        PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T,       // q, k, v in; q', v', out (inference: out only) and lse
+             (double)T * E * (3 + (pl.infer ? 0 : 2) + 1) * 2 + (double)T * 64 * 4 + (pl.infer ? 0.0 : (double)B * H * N * 4),
              pevit_launch_attn_fwd_delta(a, s));
     } else {
         if (site) {
@@ -717,10 +736,12 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
         }
         AttnArgs a = attn_args(c, B, l);
         a.out_fp8 = attn8;
-        if (c->f32)
+        if (c->f32) {
             CHECK(pevit_launch_attn_fwd_f32(a, s));
-        else
-            PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2 + (double)B * H * N * 4, pevit_launch_attn_fwd(a, s));
+        } else {
+            if (pl.infer) a.lse = nullptr;
+            PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2 + (pl.infer ? 0.0 : (double)B * H * N * 4), pevit_launch_attn_fwd(a, s));
+        }
     }
     return 0;
 }
@@ -731,6 +752,9 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
 // model.py:1046) -- everything of the last block that sits after the attention core is then
 // evaluated on the B class-token rows only (identical results, ~6 % fewer FLOPs per step).  Never with post-MLP adapters
 // (StepPlan::cls_prune).
+// Inference walk (pl.infer; the layout must be layout_workspace(.., infer = true)): the same launches in the same order with the
+// LayerNorm statistics, lse, q' / v' and the MLP pre-activation h not written; bit-identical x_final.  The post-MLP adapter kernels
+// keep writing z / act / apre / mean_a / rstd_a -- into the slots all layers share.
 int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool cls_only, int l_lo = 0, int l_hi = -1) {
     if (l_hi < 0) l_hi = c->L;
     const int E = c->E, T = B * c->N, N = c->N;
@@ -748,7 +772,8 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
         {
             LnFwdArgs a;
             a.x = x_in; a.gamma = at<float>(A, b.ln1w); a.beta = at<float>(A, b.ln1b); a.rows = T; a.E = E; a.y_bf16 = at<bf16>(W, v.xn1);
-            a.mean = at<float>(W, v.mean1); a.rstd = at<float>(W, v.rstd1); a.f32 = c->f32; a.y_fp8 = a8;
+            if (!pl.infer) { a.mean = at<float>(W, v.mean1); a.rstd = at<float>(W, v.rstd1); }
+            a.f32 = c->f32; a.y_fp8 = a8;
             PROF(c, s, PEVIT_PROF_LN_FWD, T, (double)T * E * (4 + c->es), pevit_launch_ln_fwd(a, s));
         }
         CHECK(attn_core_fwd(c, s, B, pl, l, a8, attn8));
@@ -767,15 +792,16 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
         {
             LnFwdArgs a;
             a.x = x_mid; a.gamma = at<float>(A, b.ln2w); a.beta = at<float>(A, b.ln2b); a.rows = R; a.E = E; a.y_bf16 = at<bf16>(W, c->lay.w_xn2);
-            a.mean = at<float>(W, v.mean2); a.rstd = at<float>(W, v.rstd2); a.xstride = (size_t)rs; a.f32 = c->f32; a.y_fp8 = a8;
+            if (!pl.infer) { a.mean = at<float>(W, v.mean2); a.rstd = at<float>(W, v.rstd2); }
+            a.xstride = (size_t)rs; a.f32 = c->f32; a.y_fp8 = a8;
             PROF(c, s, PEVIT_PROF_LN_FWD, R, (double)R * E * (4 + c->es), pevit_launch_ln_fwd(a, s));
         }
         {
             GemmParams p = gpw(c, at<bf16>(W, c->lay.w_xn2), E, b.wfc, E, 4 * E, R, 4 * E, E, b.sfc);
             if (a8) { p.A = reinterpret_cast<const bf16*>(a8); p.a_fp8 = 1; p.out2_fp8 = 1; }     // gelu(h) leaves as e4m3 codes
-            p.bias = at<float>(A, b.bfc); p.outb = at<bf16>(W, v.h); p.ldob = 4 * E; p.outb2 = at<bf16>(W, c->lay.w_g);
-            p.ldob2 = 4 * E;
-            CHECK(gemm(c, EPI_BIAS_GELU, p, s));
+            p.bias = at<float>(A, b.bfc); p.outb2 = at<bf16>(W, c->lay.w_g); p.ldob2 = 4 * E;
+            if (!pl.infer) { p.outb = at<bf16>(W, v.h); p.ldob = 4 * E; }
+            CHECK(gemm(c, pl.infer ? EPI_BIAS_GELU_ONLY : EPI_BIAS_GELU, p, s));
         }
         if (!pl.post_mlp) {
             GemmParams p = gpw(c, at<bf16>(W, c->lay.w_g), 4 * E, b.wpr, 4 * E, E, R, E, 4 * E, b.spr);
@@ -810,7 +836,8 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
         {
             LnFwdArgs a;
             a.x = at<float>(W, v.hf32); a.gamma = lp + c->o_nw; a.beta = lp + c->o_nb; a.rows = T; a.E = E; a.y_bf16 = at<bf16>(W, v.z);
-            a.mean = at<float>(W, v.mean_a); a.rstd = at<float>(W, v.rstd_a); a.f32 = c->f32;
+            if (!pl.infer) { a.mean = at<float>(W, v.mean_a); a.rstd = at<float>(W, v.rstd_a); }
+            a.f32 = c->f32;
             CHECK(pevit_launch_ln_fwd(a, s));
         }
         {
@@ -1329,7 +1356,8 @@ extern "C" int pevit_set_input_norm(pevit_ctx* c, const float* mean3, const floa
 }
 
 // images (B,3,R,R) f32 -> feat (B,D) f32                               model.py:1034-1051
-static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_any, int u8, float* feat, int B, int save_for_backward);
+static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_any, int u8, float* feat, int B, int save_for_backward,
+                               bool infer = false);
 extern "C" int pevit_visual_forward(pevit_ctx* c, void* stream, const float* images, float* feat, int B,
                                     int save_for_backward) {
     return visual_forward_impl(c, stream, images, 0, feat, B, save_for_backward);
@@ -1340,12 +1368,16 @@ extern "C" int pevit_visual_forward_u8(pevit_ctx* c, void* stream, const uint8_t
     if (c && !c->img_norm_set) { pevit_set_error("visual_forward_u8: call pevit_set_input_norm first"); return -1; }
     return visual_forward_impl(c, stream, images, 1, feat, B, save_for_backward);
 }
-static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_any, int u8, float* feat, int B, int save_for_backward) {
+// infer (pevit_predict): the inference layout and kernel forms; what a previous forward saved is overwritten, so no backward may follow
+static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_any, int u8, float* feat, int B, int save_for_backward,
+                               bool infer) {
     const float* images = (const float*)images_any;
-    CHECK(check_ready(c, B, "visual_forward"));
+    CHECK(check_ready(c, B, infer ? "predict" : "visual_forward"));
     hipStream_t s = (hipStream_t)stream;
-    c->lay = layout_workspace(c, B);
-    const StepPlan pl = plan_step(c, B);
+    if (infer) c->saved = SavedForward{};
+    c->lay = layout_workspace(c, B, infer);
+    if (infer && c->lay.total > c->ws_bytes_for_max) { pevit_set_error("predict: workspace too small (%zu < %zu)", c->ws_bytes_for_max, c->lay.total); return -1; }
+    const StepPlan pl = plan_step(c, B, infer);
     char* W = c->ws; char* A = c->arena;
     const int E = c->E, N = c->N, T = B * N;
     float* xpre = at<float>(W, c->lay.w_dxn);               // scratch, free during the forward pass
@@ -1379,7 +1411,8 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
     {
         LnFwdArgs a;
         a.x = at<float>(W, c->lay.w_xfinal); a.gamma = at<float>(A, c->a_lnpost_w); a.beta = at<float>(A, c->a_lnpost_b); a.rows = B; a.E = E;
-        a.y_bf16 = at<bf16>(W, c->lay.w_xpost); a.mean = at<float>(W, c->lay.w_pmean); a.rstd = at<float>(W, c->lay.w_prstd);
+        a.y_bf16 = at<bf16>(W, c->lay.w_xpost);
+        if (!infer) { a.mean = at<float>(W, c->lay.w_pmean); a.rstd = at<float>(W, c->lay.w_prstd); }
         a.xstride = (size_t)N * E; a.f32 = c->f32;
         CHECK(pevit_launch_ln_fwd(a, s));
     }
@@ -1388,8 +1421,37 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
         p.outf = feat ? feat : at<float>(W, c->lay.w_feat); p.ldo = c->D;
         CHECK(gemm(c, EPI_F32, p, s));
     }
-    c->saved = SavedForward{Saved::visual, save_for_backward ? B : 0, -1, pl};
+    c->saved = infer ? SavedForward{} : SavedForward{Saved::visual, save_for_backward ? B : 0, -1, pl};
     return 0;
+}
+
+// images (B,3,R,R) -> logits (B,C) in ONE call, for evaluation: stem -> blocks -> ln_post -> proj in the inference form (blocks_forward,
+// pl.infer), then BatchNorm1d in eval mode on the caller's running statistics -> Linear: the forward-only launch of pevit_launch_head.
+// Reads parameters and running statistics, writes logits (and feat_or_null (B,D)) and workspace scratch only: not the gradient
+// buffer, not last_loss.  batch 1 is legal (eval-mode BatchNorm takes no batch statistics).
+static int predict_impl(pevit_ctx* c, void* stream, const void* images, int u8, const float* running_mean, const float* running_var,
+                        float* logits, float* feat_or_null, int B) {
+    CHECK(check_ready(c, B, "predict"));
+    if (!c->params) { pevit_set_error("predict: parameters not set (the Linear head lives in the flat parameter buffer)"); return -1; }
+    if (!images || !running_mean || !running_var || !logits) { pevit_set_error("predict: null argument"); return -1; }
+    CHECK(visual_forward_impl(c, stream, images, u8, feat_or_null, B, 0, true));
+    char* W = c->ws;
+    HeadArgs a;
+    a.feat = feat_or_null ? feat_or_null : at<float>(W, c->lay.w_feat); a.W = c->params + c->p_head_w; a.bias = c->params + c->p_head_b;
+    // (training = 0: bn_fwd_kernel only reads the running statistics)
+    a.running_mean = const_cast<float*>(running_mean); a.running_var = const_cast<float*>(running_var); a.training = 0;
+    a.ybn = at<float>(W, c->lay.w_ybn); a.rstd = at<float>(W, c->lay.w_bnrstd); a.logits = logits; a.dlogits = at<float>(W, c->lay.w_dlogits);
+    a.dybn = at<float>(W, c->lay.w_dybn); a.B = B; a.D = c->D; a.Cc = c->C;
+    return pevit_launch_head(a, (hipStream_t)stream);
+}
+extern "C" int pevit_predict(pevit_ctx* c, void* stream, const float* images, const float* running_mean, const float* running_var,
+                             float* logits, float* feat_or_null, int B) {
+    return predict_impl(c, stream, images, 0, running_mean, running_var, logits, feat_or_null, B);
+}
+extern "C" int pevit_predict_u8(pevit_ctx* c, void* stream, const uint8_t* images, const float* running_mean, const float* running_var,
+                                float* logits, float* feat_or_null, int B) {
+    if (c && !c->img_norm_set) { pevit_set_error("predict_u8: call pevit_set_input_norm first"); return -1; }
+    return predict_impl(c, stream, images, 1, running_mean, running_var, logits, feat_or_null, B);
 }
 
 // dfeat (B,D) f32 -> adapter gradients (nothing below the first block is trainable).
@@ -1714,6 +1776,7 @@ extern "C" int pevit_op_attn_fwd_delta(void* stream, void* q, const void* k, voi
     AttnFwdDeltaArgs a;
     a.q = (bf16*)q; a.k = (const bf16*)k; a.v = (bf16*)v; a.t = t; a.q16 = (const bf16*)q16; a.bias = bias; a.ascale = ascale;
     a.out = (bf16*)out; a.ldo = ldo; a.lse = lse; a.B = B; a.H = H; a.N = N;
+    a.nosave = lse == nullptr;      // no lse buffer: the inference form (q, v are left as they are)
     return pevit_launch_attn_fwd_delta(a, (hipStream_t)stream);
 }
 extern "C" int pevit_debug_occupy(void* stream, int workgroups, int lds_bytes, double microseconds) {

@@ -1595,9 +1595,10 @@ struct EpiTraits {
     bool ksplit;   // the k-split, phased k-split and stream-K kernels
 };
 constexpr EpiTraits epi_traits(int e) {
-    return {e == EPI_QKV_HEADS || e == EPI_BIAS_RESID_F32 || e == EPI_BIAS_GELU || e == EPI_DGELU_BF16 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_F32,
-            e == EPI_QKV_HEADS || e == EPI_BIAS_RESID_F32 || e == EPI_BIAS_GELU || e == EPI_F32,
-            e == EPI_BIAS_RESID_F32 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_RESID_KEEP || e == EPI_BIAS_GELU || e == EPI_DGELU_BF16,
+    const bool gelu = e == EPI_BIAS_GELU || e == EPI_BIAS_GELU_ONLY;      // the inference form runs wherever the saving one does: the same plan
+    return {e == EPI_QKV_HEADS || e == EPI_BIAS_RESID_F32 || gelu || e == EPI_DGELU_BF16 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_F32,
+            e == EPI_QKV_HEADS || e == EPI_BIAS_RESID_F32 || gelu || e == EPI_F32,
+            e == EPI_BIAS_RESID_F32 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_RESID_KEEP || gelu || e == EPI_DGELU_BF16,
             e == EPI_BIAS_RESID_F32 || e == EPI_F32 || e == EPI_BF16 || e == EPI_BIAS_RESID_KEEP || e == EPI_PATCH_EMBED};
 }
 
@@ -1848,7 +1849,7 @@ GemmPlan plan_gemm(int epi, const GemmParams& p, const GemmTune& t, int cus) {
     }
     if (p.b_fp8 && p.K % 128 != 0) return plan_error("gemm: fp8 B needs K=%d to be a multiple of 128", p.K);
     if (p.b_fp8 && !tr.fp8b) return plan_error("gemm: epilogue %d has no fp8-weight form", epi);
-    if (epi < EPI_QKV_HEADS || epi > EPI_BIAS_F32) return plan_error("gemm: unknown epilogue %d", epi);
+    if (epi < EPI_QKV_HEADS || epi > EPI_LAST) return plan_error("gemm: unknown epilogue %d", epi);
     const GemmPlan pl = plan_tiles(tr, p, t, cus);
     if (p.B2 && (pl.path != 2 || big_bn(pl.cfg) != 256)) return plan_error("%s", no_tail);
     return pl;
@@ -1963,7 +1964,7 @@ int launch_plan(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
     return -1;
 }
 
-// launch_plan<EPI, OPS> by epilogue, EPI_QKV_HEADS (0) .. EPI_BIAS_F32
+// launch_plan<EPI, OPS> by epilogue, EPI_QKV_HEADS (0) .. EPI_LAST
 template <int OPS, int... E>
 int launch_epi(int epi, const GemmParams& p, const GemmPlan& pl, hipStream_t s, std::integer_sequence<int, E...>) {
     constexpr int (*table[])(const GemmParams&, const GemmPlan&, hipStream_t) = {launch_plan<E, OPS>...};
@@ -1986,7 +1987,7 @@ int pevit_launch_gemm(int epi, const GemmParams& p_in, const GemmTune& t, hipStr
     p.dbg = t.ablate;
     const GemmPlan pl = plan_gemm(epi, p, t, num_cus());
     if (pl.err[0]) { pevit_set_error("%s", pl.err); return -1; }
-    constexpr auto epis = std::make_integer_sequence<int, EPI_BIAS_F32 + 1>{};   // plan_gemm refused any other epilogue
+    constexpr auto epis = std::make_integer_sequence<int, EPI_LAST + 1>{};   // plan_gemm refused any other epilogue
     switch (pl.ops) {
         case 2: return launch_epi<2>(epi, p, pl, stream, epis);
         case 1: return launch_epi<1>(epi, p, pl, stream, epis);

@@ -82,7 +82,9 @@ template <typename ST> __device__ __forceinline__ float as_stored(float x) {
 template <int EPI> constexpr bool epi_reads_aux = (EPI == EPI_DGELU_BF16 || EPI == EPI_DRELU_BF16 || EPI == EPI_DGELUNEW_BF16);
 // epilogues whose only other operand is a per-column constant (bias / channel scale): the staggered 8-wave kernel loads
 // it ONCE per lane and runs these epilogues branch-free (epilogue_store_pre)
-template <int EPI> constexpr bool epi_has_pre = (EPI == EPI_QKV_HEADS || EPI == EPI_BIAS_GELU || EPI == EPI_DGELU_BF16);
+template <int EPI> constexpr bool epi_has_pre = (EPI == EPI_QKV_HEADS || EPI == EPI_BIAS_GELU || EPI == EPI_DGELU_BF16 || EPI == EPI_BIAS_GELU_ONLY);
+// QuickGELU of the c_fc product: with the pre-activation h saved for the backward pass, or (inference) the activation alone
+template <int EPI> constexpr bool epi_is_gelu = (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ONLY);
 
 // column constants of the 8 columns col..col+7: the bias; for dGELU the channel scale folded into the output (1 when absent)
 template <int EPI>
@@ -90,7 +92,7 @@ __device__ __forceinline__ void epi_load_cols(const GemmParams& p, int col, floa
     const float* src = nullptr;
     float fill = 0.0f;
     if constexpr (EPI == EPI_QKV_HEADS) { if (col < 3 * p.E) src = p.bias + col; }
-    else if constexpr (EPI == EPI_BIAS_GELU) src = p.bias + col;
+    else if constexpr (epi_is_gelu<EPI>) src = p.bias + col;
     else if constexpr (EPI == EPI_DGELU_BF16) { fill = 1.0f; if (p.oscale) src = p.oscale + col; }
 #pragma unroll
     for (int i = 0; i < 8; ++i) c[i] = fill;
@@ -118,7 +120,7 @@ __device__ __forceinline__ void epilogue_store_pre(const GemmParams& p, int row,
         } else {
             store8f(p.outf + (size_t)row * p.ldo + (col - E3), v);
         }
-    } else if constexpr (EPI == EPI_BIAS_GELU) {
+    } else if constexpr (epi_is_gelu<EPI>) {
         float g[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -128,7 +130,9 @@ __device__ __forceinline__ void epilogue_store_pre(const GemmParams& p, int row,
             g[i] = v[i] * sigmoidf_fast(1.702f * v[i]);
         }
         // the saved pre-activation is not read again before the backward pass: non-temporal store (+0.7 % per step)
-        if constexpr (sizeof(ST) == 2) {
+        // (EPI_BIAS_GELU_ONLY: no backward pass will read it -- the same g from the same rounded h, and no store of h)
+        if constexpr (EPI == EPI_BIAS_GELU_ONLY) {
+        } else if constexpr (sizeof(ST) == 2) {
             bf16x8 o;
 #pragma unroll
             for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
@@ -173,7 +177,7 @@ __device__ __forceinline__ void epilogue_store_aux(const GemmParams& p, int row,
 template <int EPI, typename ST>
 __device__ __forceinline__ void epilogue_store(const GemmParams& p, int row, int col, float v[8]) {
     // row < M and col < N (col multiple of 8) are guaranteed by the caller.
-    if constexpr (EPI == EPI_QKV_HEADS || EPI == EPI_BIAS_GELU) {
+    if constexpr (EPI == EPI_QKV_HEADS || epi_is_gelu<EPI>) {
         float c[8];
         epi_load_cols<EPI>(p, col, c);
         epilogue_store_pre<EPI, ST>(p, row, col, v, c, c);
@@ -232,7 +236,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int row, int
 // stores in flight.  (A load issued after a store is only consumed once that store has been acknowledged: gfx950 counts both
 // in vmcnt, in order.  On these tiles that was one store latency per 16-row pass.)
 template <int EPI> constexpr bool epi_reads_resid = (EPI == EPI_BIAS_RESID_F32 || EPI == EPI_BIAS_RESID_KEEP || EPI == EPI_PATCH_EMBED);
-template <int EPI> constexpr bool epi_has_bias = (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID_F32 || EPI == EPI_BIAS_RESID_KEEP ||
+template <int EPI> constexpr bool epi_has_bias = (epi_is_gelu<EPI> || EPI == EPI_BIAS_RESID_F32 || EPI == EPI_BIAS_RESID_KEEP ||
                                                   EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_GELUNEW || EPI == EPI_BIAS_RELU_BF16 ||
                                                   EPI == EPI_BIAS_F32);
 struct EpiOperand { float4 r0, r1; bf16x8 a; };
@@ -270,7 +274,7 @@ __device__ __forceinline__ void epi_prefetch(const GemmParams& p, int row, int c
 // row < M and col < N (col multiple of 8) are guaranteed by the caller; c = epi_cols, o = epi_prefetch of this position
 template <int EPI, typename ST>
 __device__ __forceinline__ void epilogue_store_full(const GemmParams& p, int row, int col, float v[8], const float c[8], const EpiOperand& o) {
-    if constexpr (EPI == EPI_QKV_HEADS || EPI == EPI_BIAS_GELU) {
+    if constexpr (EPI == EPI_QKV_HEADS || epi_is_gelu<EPI>) {
         epilogue_store_pre<EPI, ST>(p, row, col, v, c, c);
     } else if constexpr (epi_reads_aux<EPI>) {
         float h[8];

@@ -20,7 +20,9 @@ enum GemmEpilogue {
     EPI_DRELU_BF16 = 11,     // out_bf16 = acc * (aux > 0)
     EPI_DGELUNEW_BF16 = 12,  // out_bf16 = acc * gelu_new'(aux)
     EPI_BIAS_F32 = 13,       // out_f32 = acc + bias   (MultiheadAttention.forward: out_proj without the block's residual)
+    EPI_BIAS_GELU_ONLY = 14, // g = QuickGELU(h) (bf16 or e4m3) of the SAME h = stored(acc + bias) as EPI_BIAS_GELU; h is not written, outb may be null (inference)
 };
+constexpr int EPI_LAST = EPI_BIAS_GELU_ONLY;
 
 struct GemmParams {
     const bf16* A; int lda;
@@ -31,7 +33,7 @@ struct GemmParams {
     const bf16* B2; int ldb2, Nb2, n_fp8;
     int b_fp8;                        // B holds e4m3 codes, k-permuted per 128 (fp8_kperm), K % 128 == 0
     int a_fp8;                        // A holds e4m3 codes as well (lda in codes): fp8 x fp8 on the MX matrix instruction (needs b_fp8)
-    int out2_fp8;                     // EPI_BIAS_GELU: the activation output (outb2, ldob2 in codes) is written as k-permuted e4m3 codes
+    int out2_fp8;                     // EPI_BIAS_GELU / EPI_BIAS_GELU_ONLY: the activation output (outb2, ldob2 in codes) is written as k-permuted e4m3 codes
     const float* bscale;              // fp8 B: per-output-channel (power-of-two) scale, applied to the accumulator
     const float* oscale;              // EPI_DGELU_BF16 only: per-column factor folded into the bf16 output (or null)
     int M, N, K;
@@ -116,7 +118,7 @@ int pevit_launch_ln_bwd(const LnBwdArgs& a, hipStream_t s);
 struct AttnArgs {
     const bf16* q = nullptr; const bf16* k = nullptr; const bf16* v = nullptr;
     bf16* out = nullptr; int ldo = 0;       // written by attn_fwd, read by attn_bwd
-    float* lse = nullptr;                   // written by attn_fwd, read by attn_bwd and attn_probs
+    float* lse = nullptr;                   // written by attn_fwd (null: not written, the inference form), read by attn_bwd and attn_probs
     int B = 0, H = 0, N = 0;
     unsigned char* out_fp8 = nullptr;       // attn_fwd: + e4m3 copy of out, row pitch ldo codes
     // attn_bwd.  dqkv: row layout [T][ld]: cols [0,E) dq, [E,2E) dk, [2E,3E) dv
@@ -140,6 +142,7 @@ struct AttnFwdDeltaArgs {
     const float* t = nullptr; const bf16* q16 = nullptr; const float* bias = nullptr; float ascale = 0.f;
     bf16* out = nullptr; int ldo = 0; float* lse = nullptr;
     int B = 0, H = 0, N = 0;
+    int nosave = 0;     // inference: q' / v' stay in LDS and lse is not written (q, v are only read; lse may be null); same `out`
 };
 int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s);
 

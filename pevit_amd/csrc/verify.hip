@@ -304,6 +304,7 @@ int pevit_launch_gemm_f32(int epi, const GemmParams& p, hipStream_t s) {
         case EPI_DRELU_BF16: return launch_f32<EPI_DRELU_BF16>(p, s);
         case EPI_DGELUNEW_BF16: return launch_f32<EPI_DGELUNEW_BF16>(p, s);
         case EPI_BIAS_F32: return launch_f32<EPI_BIAS_F32>(p, s);
+        case EPI_BIAS_GELU_ONLY: return launch_f32<EPI_BIAS_GELU_ONLY>(p, s);
     }
     pevit_set_error("gemm (f32 verification): unknown epilogue %d", epi);
     return -1;

@@ -353,6 +353,30 @@ class HipEngine:
         _lib.check(fn(self._ctx, _lib.stream_ptr(), _lib.ptr(img), _lib.ptr(feat), B, int(save)), "pevit_visual_forward")
         return feat
 
+    def predict(self, images: torch.Tensor, logits_out=None, return_features: bool = False):
+        """images -> logits in ONE engine call, for evaluation (``pevit_predict``): the tower in its inference form (nothing is
+        stored for a backward pass), BatchNorm1d in eval mode on ``running_mean`` / ``running_var``, the Linear head.  Bit-identical
+        to ``head_forward_backward(visual_forward(images, save=False), None, bn_training=False)[0]``; parameters, gradients,
+        momentum and the running statistics are only read.  Returns the logits (B, C) as a device tensor without synchronising --
+        ``logits_out``: a caller-owned f32 destination -- and ``(logits, features (B, D))`` with ``return_features``.  Like every
+        forward it invalidates the activations a pending backward would read."""
+        self.dp_flush()                # a pipelined DP step may still owe the parameter update
+        B = images.shape[0]
+        img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
+        self._check_batch(img)
+        self.forward_generation += 1
+        for l in range(self.arch.layers):
+            self.block_generation[l] = self.block_generation.get(l, 0) + 1
+        if logits_out is None:
+            logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=self.device)
+        else:
+            logits = self._out_buf(logits_out, (B, self.num_classes))
+        feat = torch.empty((B, self.arch.embed_dim), dtype=torch.float32, device=self.device) if return_features else None
+        fn = self.lib.pevit_predict_u8 if img.dtype == torch.uint8 else self.lib.pevit_predict
+        _lib.check(fn(self._ctx, _lib.stream_ptr(), _lib.ptr(img), _lib.ptr(self.running_mean), _lib.ptr(self.running_var),
+                      _lib.ptr(logits), _lib.ptr(feat), B), "pevit_predict")
+        return (logits, feat) if return_features else logits
+
     def visual_backward(self, dfeat: torch.Tensor):
         self.dp_flush()
         B = dfeat.shape[0]

@@ -434,6 +434,33 @@ class ClassifierBase(nn.Module):
             loss = loss.clone()
         return logits, loss
 
+    # ---- fused evaluation ----------------------------------------------------------------
+    def can_fuse_eval(self, images=None) -> bool:
+        """True when one ``pevit_predict`` is exactly ``self(images)``: the module in eval mode, ``channel_bn`` the reference's
+        BatchNorm1d(affine=False, eps=1e-5) with running statistics, no feature normalisation and (``images`` given) f32 or
+        preprocessed-in-engine uint8 pixels on the tower's GPU."""
+        bn = self.channel_bn
+        if self.training or not isinstance(bn, nn.BatchNorm1d) or bn.training or bn.affine or bn.running_mean is None:
+            return False
+        if bn.eps != 1e-5 or self.normalize_visual_output:
+            return False
+        visual = getattr(self.backbone, "visual", None)
+        if visual is None or not hasattr(visual, "engine") or visual.class_embedding.device.type != "cuda":
+            return False
+        if images is not None:
+            if images.device != visual.class_embedding.device:
+                return False
+            if images.dtype == torch.uint8:
+                return getattr(visual, "_input_norm", None) is not None
+            return images.dtype == torch.float32
+        return True
+
+    def fused_predict(self, images):
+        """``self(images)`` in eval mode as one engine call (``can_fuse_eval``): logits (B, C), a fresh device tensor."""
+        eng = self.engine()
+        eng.ensure_batch(images.shape[0])
+        return eng.predict(images.contiguous())
+
     def flush_bn_counter(self, *_):
         """Fold the fused steps counted since the last flush into ``channel_bn.num_batches_tracked`` (train_one does it at the end
         of an epoch, also when the epoch raises; ``state_dict()`` does it first, so a checkpoint taken mid-epoch -- or after direct
@@ -676,7 +703,9 @@ def validate(val_loader, model, criterion, epoch, config, return_logits=False):
             target = target.cuda(dev, non_blocking=True)
         if target.shape[-1] == 1:
             target = target[:, 0]
-        outputs.append(model(images))
+        # images -> logits as one engine call where that is exactly the module's forward (ClassifierBase.can_fuse_eval)
+        fuse = getattr(model, "can_fuse_eval", None)
+        outputs.append(model.fused_predict(images) if fuse is not None and fuse(images) else model(images))
         targets.append(target)
     metric_result, logits = _score(metric, outputs, targets)
     logging.info(f"[Epoch {epoch}] Val: {metric.__name__} {metric_result:.3f}")

@@ -1,0 +1,166 @@
+"""Evaluation images/s of the two routes validate() can take (ViT-B/32, synthetic weights, resident f32 images):
+
+  module   the route before the inference path: Classifier.forward in eval mode under no_grad -- pevit_visual_forward(save = 0), which
+           launches and stores exactly what the training forward does, then BatchNorm1d and Linear as torch launches
+  predict  ClassifierBase.fused_predict: one pevit_predict call (the tower's inference forms + the engine's forward-only head)
+
+Configurations: KAdaptation at batch 64, 128 and TEST.BATCH_SIZE_PER_GPU's default (32); Adapter at batch 128.  Each route runs one
+warm-up pass, then REPS timed passes in alternation (the order swaps every repetition), a pass being STEPS batches.  Wall clock is
+taken with a synchronise on both sides; next to it the median over the batches of a HIP-event pair around each batch.  The logits
+of the two routes are compared once per configuration (the tower bits are the same; the f32 head is computed by different code).
+
+--profile: additionally one batch per route under the engine's own per-launch events (HipEngine.profile_gemms(all_kernels=True)):
+per kernel kind / GEMM shape the launches, milliseconds and ALGORITHMIC bytes (capi.hip prof_close) of a whole forward.
+--one-pass ROUTE: nothing but a warm-up and one pass of ROUTE at batch 128 (the process to put under rocprofv3 --kernel-trace --stats).
+Prints one JSON object.  usage: python scripts/predict_rate.py [--steps 20] [--reps 3] [--profile] [--out FILE]"""
+import argparse
+import dataclasses
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+EPI_NAMES = {0: "qkv", 1: "bias_resid (out_proj / c_proj)", 2: "c_fc bias_gelu (h + g)", 4: "f32", 9: "bias_resid_keep",
+             14: "c_fc bias_gelu_only (g)"}
+
+
+def build(method, ckpt, max_batch):
+    import importlib
+    from pevit_amd.config import vitb32_clip_config
+    mod = importlib.import_module("pevit_amd.evaluation." + {"kadaptation": "kadaptation_clip", "adapter": "adapter_tuning_clip"}[method])
+    cfg = vitb32_clip_config()
+    cfg.MODEL.NAME = ckpt
+    cfg.DATASET.NUM_CLASSES = 100
+    cfg.TEST.BATCH_SIZE_PER_GPU = max_batch
+    cfg.GPUS = (0,)
+    model = mod.Classifier(cfg, 0).cuda(0)
+    model.eval()
+    with torch.no_grad():       # non-trivial running statistics and adapters, so that the compared logits mean something
+        g = torch.Generator().manual_seed(1)
+        model.engine()
+        model.channel_bn.running_mean.copy_((torch.randn(512, generator=g) * 0.3).cuda())
+        model.channel_bn.running_var.copy_((0.5 + torch.rand(512, generator=g)).cuda())
+        for n, p in model.backbone.named_parameters():
+            if p.requires_grad:
+                p.copy_((torch.randn(p.shape, generator=g) * 0.02).cuda())
+    return model
+
+
+def run_pass(fn, batches, events=None):
+    for i, x in enumerate(batches):
+        if events is not None:
+            events[i][0].record()
+        fn(x)
+        if events is not None:
+            events[i][1].record()
+
+
+def measure(model, bs, steps, reps):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn((steps * bs, 3, 224, 224), generator=g).to(dev)
+    batches = [x[i * bs:(i + 1) * bs] for i in range(steps)]
+    routes = {"module": lambda b: model(b), "predict": model.fused_predict}
+    assert model.can_fuse_eval(batches[0])
+    with torch.no_grad():
+        a, b = routes["module"](batches[0]), routes["predict"](batches[0])
+        torch.cuda.synchronize(dev)
+        agree = float((a - b).abs().max() / a.abs().max())
+        for r in routes.values():
+            run_pass(r, batches)                                  # warm-up pass
+        wall = {r: [] for r in routes}
+        ev_us = {r: [] for r in routes}
+        order = list(routes)
+        for rep in range(reps):
+            for r in (order if rep % 2 == 0 else order[::-1]):
+                events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in batches]
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                run_pass(routes[r], batches, events)
+                torch.cuda.synchronize(dev)
+                wall[r].append(steps * bs / (time.perf_counter() - t0))
+                ev_us[r].append(statistics.median(s.elapsed_time(e) * 1e3 for s, e in events))
+    res = {r: {"images_per_s_median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1),
+               "rounds": [round(q, 1) for q in v], "event_us_per_batch_median": round(statistics.median(ev_us[r]), 1),
+               "event_us_per_batch_rounds": [round(q, 1) for q in ev_us[r]]} for r, v in wall.items()}
+    res["predict_over_module"] = round(res["predict"]["images_per_s_median"] / res["module"]["images_per_s_median"], 4)
+    # "not slower": no predict round below the slowest round of the module route on this box
+    res["predict_min_over_module_min"] = round(res["predict"]["min"] / res["module"]["min"], 4)
+    res["logits_max_rel_difference"] = agree
+    return res
+
+
+def profile(model, bs):
+    """per route one forward under the engine's per-launch events: {kernel: [launches, ms, algorithmic MB]}"""
+    eng = model.engine()
+    x = torch.randn((bs, 3, 224, 224), generator=torch.Generator().manual_seed(0)).cuda()
+    out = {}
+    with torch.no_grad():
+        for name, fn in (("module", lambda: model(x)), ("predict", lambda: model.fused_predict(x))):
+            fn()
+            rows = {}
+            for rep in range(5):        # summed over 5 forwards, reported per forward
+                eng.profile_gemms(fn, all_kernels=True)
+                for k, (n, ms, fl, by) in eng.last_profile_by_shape.items():
+                    key = f"gemm {EPI_NAMES.get(k[0], k[0])} M={k[1]} N={k[2]} K={k[3]}"
+                    e = rows.setdefault(key, [0, 0.0, 0.0]); e[0] += n; e[1] += ms; e[2] += by
+                for k, (n, ms, by) in eng.last_profile_hbm.items():
+                    e = rows.setdefault(k, [0, 0.0, 0.0]); e[0] += n; e[1] += ms; e[2] += by
+            out[name] = {k: {"launches": v[0] // 5, "us": round(v[1] / 5 * 1e3, 1), "algorithmic_MB": round(v[2] / 5 / 1e6, 2)}
+                         for k, v in sorted(rows.items())}
+            out[name]["TOTAL"] = {"us": round(sum(v[1] for v in rows.values()) / 5 * 1e3, 1),
+                                  "algorithmic_MB": round(sum(v[2] for v in rows.values()) / 5 / 1e6, 2)}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--one-pass", choices=["module", "predict"], default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from pevit_amd.config import default_config
+    from pevit_amd.evaluation import _harness
+    from pevit_amd.synth import ARCHS, synth_state_dict
+    arch = dataclasses.replace(ARCHS["ViT-B/32"], text_layers=1)
+    test_bs = int(default_config().TEST.BATCH_SIZE_PER_GPU)
+    out = {"how": f"ViT-B/32, synthetic weights, 100 classes, resident f32 images; a pass = {args.steps} batches; one warm-up pass per "
+                  f"route, then {args.reps} timed passes per route in alternation; wall clock between two synchronises"}
+    with tempfile.TemporaryDirectory() as tmp:
+        ckpt = os.path.join(tmp, "vitb32_synth.pt")
+        torch.save(synth_state_dict(arch, seed=2, text_tower=True), ckpt)
+        if args.one_pass:
+            model = build("kadaptation", ckpt, 128)
+            x = torch.randn((128, 3, 224, 224), generator=torch.Generator().manual_seed(0)).cuda()
+            fn = model.fused_predict if args.one_pass == "predict" else model
+            with torch.no_grad():
+                for _ in range(1 + args.steps):
+                    fn(x)
+            torch.cuda.synchronize()
+            print(json.dumps({"one_pass": args.one_pass, "forwards": 1 + args.steps, "batch": 128}))
+            return
+        for method, sizes in (("kadaptation", (64, 128, test_bs)), ("adapter", (128,))):
+            model = build(method, ckpt, 128)
+            for bs in sizes:
+                out[f"{method}_bs{bs}"] = measure(model, bs, args.steps, args.reps)
+            if args.profile:
+                out[f"{method}_bs128_per_kernel"] = profile(model, 128)
+            del model
+            _harness._BACKBONES.clear()
+    s = json.dumps(out, indent=1)
+    print(s)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
