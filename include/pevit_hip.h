@@ -282,6 +282,25 @@ int pevit_op_attn_delta_hpw(int B, int H, int N);
 /* softmax probabilities P = exp(q k^T - lse) (attn_probs.hip): q, k (B*H, N, 64) bf16 as pevit_op_attn_fwd takes them, lse as it
  * wrote it; average = 1: out (B, N, N) f32, the mean over the H heads; 0: out (B, H, N, N) f32.  N <= 384. */
 int pevit_op_attn_probs(void* stream, const void* q, const void* k, const float* lse, float* out, int B, int H, int N, int average);
+/* Test-only forms of the four entry points above (tests/test_gpu_kernel_forms.py): the members of the launchers' parameter structs
+ * that only the training step sets, one kernel at a time.  They add no kernel; 0 / NULL in the extra arguments is the plain call.
+ *   ln_fwd_ex:   xstride = elements between the rows of x (0: E); y_fp8 = k-permuted e4m3 copy [rows][E] (E % 128 == 0)
+ *   ln_bwd_ex:   dy is f32, or (dy_stored) bf16; dres is f32, or (res16, needs dy_stored and dx_bf16) bf16 -- it may then be dx_bf16
+ *                itself (in place) and dx may be NULL; res_period > 0: dres is read on rows that are multiples of it only (zero
+ *                elsewhere); xstride = elements between the rows of x, dres, dx and dx_bf16 (dy, mean, rstd stay compact);
+ *                bf16_colscale: power-of-two column factors on dx_bf16; res_colscale (res16): such factors taken out of dres
+ *   attn_fwd_ex: out_fp8 = k-permuted e4m3 copy of out, row pitch ldo codes
+ *   attn_bwd_ex: dout_cls_only (N <= 64) = dout is zero except on token 0 of every image, the other rows are not read */
+int pevit_op_ln_fwd_ex(void* stream, const float* x, const float* gamma, const float* beta, int rows, int E, size_t xstride,
+                       void* y_bf16, float* y_f32, float* mean, float* rstd, void* y_fp8);
+int pevit_op_ln_bwd_ex(void* stream, const void* dy, int dy_stored, const float* x, const float* mean, const float* rstd,
+                       const float* gamma, const void* dres, int res16, int res_period, float* dx, void* dx_bf16,
+                       int rows, int E, size_t xstride, const float* bf16_colscale, const float* res_colscale);
+int pevit_op_attn_fwd_ex(void* stream, const void* q, const void* k, const void* v, void* out, int ldo, float* lse,
+                         int B, int H, int N, void* out_fp8);
+int pevit_op_attn_bwd_ex(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
+                         const void* dout, int lddo, const float* lse, void* dqkv, int ld, int B, int H, int N,
+                         int dout_cls_only);
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
  * stamps at their phase boundaries (NULL switches it off) */
 int pevit_debug_timeline(void* buf);

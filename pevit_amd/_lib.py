@@ -89,6 +89,11 @@ SIGNATURES = {
     "pevit_op_attn_fwd_delta": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int, P, c_int, c_int, c_int]),
     "pevit_op_attn_delta_hpw": (c_int, [c_int, c_int, c_int]),
     "pevit_op_attn_probs": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int]),
+    # test-only forms (csrc/verify.hip): the step-only members of the launchers' parameter structs
+    "pevit_op_ln_fwd_ex": (c_int, [P, P, P, P, c_int, c_int, c_size_t, P, P, P, P, P]),
+    "pevit_op_ln_bwd_ex": (c_int, [P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, c_int, c_int, c_size_t, P, P]),
+    "pevit_op_attn_fwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, c_int, c_int, P]),
+    "pevit_op_attn_bwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int]),
     "pevit_debug_timeline": (c_int, [P]),
     "pevit_debug_occupy": (c_int, [P, c_int, c_int, C.c_double]),
     "pevit_op_lowrank_u": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int]),

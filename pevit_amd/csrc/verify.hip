@@ -348,3 +348,43 @@ int pevit_launch_lowrank_grad_f32(const LowrankArgs& a, hipStream_t s) {
     LAUNCH_OK("lowrank_grad_f32_kernel");
     return 0;
 }
+
+// ===============================================================================================================
+// TEST-ONLY C-ABI ENTRY POINTS (pevit_op_*_ex).  They hold no kernel: each fills the parameter struct of an existing production
+// launcher by name and calls it, so that the forms that only the training step selects -- strided class-token rows, the in-place
+// bf16 residual gradient, the power-of-two column scales, the e4m3 copies, the class-token-only dO -- can be launched one kernel
+// at a time (tests/test_gpu_kernel_forms.py).  They live in this file because it holds nothing of the profiled production step.
+extern "C" int pevit_op_ln_fwd_ex(void* stream, const float* x, const float* gamma, const float* beta, int rows, int E, size_t xstride,
+                                  void* y_bf16, float* y_f32, float* mean, float* rstd, void* y_fp8) {
+    LnFwdArgs a;
+    a.x = x; a.gamma = gamma; a.beta = beta; a.rows = rows; a.E = E; a.xstride = xstride;
+    a.y_bf16 = (bf16*)y_bf16; a.y_f32 = y_f32; a.mean = mean; a.rstd = rstd; a.y_fp8 = (unsigned char*)y_fp8;
+    return pevit_launch_ln_fwd(a, (hipStream_t)stream);
+}
+// dy: f32, or (dy_stored) bf16.  dres: f32, or (res16) bf16 -- it may then be dx_bf16 itself, and dx may be null.
+extern "C" int pevit_op_ln_bwd_ex(void* stream, const void* dy, int dy_stored, const float* x, const float* mean, const float* rstd,
+                                  const float* gamma, const void* dres, int res16, int res_period, float* dx, void* dx_bf16,
+                                  int rows, int E, size_t xstride, const float* bf16_colscale, const float* res_colscale) {
+    LnBwdArgs a;
+    a.dy = dy; a.dy_stored = dy_stored; a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma;
+    a.dres = (const float*)dres; a.res16 = res16; a.res_period = res_period; a.dx_out = dx; a.dx_bf16 = (bf16*)dx_bf16;
+    a.rows = rows; a.E = E; a.xstride = xstride; a.bf16_colscale = bf16_colscale; a.res_colscale = res_colscale;
+    return pevit_launch_ln_bwd(a, (hipStream_t)stream);
+}
+// out_fp8: e4m3 copy of out (k-permuted, row pitch ldo codes), or null
+extern "C" int pevit_op_attn_fwd_ex(void* stream, const void* q, const void* k, const void* v, void* out, int ldo, float* lse,
+                                    int B, int H, int N, void* out_fp8) {
+    AttnArgs a;
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.ldo = ldo; a.lse = lse; a.B = B; a.H = H; a.N = N;
+    a.out_fp8 = (unsigned char*)out_fp8;
+    return pevit_launch_attn_fwd(a, (hipStream_t)stream);
+}
+extern "C" int pevit_op_attn_bwd_ex(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
+                                    const void* dout, int lddo, const float* lse, void* dqkv, int ld, int B, int H, int N,
+                                    int dout_cls_only) {
+    AttnArgs a;      // (out and lse are only read by the backward)
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)const_cast<void*>(out); a.ldo = ldo;
+    a.lse = const_cast<float*>(lse); a.B = B; a.H = H; a.N = N; a.dout = (const bf16*)dout; a.lddo = lddo; a.dqkv = (bf16*)dqkv; a.ld = ld;
+    a.dout_cls_only = dout_cls_only;
+    return pevit_launch_attn_bwd(a, (hipStream_t)stream);
+}

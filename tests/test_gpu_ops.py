@@ -1,5 +1,15 @@
-"""Kernel-level parity: every HIP kernel, called through the C ABI, against a plain PyTorch
+"""Kernel-level parity, part 1: HIP kernels called one at a time through the C ABI, against a plain PyTorch
 fp32 statement of the same op evaluated on the same (bf16-rounded) operands.
+
+Covered here: the bf16 GEMM family (epilogues 0-8, every tile configuration, the stream-K / k-split / few-row paths), LayerNorm
+forward and backward in their plain form (f32 dy, f32 residual gradient, compact rows), the attention core forward and backward at
+N in {1, 10, 50, 64, 197, 257} with row pitches equal to the width (the N <= 64 instance and the two compile-time-N forward
+instances), delta_add and its fusion with the attention forward, and the low-rank adapter products.
+Elsewhere: the other attention token counts (the runtime-N forward instances, the backward kernel's shared last tile, other
+pitches), the LayerNorm forms that the training step selects (bf16 dy, the in-place bf16 residual gradient, class-token period and
+row stride, column scales, e4m3 copy) and the attention e4m3 copy / class-token-only dO in test_gpu_kernel_forms.py; the post-MLP
+adapter kernels, epilogues 9-12, stem, head and SGD in test_gpu_ops2.py; the fp8 kernels in test_gpu_fp8.py; attn_probs in
+test_gpu_attention_seam.py and test_gpu_kernel_forms.py; the all-reduce in test_gpu_allreduce.py.
 
 Tolerances: f32 outputs of bf16xbf16 MFMA contractions differ from the torch reference only by
 summation order -> 2e-4 relative-to-max; bf16 outputs add one rounding (2^-9) -> 1e-2.
