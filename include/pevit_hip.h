@@ -301,6 +301,35 @@ int pevit_op_attn_fwd_ex(void* stream, const void* q, const void* k, const void*
 int pevit_op_attn_bwd_ex(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
                          const void* dout, int lddo, const float* lse, void* dqkv, int ld, int B, int H, int N,
                          int dout_cls_only);
+/* Test-only form of the three GEMM entry points above (tests/test_gpu_gemm_forms.py): EVERY member of the launcher's parameter
+ * struct, by name, from one flat argument struct -- the second f32 output of EPI_BIAS_RESID_KEEP (out_f32_2 / ldo2), the bf16 tail of
+ * an fp8-B product (B2 / ldb2 / b2_rows / n_fp8: output columns >= n_fp8 take their B rows from B2, which lies behind B), the operand
+ * forms (b_fp8, a_fp8, bscale, oscale) -- a tune of its own, and the caller's stream-K workspace.  It adds no kernel.
+ *   tune:      a default-constructed tune in which the knobs whose bit is set in tune_set are overwritten (bit i = the i-th of
+ *              config, stagger, big, ksplit, ksplit_small, ksplit_stagger, ksplit_mink, kphase_nl, kz2, skinny, skinny_slices,
+ *              streamk, persistent: enum pevit_gemm_knob); the process-wide tune of pevit_tune(NULL, ...) is neither read nor written
+ *   workspace: sk_flag = sk_slots + 1 zeroed words (hand-off flags / tickets, then the error word at sk_flag[sk_slots]), sk_slab =
+ *              sk_slots x 128 x 128 floats, sk_slots = pevit_op_gemm_sk_slots(); all NULL / 0: the families that need one are not taken */
+enum pevit_gemm_knob {
+    PEVIT_KNOB_CONFIG = 0, PEVIT_KNOB_STAGGER = 1, PEVIT_KNOB_BIG = 2, PEVIT_KNOB_KSPLIT = 3, PEVIT_KNOB_KSPLIT_SMALL = 4,
+    PEVIT_KNOB_KSPLIT_STAGGER = 5, PEVIT_KNOB_KSPLIT_MINK = 6, PEVIT_KNOB_KPHASE_NL = 7, PEVIT_KNOB_KZ2 = 8, PEVIT_KNOB_SKINNY = 9,
+    PEVIT_KNOB_SKINNY_SLICES = 10, PEVIT_KNOB_STREAMK = 11, PEVIT_KNOB_PERSISTENT = 12, PEVIT_KNOB_COUNT = 13
+};
+typedef struct pevit_gemm_ex_args {
+    const void* A; const void* B; const void* B2;
+    const float* bias; const float* resid; const float* bscale; const float* oscale;
+    float* out_f32; float* out_f32_2; void* out_bf16; void* out2_bf16; const void* aux_bf16;
+    float* sk_slab; unsigned* sk_flag;
+    size_t head_stride;
+    int32_t epilogue, M, N, K;
+    int32_t lda, ldb, b_rows, ldb2, b2_rows, n_fp8, b_fp8, a_fp8;
+    int32_t ldr, ldo, ldo2, ldob, ldob2, ldaux;
+    int32_t E, H, tokens, sk_slots;
+    uint32_t tune_set;                      /* bit per knob of tune[] that is set */
+    int32_t tune[13];                       /* indexed by enum pevit_gemm_knob */
+} pevit_gemm_ex_args;
+int pevit_op_gemm_ex(void* stream, const pevit_gemm_ex_args* args);
+int pevit_op_gemm_sk_slots(void);           /* residency slots of the stream-K workspace on this device (pevit_op_gemm sizes its own by it) */
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
  * stamps at their phase boundaries (NULL switches it off) */
 int pevit_debug_timeline(void* buf);

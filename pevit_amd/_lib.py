@@ -21,6 +21,26 @@ class PevitDims(C.Structure):
                 ("num_classes", C.c_int32), ("weight_format", C.c_int32)]
 
 
+GEMM_KNOBS = ("config", "stagger", "big", "ksplit", "ksplit_small", "ksplit_stagger", "ksplit_mink", "kphase_nl", "kz2", "skinny",
+              "skinny_slices", "streamk", "persistent")           # enum pevit_gemm_knob
+
+
+class PevitGemmExArgs(C.Structure):
+    """pevit_gemm_ex_args of include/pevit_hip.h (the test-only pevit_op_gemm_ex); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("A", "B", "B2", "bias", "resid", "bscale", "oscale", "out_f32", "out_f32_2", "out_bf16",
+                                         "out2_bf16", "aux_bf16", "sk_slab", "sk_flag")] +
+                [("head_stride", c_size_t)] +
+                [(n, C.c_int32) for n in ("epilogue", "M", "N", "K", "lda", "ldb", "b_rows", "ldb2", "b2_rows", "n_fp8", "b_fp8", "a_fp8",
+                                          "ldr", "ldo", "ldo2", "ldob", "ldob2", "ldaux", "E", "H", "tokens", "sk_slots")] +
+                [("tune_set", C.c_uint32), ("tune", C.c_int32 * len(GEMM_KNOBS))])
+
+    def set_tune(self, **knobs):
+        for k, v in knobs.items():
+            i = GEMM_KNOBS.index(k)
+            self.tune[i] = v
+            self.tune_set |= 1 << i
+
+
 WEIGHT_FORMATS = {"bf16": 0, "fp8": 1, "f32-verify": 2, "fp8-act": 3}
 
 
@@ -94,6 +114,8 @@ SIGNATURES = {
     "pevit_op_ln_bwd_ex": (c_int, [P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, c_int, c_int, c_size_t, P, P]),
     "pevit_op_attn_fwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, c_int, c_int, P]),
     "pevit_op_attn_bwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int]),
+    "pevit_op_gemm_ex": (c_int, [P, C.POINTER(PevitGemmExArgs)]),
+    "pevit_op_gemm_sk_slots": (c_int, []),
     "pevit_debug_timeline": (c_int, [P]),
     "pevit_debug_occupy": (c_int, [P, c_int, c_int, C.c_double]),
     "pevit_op_lowrank_u": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int]),

@@ -5,7 +5,9 @@ Covered here: the bf16 GEMM family (epilogues 0-8, every tile configuration, the
 forward and backward in their plain form (f32 dy, f32 residual gradient, compact rows), the attention core forward and backward at
 N in {1, 10, 50, 64, 197, 257} with row pitches equal to the width (the N <= 64 instance and the two compile-time-N forward
 instances), delta_add and its fusion with the attention forward, and the low-rank adapter products.
-Elsewhere: the other attention token counts (the runtime-N forward instances, the backward kernel's shared last tile, other
+Elsewhere: every GEMM epilogue on every kernel family and operand form, bit for bit on exactly representable operands, with
+guarded buffers and pairwise different pitches, in test_gpu_gemm_forms.py (its table, operands and references:
+test_gemm_forms_host.py); the other attention token counts (the runtime-N forward instances, the backward kernel's shared last tile, other
 pitches), the LayerNorm forms that the training step selects (bf16 dy, the in-place bf16 residual gradient, class-token period and
 row stride, column scales, e4m3 copy) and the attention e4m3 copy / class-token-only dO in test_gpu_kernel_forms.py; the post-MLP
 adapter kernels, epilogues 9-12, stem, head and SGD in test_gpu_ops2.py; the fp8 kernels in test_gpu_fp8.py; attn_probs in
