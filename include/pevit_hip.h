@@ -330,6 +330,37 @@ typedef struct pevit_gemm_ex_args {
 } pevit_gemm_ex_args;
 int pevit_op_gemm_ex(void* stream, const pevit_gemm_ex_args* args);
 int pevit_op_gemm_sk_slots(void);           /* residency slots of the stream-K workspace on this device (pevit_op_gemm sizes its own by it) */
+/* Test-only form of the fused post-MLP adapter launches (adapter_fused.hip; tests/test_gpu_adapter_fused.py): EVERY member of the
+ * launchers' parameter structs, by name, from one flat argument struct each (zero-initialised = nothing set).  They add no kernel.
+ *   act_kind 0 = ReLU (Adapter), 1 = gelu_new (Compacter); E in {256, 512, 768, 1024} (pevit_op_adapter_fused_ok), T >= 1
+ *   forward:  hraw [T][E] f32 = the c_proj accumulators WITHOUT their bias bpr [E]; x_mid [T][E] f32; gamma, beta [E]; wd [64][E] and
+ *             wu [E][64] bf16; b_down [64], b_up [E] -> z [T][E] bf16, mean_a / rstd_a [T], act [T][64] bf16, apre [T][64] bf16
+ *             (gelu_new only: the ReLU kernel does not touch it), x_out [T][E] f32
+ *   backward: dyb [T][E] bf16 = dx_out; dres [T][E] f32 = dx_out, or NULL (the residual and the d b_up sums then take dyb);
+ *             wuT [64][E], wdT [E][64] bf16; saved [T][64] bf16 = act (ReLU) / apre (gelu_new) -> dpre [T][64] bf16, dh_bf16 [T][E],
+ *             partial [pevit_op_adapter_blocks(T)][3][E] = column sums of dz * xhat, dz, dx_out over the rows of each workgroup
+ *   tn_*:     the token-contracted products that ride in the backward launch, layouts of pevit_op_tn_gemm64 below: product 1 =
+ *             (tn_x1 [T][E], tn_y1 [T][64]) -> tn_partial1; product 2 = (tn_x2, tn_y2) -> tn_partial2 and the column sums of tn_y2
+ *             -> tn_csy2; tn_x1 / tn_x2 NULL leave a product out; tn_y2 must not be dpre; tn_blocks = workgroups of that range
+ *             (0: one per pair of (256-row chunk, 64-column slab) units) */
+typedef struct pevit_adapter_fwd_args {
+    const float* hraw; const float* bpr; const float* x_mid; const float* gamma; const float* beta;
+    const void* wd; const float* b_down; const void* wu; const float* b_up;
+    void* z; float* mean_a; float* rstd_a; void* act; void* apre; float* x_out;
+    int32_t act_kind, T, E;
+} pevit_adapter_fwd_args;
+typedef struct pevit_adapter_bwd_args {
+    const void* dyb; const float* dres; const void* wuT; const void* saved; const void* wdT;
+    const float* hraw; const float* bpr; const float* mean_a; const float* rstd_a; const float* gamma;
+    void* dpre; void* dh_bf16; float* partial;
+    const void* tn_x1; const void* tn_y1; float* tn_partial1;
+    const void* tn_x2; const void* tn_y2; float* tn_partial2; float* tn_csy2;
+    int32_t act_kind, T, E, tn_blocks;
+} pevit_adapter_bwd_args;
+int pevit_op_adapter_fwd_ex(void* stream, const pevit_adapter_fwd_args* args);
+int pevit_op_adapter_bwd_ex(void* stream, const pevit_adapter_bwd_args* args);
+int pevit_op_adapter_blocks(int T);         /* workgroups (= blocks of `partial`) of the fused backward */
+int pevit_op_adapter_fused_ok(int E);       /* 1: the fused launches take this width */
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
  * stamps at their phase boundaries (NULL switches it off) */
 int pevit_debug_timeline(void* buf);

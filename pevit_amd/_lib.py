@@ -41,6 +41,21 @@ class PevitGemmExArgs(C.Structure):
             self.tune_set |= 1 << i
 
 
+class PevitAdapterFwdArgs(C.Structure):
+    """pevit_adapter_fwd_args of include/pevit_hip.h (the test-only pevit_op_adapter_fwd_ex); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("hraw", "bpr", "x_mid", "gamma", "beta", "wd", "b_down", "wu", "b_up", "z", "mean_a",
+                                         "rstd_a", "act", "apre", "x_out")] +
+                [(n, C.c_int32) for n in ("act_kind", "T", "E")])
+
+
+class PevitAdapterBwdArgs(C.Structure):
+    """pevit_adapter_bwd_args of include/pevit_hip.h (the test-only pevit_op_adapter_bwd_ex); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("dyb", "dres", "wuT", "saved", "wdT", "hraw", "bpr", "mean_a", "rstd_a", "gamma", "dpre",
+                                         "dh_bf16", "partial", "tn_x1", "tn_y1", "tn_partial1", "tn_x2", "tn_y2", "tn_partial2",
+                                         "tn_csy2")] +
+                [(n, C.c_int32) for n in ("act_kind", "T", "E", "tn_blocks")])
+
+
 WEIGHT_FORMATS = {"bf16": 0, "fp8": 1, "f32-verify": 2, "fp8-act": 3}
 
 
@@ -116,6 +131,10 @@ SIGNATURES = {
     "pevit_op_attn_bwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int]),
     "pevit_op_gemm_ex": (c_int, [P, C.POINTER(PevitGemmExArgs)]),
     "pevit_op_gemm_sk_slots": (c_int, []),
+    "pevit_op_adapter_fwd_ex": (c_int, [P, C.POINTER(PevitAdapterFwdArgs)]),
+    "pevit_op_adapter_bwd_ex": (c_int, [P, C.POINTER(PevitAdapterBwdArgs)]),
+    "pevit_op_adapter_blocks": (c_int, [c_int]),
+    "pevit_op_adapter_fused_ok": (c_int, [c_int]),
     "pevit_debug_timeline": (c_int, [P]),
     "pevit_debug_occupy": (c_int, [P, c_int, c_int, C.c_double]),
     "pevit_op_lowrank_u": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int]),

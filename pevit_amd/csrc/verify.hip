@@ -412,3 +412,28 @@ extern "C" int pevit_op_gemm_ex(void* stream, const pevit_gemm_ex_args* a) {
     return pevit_launch_gemm(a->epilogue, p, t, (hipStream_t)stream);
 }
 extern "C" int pevit_op_gemm_sk_slots(void) { return pevit_gemm_sk_slots(); }
+// The fused post-MLP adapter launches (adapter_fused.hip; tests/test_gpu_adapter_fused.py): every member of AdapterFwdArgs /
+// AdapterBwdArgs by name, the contraction range of the backward included.
+extern "C" int pevit_op_adapter_fwd_ex(void* stream, const pevit_adapter_fwd_args* a) {
+    if (!a) { pevit_set_error("adapter_fwd_ex: null argument struct"); return -1; }
+    AdapterFwdArgs p;
+    p.act_kind = a->act_kind; p.T = a->T; p.E = a->E;
+    p.hraw = a->hraw; p.bpr = a->bpr; p.x_mid = a->x_mid; p.gamma = a->gamma; p.beta = a->beta;
+    p.wd = (const bf16*)a->wd; p.b_down = a->b_down; p.wu = (const bf16*)a->wu; p.b_up = a->b_up;
+    p.z = (bf16*)a->z; p.mean_a = a->mean_a; p.rstd_a = a->rstd_a; p.act = (bf16*)a->act; p.apre = (bf16*)a->apre; p.x_out = a->x_out;
+    return pevit_launch_adapter_fwd(p, (hipStream_t)stream);
+}
+extern "C" int pevit_op_adapter_bwd_ex(void* stream, const pevit_adapter_bwd_args* a) {
+    if (!a) { pevit_set_error("adapter_bwd_ex: null argument struct"); return -1; }
+    AdapterBwdArgs p;
+    p.act_kind = a->act_kind; p.T = a->T; p.E = a->E;
+    p.dyb = (const bf16*)a->dyb; p.dres = a->dres; p.wuT = (const bf16*)a->wuT; p.saved = (const bf16*)a->saved; p.wdT = (const bf16*)a->wdT;
+    p.hraw = a->hraw; p.bpr = a->bpr; p.mean_a = a->mean_a; p.rstd_a = a->rstd_a; p.gamma = a->gamma;
+    p.dpre = (bf16*)a->dpre; p.dh_bf16 = (bf16*)a->dh_bf16; p.partial = a->partial;
+    p.tn_x1 = (const bf16*)a->tn_x1; p.tn_y1 = (const bf16*)a->tn_y1; p.tn_partial1 = a->tn_partial1;
+    p.tn_x2 = (const bf16*)a->tn_x2; p.tn_y2 = (const bf16*)a->tn_y2; p.tn_partial2 = a->tn_partial2; p.tn_csy2 = a->tn_csy2;
+    p.tn_blocks = a->tn_blocks;
+    return pevit_launch_adapter_bwd(p, (hipStream_t)stream);
+}
+extern "C" int pevit_op_adapter_blocks(int T) { return pevit_adapter_blocks(T); }
+extern "C" int pevit_op_adapter_fused_ok(int E) { return pevit_adapter_fused_ok(E) ? 1 : 0; }

@@ -636,15 +636,30 @@ def test_bf16_ln_input_gradient_hand_over_costs_what_it_is_said_to():
     assert worst[0] < 1.5e-2, worst
 
 
-@pytest.mark.parametrize("arch_name,B", [("tiny-256", 7), ("ViT-B/32-2L", 24)])
+# one-block towers at the widths no named test architecture has: (width, patch, resolution, embed_dim)
+FUSED_BLOCKS = {"block-512": (512, 16, 64, 128), "block-1024": (1024, 14, 224, 768)}
+
+
+@pytest.mark.parametrize("arch_name,B,gstream", [
+    pytest.param("tiny-256", 7, 1, id="tiny-256-7"), pytest.param("ViT-B/32-2L", 24, 1, id="ViT-B/32-2L-24"),
+    pytest.param("tiny-256", 7, 0, id="tiny-256-7-gstream0"), pytest.param("ViT-B/32-2L", 24, 0, id="ViT-B/32-2L-24-gstream0"),
+    pytest.param("block-512", 6, 1, id="block-512-6"), pytest.param("block-512", 6, 0, id="block-512-6-gstream0"),
+    pytest.param("block-1024", 2, 1, id="block-1024-2"), pytest.param("block-1024", 2, 0, id="block-1024-2-gstream0")])
 @pytest.mark.parametrize("method", ["adapter", "compacter"])
-def test_fused_post_mlp_adapter_equals_the_separate_launches(method, arch_name, B):
+def test_fused_post_mlp_adapter_equals_the_separate_launches(method, arch_name, B, gstream):
     """adapter_fused.hip (LayerNorm -> down -> activation -> up -> residual as one launch, and its backward with the affine
     LayerNorm gradients) against the separate LayerNorm / GEMM launches it replaces (`adapter_fused` = 0): the same bf16 rounding
-    points (z, activation, d pre), so logits and every gradient agree to f32 summation order -- ragged last row block included."""
+    points (z, activation, d pre), so logits and every gradient agree to f32 summation order -- ragged last row block included.
+    Widths 256, 512, 768 and 1024 (the four E / 256 instances of the fused kernels), and with `gstream_bf16` = 0 on the fused
+    engine the backward instances that take the f32 residual gradient: the step itself selects every kind of instance once."""
     from pevit_amd.engine import HipEngine, adapter_param_spec
-    from pevit_amd.synth import ARCHS, randomize_adapters, synth_batch, synth_state_dict
-    arch, C = ARCHS[arch_name], 10
+    from pevit_amd.synth import ARCHS, VitArch, randomize_adapters, synth_batch, synth_state_dict
+    if arch_name in ARCHS:
+        arch = ARCHS[arch_name]
+    else:
+        width, patch, resolution, embed = FUSED_BLOCKS[arch_name]
+        arch = VitArch(arch_name, width, 1, patch, resolution, embed)
+    C = 10
     sd = {k: v for k, v in synth_state_dict(arch, seed=2, text_tower=False).items() if k.startswith("visual.")}
     ad = [(n, torch.zeros(s)) for n, s, _ in adapter_param_spec(method, arch.width, arch.layers)]
     randomize_adapters(ad, seed=3)
@@ -658,6 +673,8 @@ def test_fused_post_mlp_adapter_equals_the_separate_launches(method, arch_name, 
         eng = HipEngine(arch, method, C, B)
         eng.load_state_dict(sd)
         assert eng.tune("adapter_fused", fused) == 0
+        if fused and not gstream:
+            assert eng.tune("gstream_bf16", 0) == 0
         logits, loss = eng.forward_backward(images.cuda(), labels.cuda())
         torch.cuda.synchronize()
         res.append((logits.cpu().clone(), float(loss), {k: v.cpu().clone() for k, v in eng.grad_views().items()}))
