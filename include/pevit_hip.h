@@ -22,6 +22,8 @@
  *                                           kadaptation_clip.py:128-132,176-185,276,351-352
  *   pevit_sgd_step                          optimizer.step()               kadaptation_clip.py:353,
  *                                           optim/build.py:120-127
+ *   pevit_optim_step                        optimizer.step() of Adam / AdamW / SGD with several groups
+ *                                           optim/build.py:107-170
  *   pevit_load_block / pevit_load_stem      build_model's load_state_dict  model.py:1247-1250
  *
  * Conventions: extern "C"; every function returns 0 on success and a negative value on error
@@ -173,6 +175,29 @@ int pevit_zero_grads(pevit_ctx* ctx, void* stream);
 /* flags: bit 0 = first step of the run (momentum buffer := gradient, like torch), bit 1 = Nesterov momentum */
 int pevit_sgd_step(pevit_ctx* ctx, void* stream, float lr, float momentum, float weight_decay,
                    float grad_scale, int flags);
+/* The fused update for the other optimizers optim/build.py constructs (build.py:107-170): torch.optim.Adam, torch.optim.AdamW
+ * (torch 2.10, foreach=False: _single_tensor_adam) and torch.optim.SGD whose parameter groups differ in lr / weight decay.  One
+ * launch over the flat buffer; plain SGD keeps pevit_sgd_step.
+ * pevit_set_optim_state: device buffers of pevit_num_params elements (borrowed).  `group_of[i]` is the index of element i's
+ * group in the `groups` array of pevit_optim_step; 255 = the parameter's .grad is None (nothing of it is touched, AdamW's
+ * decoupled decay included) -- it takes the place of grad_mask here.  `exp_avg_sq` may be NULL while only the SGD kind is used;
+ * exp_avg is the momentum buffer of pevit_set_params.
+ * pevit_optim_group: plain floating-point values, in double: Python's scalars arrive unrounded, and everything derived from them
+ * (1 - beta1, 1 - beta2, 1 - lr * wd, lr / (1 - beta1^step), sqrt(1 - beta2^step)) is computed in double and rounded to f32 once,
+ * as torch does with its Python scalars.  The groups travel by value in the kernel arguments: no copy to the device.
+ * pevit_optim_step: `step` is the 1-based count of updates (Adam kinds: the bias corrections); flags bit 0 = first step of the
+ * run (SGD kind: momentum buffer := gradient, as for pevit_sgd_step).  Fails, launching nothing, when n_groups is outside
+ * [1, PEVIT_OPTIM_MAX_GROUPS], step < 1 for the Adam kinds, the state is missing or the context has no parameters.  The
+ * stream-K error word and pevit_set_external_poison withhold the update exactly as for pevit_sgd_step. */
+enum pevit_optim_kind { PEVIT_OPTIM_SGD = 0, PEVIT_OPTIM_ADAM = 1, PEVIT_OPTIM_ADAMW = 2 };
+#define PEVIT_OPTIM_MAX_GROUPS 8
+typedef struct pevit_optim_group {
+    double lr, weight_decay, momentum, beta1, beta2, eps;
+    int nesterov;
+} pevit_optim_group;
+int pevit_set_optim_state(pevit_ctx* ctx, float* exp_avg_sq_or_null, const unsigned char* group_of);
+int pevit_optim_step(pevit_ctx* ctx, void* stream, int kind, const pevit_optim_group* groups, int n_groups, int step,
+                     float grad_scale, int flags);
 /* uint8 pixels (B,3,R,R) instead of preprocessed f32: the dataset transforms of the reference (ToTensor + Normalize with
  * INPUT.MEAN / INPUT.STD: feature.py:537-542, resources/model/vitb32_CLIP.yaml:4-6), x = (u8 / 255 - mean[c]) / std[c], run inside
  * the patch gather -- bit for bit the f32 values `(x.float() / 255 - mean) / std` gives on the host; a quarter of the bytes

@@ -56,6 +56,15 @@ class PevitAdapterBwdArgs(C.Structure):
                 [(n, C.c_int32) for n in ("act_kind", "T", "E", "tn_blocks")])
 
 
+class PevitOptimGroup(C.Structure):
+    """pevit_optim_group of include/pevit_hip.h: one parameter group of pevit_optim_step (doubles: Python's scalars unrounded)"""
+    _fields_ = [(n, C.c_double) for n in ("lr", "weight_decay", "momentum", "beta1", "beta2", "eps")] + [("nesterov", C.c_int)]
+
+
+OPTIM_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}           # enum pevit_optim_kind
+OPTIM_MAX_GROUPS = 8                                       # PEVIT_OPTIM_MAX_GROUPS
+OPTIM_NO_GRAD = 255                                        # group_of value of an element whose parameter has .grad None
+
 WEIGHT_FORMATS = {"bf16": 0, "fp8": 1, "f32-verify": 2, "fp8-act": 3}
 
 
@@ -93,6 +102,8 @@ SIGNATURES = {
     "pevit_predict_u8": (c_int, [P, P, P, P, P, P, P, c_int]),
     "pevit_zero_grads": (c_int, [P, P]),
     "pevit_sgd_step": (c_int, [P, P, c_float, c_float, c_float, c_float, c_int]),
+    "pevit_set_optim_state": (c_int, [P, P, P]),
+    "pevit_optim_step": (c_int, [P, P, c_int, C.POINTER(PevitOptimGroup), c_int, c_int, c_float, c_int]),
     "pevit_train_forward_backward": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
     "pevit_set_input_norm": (c_int, [P, P, P]),
     "pevit_visual_forward_u8": (c_int, [P, P, P, P, c_int, c_int]),

@@ -1,5 +1,6 @@
 // C-ABI layer: context, memory layout of the weight arena / workspace, and the launch
 // sequences of the fine-tune step.  See include/pevit_hip.h for the boundary contract.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -120,6 +121,8 @@ struct pevit_ctx {
     // parameters
     float* params = nullptr; float* grads = nullptr; float* mom = nullptr;
     const unsigned char* grad_mask = nullptr;   // device, 1 = parameter receives gradients
+    float* exp_avg_sq = nullptr;                // pevit_set_optim_state: Adam's second moment (exp_avg is `mom`) ...
+    const unsigned char* group_of = nullptr;    // ... and every element's parameter group (255: no gradient)
     size_t n_tower = 0, n_total = 0;
     size_t p_layer0 = 0, p_layer_stride = 0;     // offsets in floats
     size_t p_head_w = 0, p_head_b = 0;
@@ -1295,6 +1298,50 @@ extern "C" int pevit_sgd_step(pevit_ctx* c, void* stream, float lr, float moment
     a.poison = poison; a.skipped = skipped; a.poison2 = c->ext_poison;
     if (poison || c->ext_poison) a.loss_slot = loss_slot;
     return pevit_launch_sgd(a, (hipStream_t)stream);
+}
+
+static_assert((int)PEVIT_OPTIM_SGD == (int)OPTIM_SGD && (int)PEVIT_OPTIM_ADAM == (int)OPTIM_ADAM &&
+              (int)PEVIT_OPTIM_ADAMW == (int)OPTIM_ADAMW && PEVIT_OPTIM_MAX_GROUPS == OPTIM_MAX_GROUPS, "optimizer kinds: header vs kernels.h");
+
+extern "C" int pevit_set_optim_state(pevit_ctx* c, float* exp_avg_sq, const unsigned char* group_of) {
+    if (!c || !group_of) { pevit_set_error("set_optim_state: null argument"); return -1; }
+    c->exp_avg_sq = exp_avg_sq; c->group_of = group_of;
+    return 0;
+}
+
+// Adam / AdamW / per-group SGD: one launch of optim_kernel (optim.hip).  Everything that is a function of the hyper-parameters
+// and the step alone is computed here in double and rounded to f32 once.
+extern "C" int pevit_optim_step(pevit_ctx* c, void* stream, int kind, const pevit_optim_group* groups, int n_groups, int step,
+                                float grad_scale, int flags) {
+    if (!c || !c->params || !c->grads || !c->mom) { pevit_set_error("optim_step: parameters/momentum not set"); return -1; }
+    if (kind != PEVIT_OPTIM_SGD && kind != PEVIT_OPTIM_ADAM && kind != PEVIT_OPTIM_ADAMW) {
+        pevit_set_error("optim_step: unknown optimizer kind %d", kind); return -1;
+    }
+    const bool adam = kind != PEVIT_OPTIM_SGD;
+    if (!groups || n_groups < 1 || n_groups > PEVIT_OPTIM_MAX_GROUPS) {
+        pevit_set_error("optim_step: %d parameter groups (1 to %d are supported)", n_groups, PEVIT_OPTIM_MAX_GROUPS); return -1;
+    }
+    if (adam && step < 1) { pevit_set_error("optim_step: step %d (the Adam kinds count updates from 1)", step); return -1; }
+    if (!c->group_of || (adam && !c->exp_avg_sq)) { pevit_set_error("optim_step: optimizer state not set (pevit_set_optim_state)"); return -1; }
+    unsigned* poison = (c->ws && c->sk_slots) ? at<unsigned>(c->ws, c->lay.w_skflag) + c->sk_slots : nullptr;
+    unsigned* skipped = poison ? at<unsigned>(c->ws, c->lay.w_skflag) + PEVIT_SK_MAX_SLOTS + 1 : nullptr;
+    float* loss_slot = c->last_loss; c->last_loss = nullptr;
+    OptimArgs a;
+    a.p = c->params; a.g = c->grads; a.exp_avg = c->mom; a.exp_avg_sq = c->exp_avg_sq; a.group_of = c->group_of; a.n = c->n_total;
+    a.kind = kind; a.n_groups = n_groups; a.first_step = flags & 1; a.grad_scale = grad_scale;
+    a.poison = poison; a.skipped = skipped; a.poison2 = c->ext_poison;
+    if (poison || c->ext_poison) a.loss_slot = loss_slot;
+    for (int k = 0; k < n_groups; ++k) {
+        const pevit_optim_group& h = groups[k];
+        OptimGroup& o = a.groups[k];
+        o.lr = (float)h.lr; o.wd = (float)h.weight_decay; o.momentum = (float)h.momentum; o.nesterov = h.nesterov != 0;
+        if (!adam) continue;
+        o.w1 = (float)(1.0 - h.beta1); o.beta2 = (float)h.beta2; o.w2 = (float)(1.0 - h.beta2); o.eps = (float)h.eps;
+        o.step_size = (float)(h.lr / (1.0 - pow(h.beta1, (double)step)));
+        o.sqrt_bc2 = (float)sqrt(1.0 - pow(h.beta2, (double)step));
+        o.decay = (float)(1.0 - h.lr * h.weight_decay);
+    }
+    return pevit_launch_optim(a, (hipStream_t)stream);
 }
 
 // a device word owned by the caller (e.g. pevit_ar_error_word) that, while non-zero, makes pevit_sgd_step withhold the update --

@@ -242,6 +242,32 @@ struct SgdArgs {
 };
 int pevit_launch_sgd(const SgdArgs& a, hipStream_t s);
 
+// ---- optim.hip (Adam, AdamW and per-group SGD over the flat parameter buffer) ------------------------
+enum OptimKind { OPTIM_SGD = 0, OPTIM_ADAM = 1, OPTIM_ADAMW = 2 };      // == enum pevit_optim_kind (include/pevit_hip.h)
+constexpr int OPTIM_MAX_GROUPS = 8;
+// one parameter group as the kernel reads it: every scalar derived from the caller's double-precision hyper-parameters is
+// rounded to f32 once, on the host (torch hands its Python scalars to the f32 kernels the same way)
+struct OptimGroup {
+    float lr = 0.f, wd = 0.f, momentum = 0.f;                 // SGD
+    float w1 = 0.f, beta2 = 0.f, w2 = 0.f, eps = 0.f;         // Adam kinds: 1 - beta1, beta2, 1 - beta2, eps
+    float step_size = 0.f, sqrt_bc2 = 1.f;                    // lr / (1 - beta1^t), sqrt(1 - beta2^t)
+    float decay = 1.f;                                        // AdamW: 1 - lr * wd
+    int nesterov = 0;
+};
+// passed to the kernel BY VALUE (the groups included): no host-to-device copy on the step
+struct OptimArgs {
+    float* p = nullptr; const float* g = nullptr; float* exp_avg = nullptr; float* exp_avg_sq = nullptr;   // exp_avg: the momentum buffer
+    const unsigned char* group_of = nullptr;   // per element: index into groups; 255 = the parameter's .grad is None (skipped)
+    size_t n = 0;
+    int kind = OPTIM_SGD, n_groups = 0, first_step = 0; float grad_scale = 0.f;
+    const unsigned* poison = nullptr;     // as in SgdArgs: error words that withhold the update,
+    unsigned* skipped = nullptr;          // the counter of withheld updates
+    const unsigned* poison2 = nullptr;
+    float* loss_slot = nullptr;           // and where NaN goes when it is withheld
+    OptimGroup groups[OPTIM_MAX_GROUPS];
+};
+int pevit_launch_optim(const OptimArgs& a, hipStream_t s);
+
 int pevit_launch_occupy(int blocks, int lds_bytes, double micros, hipStream_t s);   // measurement only (pevit_debug_occupy)
 
 // ---- fp8.hip (e4m3 codes + power-of-two channel scales of the frozen weights) -----------------

@@ -12,6 +12,7 @@ and DP all-reduce see exactly the tensors the reference has.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from collections import OrderedDict
 
 import torch
@@ -74,6 +75,35 @@ def _numel(shape):
     return n
 
 
+@dataclasses.dataclass
+class OptimPlan:
+    """What ``HipEngine.optimizer_step`` needs to run a torch optimizer's ``step()`` as one launch over the flat buffer.
+
+    ``kind``: "sgd" | "adam" | "adamw".  ``groups``: one dict per LIVE parameter group, in ``group_of``'s numbering, with ``lr``,
+    ``weight_decay`` and (SGD) ``momentum``, ``nesterov`` / (Adam kinds) ``beta1``, ``beta2``, ``eps`` as Python floats.
+    ``group_of``: host uint8 tensor over the flat buffer, 255 where the parameter's ``.grad`` is None (it is uploaded only when
+    its contents change: a tensor edited in place with torch operations is compared again, one written through a NumPy view or
+    a raw pointer is not, so build a new tensor for those).  ``group_index``: the position of each live group in the torch optimizer's ``param_groups``
+    (``refresh`` re-reads the hyper-parameters from there, so schedulers keep working)."""
+    kind: str
+    groups: list
+    group_of: torch.Tensor
+    group_index: list = dataclasses.field(default_factory=list)
+
+    def refresh(self, optimizer):
+        for k, j in enumerate(self.group_index):
+            self.groups[k] = _group_hypers(self.kind, optimizer.param_groups[j])
+        return self
+
+
+def _group_hypers(kind, g):
+    if kind == "sgd":
+        return {"lr": float(g["lr"]), "weight_decay": float(g["weight_decay"]), "momentum": float(g["momentum"]),
+                "nesterov": bool(g["nesterov"])}
+    return {"lr": float(g["lr"]), "weight_decay": float(g["weight_decay"]), "beta1": float(g["betas"][0]),
+            "beta2": float(g["betas"][1]), "eps": float(g["eps"])}
+
+
 class HipEngine:
     def __init__(self, arch: VitArch, method: str, num_classes: int, max_batch: int, lora_rank: int = 4,
                  device: str | torch.device = "cuda:0", weight_format: str = "bf16"):
@@ -115,6 +145,11 @@ class HipEngine:
         if total != self.n_tower:
             raise _lib.PevitError(f"host/engine parameter layout mismatch: {total} vs {self.n_tower}")
         self._steps = 0
+        self.exp_avg_sq = None           # Adam / AdamW second moment: allocated on first use (optimizer_step); exp_avg is self.momentum
+        self._group_of = None            # device copy of the last OptimPlan.group_of ...
+        self._group_of_host = None       # ... a host copy of what was uploaded ...
+        self._group_of_seen = None       # ... and the (tensor, version) last compared with it: an in-place edit of a plan is seen
+        self._optim_kind = None          # which optimizer the momentum / exp_avg_sq buffers belong to (None: fresh, or plain sgd_step)
         self.forward_generation = 0      # bumped by EVERY forward: each one overwrites the single activation workspace
         self.block_generation = {}       # per block: bumped by every forward THROUGH that block (blocks keep their own activations)
         self.attention_generation = {}   # per block: the block_generation its last attention_forward left (attention seam)
@@ -429,6 +464,8 @@ class HipEngine:
     def sgd_step(self, lr, momentum=0.9, weight_decay=0.0, grad_scale=1.0, nesterov=False, _pipelined=False):
         if not _pipelined:             # a direct call while a pipelined update is still running on the second stream
             self.dp_flush()
+        if self._optim_kind not in (None, "sgd"):
+            raise _lib.PevitError(f"sgd_step: the optimizer state belongs to {self._optim_kind!r}; call reset_optimizer() first")
         flags = int(self._steps == 0) | (2 if nesterov else 0)
         _lib.check(self.lib.pevit_sgd_step(self._ctx, _lib.stream_ptr(), lr, momentum, weight_decay, grad_scale, flags),
                    "pevit_sgd_step")
@@ -439,6 +476,67 @@ class HipEngine:
         if self._steps % self.STREAMK_CHECK_EVERY == 0 or getattr(self, "_flat_ar", None) is not None:
             self.check_streamk()
         self._steps += 1
+
+    def _adam_state(self):
+        """Adam's second moment, allocated (zero) on first use and made known to the context."""
+        if self.exp_avg_sq is None:
+            self.exp_avg_sq = torch.zeros_like(self.params)
+            self._bind_optim_state()
+        return self.exp_avg_sq
+
+    def _bind_optim_state(self):
+        if self._group_of is None:
+            self._group_of = torch.full((self.n_params,), _lib.OPTIM_NO_GRAD, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.pevit_set_optim_state(self._ctx, _lib.ptr(self.exp_avg_sq), _lib.ptr(self._group_of)),
+                   "pevit_set_optim_state")
+
+    def optimizer_step(self, plan: "OptimPlan", grad_scale=1.0, _pipelined=False):
+        """``optimizer.step()`` of the optimizer ``plan`` describes (torch.optim.Adam / AdamW, or SGD whose groups differ) as one
+        launch of the fused kernel (csrc/optim.hip) over the flat buffer.  ``exp_avg`` lives in ``self.momentum``, ``exp_avg_sq`` in
+        ``self.exp_avg_sq``; the Adam step ``t`` is this engine's count of optimizer calls since ``reset_optimizer()`` (there is
+        no device-side counter): an update that a raised error word withholds still counts, so after ``clear_streamk_error()``
+        the bias corrections are those of the call count, one ahead of the updates applied, per withheld step.  The state belongs to one optimizer kind: a plan of another kind raises until
+        ``reset_optimizer()``.  Error words, the periodic check and ``dp_flush()`` behave as in ``sgd_step``."""
+        if not _pipelined:
+            self.dp_flush()
+        prior = self._optim_kind or ("sgd" if self._steps else None)
+        if prior is not None and prior != plan.kind:
+            raise _lib.PevitError(f"optimizer_step: the optimizer state belongs to {prior!r}, the plan is {plan.kind!r}; call "
+                                  f"reset_optimizer() first")
+        n = len(plan.groups)
+        if not 1 <= n <= _lib.OPTIM_MAX_GROUPS:
+            raise _lib.PevitError(f"optimizer_step: {n} parameter groups (1 to {_lib.OPTIM_MAX_GROUPS} are supported)")
+        if plan.kind != "sgd":
+            self._adam_state()
+        host = plan.group_of
+        seen = (host, host._version)            # the same tensor, not written since: nothing to compare
+        if self._group_of_seen is None or seen[0] is not self._group_of_seen[0] or seen[1] != self._group_of_seen[1]:
+            if host.dtype != torch.uint8 or host.numel() != self.n_params:
+                raise _lib.PevitError(f"optimizer_step: group_of must hold {self.n_params} uint8 entries")
+            if self._group_of_host is None or not torch.equal(host, self._group_of_host):      # membership changed: the one upload
+                if self._group_of is None:
+                    self._bind_optim_state()
+                self._group_of.copy_(host)
+                self._group_of_host = host.clone()
+            self._group_of_seen = seen
+        groups = (_lib.PevitOptimGroup * n)()
+        for dst, g in zip(groups, plan.groups):
+            dst.lr, dst.weight_decay, dst.momentum = g["lr"], g["weight_decay"], g.get("momentum", 0.0)
+            dst.beta1, dst.beta2, dst.eps = g.get("beta1", 0.0), g.get("beta2", 0.0), g.get("eps", 0.0)
+            dst.nesterov = int(bool(g.get("nesterov", False)))
+        _lib.check(self.lib.pevit_optim_step(self._ctx, _lib.stream_ptr(), _lib.OPTIM_KINDS[plan.kind], groups, n,
+                                             self._steps + 1, grad_scale, int(self._steps == 0)), "pevit_optim_step")
+        self._optim_kind = plan.kind
+        if self._steps % self.STREAMK_CHECK_EVERY == 0 or getattr(self, "_flat_ar", None) is not None:
+            self.check_streamk()
+        self._steps += 1
+
+    def _update(self, optimizer, lr, momentum, weight_decay, grad_scale, nesterov, _pipelined=False):
+        """The step's one dispatch point between the plain-SGD kernel and a planned optimizer."""
+        if optimizer is not None:
+            self.optimizer_step(optimizer, grad_scale, _pipelined=_pipelined)
+        else:
+            self.sgd_step(lr, momentum, weight_decay, grad_scale, nesterov, _pipelined=_pipelined)
 
     STREAMK_CHECK_EVERY = 64
 
@@ -501,39 +599,46 @@ class HipEngine:
     def reset_optimizer(self):
         self.dp_flush()
         self._steps = 0
+        self._optim_kind = None
         self.momentum.zero_()
+        if self.exp_avg_sq is not None:
+            self.exp_avg_sq.zero_()
 
     def reset_run(self):
         """State a fresh ``Classifier`` would have, with the frozen backbone left resident (the
-        reference rebuilds everything for each of its ~90 sweep runs)."""
+        reference rebuilds everything for each of its ~90 sweep runs).  Clears both optimizer moments."""
         self.dp_flush()
         self.reset_optimizer()
         self.params.zero_(); self.grads.zero_()
         self.running_mean.zero_(); self.running_var.fill_(1.0)
 
-    def train_step(self, images, labels, lr, momentum=0.9, weight_decay=0.0, bn_training=True, process_group=None,
-                   world_size=1, nesterov=False, logits_out=None, loss_out=None):
+    def train_step(self, images, labels, lr=None, momentum=0.9, weight_decay=0.0, bn_training=True, process_group=None,
+                   world_size=1, nesterov=False, logits_out=None, loss_out=None, optimizer=None):
         """One reference ``train_one`` iteration (kadaptation_clip.py:347-353).  With DP the flat gradient buffer
         is the only thing that crosses xGMI (the frozen backbone never does); how it is exchanged is ``dp_exchange_mode``
-        (default: one in-stream all-reduce behind the fused forward/backward call, 1/world folded into the SGD kernel)."""
+        (default: one in-stream all-reduce behind the fused forward/backward call, 1/world folded into the SGD kernel).
+        ``optimizer``: an ``OptimPlan`` (Adam, AdamW, SGD with several groups) -- the update is then ``optimizer_step(plan)``
+        wherever it is ``sgd_step`` otherwise, and ``lr`` / ``momentum`` / ``weight_decay`` / ``nesterov`` are not read."""
+        if optimizer is None and lr is None:
+            raise TypeError("train_step: lr (plain SGD) or optimizer (an OptimPlan) is required")
         if world_size <= 1:
             logits, loss = self.forward_backward(images, labels, bn_training, logits_out, loss_out)
-            self.sgd_step(lr, momentum, weight_decay, 1.0, nesterov)
+            self._update(optimizer, lr, momentum, weight_decay, 1.0, nesterov)
             return logits, loss
         if self.dp_exchange_mode == "pipelined":
             return self._train_step_pipelined(images, labels, lr, momentum, weight_decay, bn_training, process_group, world_size,
-                                              nesterov, logits_out, loss_out)
+                                              nesterov, logits_out, loss_out, optimizer)
         logits, loss = self.forward_backward_dp(images, labels, bn_training, process_group)
         if logits_out is not None:
             logits_out.copy_(logits)
         if loss_out is not None:
             loss_out.copy_(loss)
-        self.sgd_step(lr, momentum, weight_decay, 1.0 / world_size, nesterov)
+        self._update(optimizer, lr, momentum, weight_decay, 1.0 / world_size, nesterov)
         return logits, loss
 
     # ---- DP with the exchange under the next step's stem (round 5) ----------------------------------------------------------------
     def _train_step_pipelined(self, images, labels, lr, momentum, weight_decay, bn_training, process_group, world_size, nesterov,
-                              logits_out, loss_out):
+                              logits_out, loss_out, optimizer=None):
         """``dp_exchange_mode = "pipelined"``: the fused forward/backward call on the current stream; the all-reduce of the flat
         gradient buffer and the fused SGD kernel on a SECOND stream behind it; the next fused call runs its stem (patch gather,
         patch embedding, ln_pre: ~70 us that read no trainable parameter) and only then waits, on the device, for the update
@@ -558,7 +663,7 @@ class HipEngine:
             if xt: xt[0].record(st["stream"])
             self._exchange(self.grads, process_group, in_stream=True).wait()
             if xt: xt[1].record(st["stream"])
-            self.sgd_step(lr, momentum, weight_decay, 1.0 / world_size, nesterov, _pipelined=True)
+            self._update(optimizer, lr, momentum, weight_decay, 1.0 / world_size, nesterov, _pipelined=True)
             st["params"].record(st["stream"])
         return logits, loss
 
@@ -597,13 +702,21 @@ class HipEngine:
             self._pipe = None
 
     # ---- whole-step HIP graph -----------------------------------------------------
-    def capture_train_step(self, images, labels, lr, momentum=0.9, weight_decay=0.0, bn_training=True, nesterov=False):
+    def capture_train_step(self, images, labels, lr=None, momentum=0.9, weight_decay=0.0, bn_training=True, nesterov=False,
+                           optimizer=None):
         """Capture ``forward_backward + sgd_step`` on THESE buffers (pointers, batch, hyper-parameters and BatchNorm mode are baked
         in) into a HIP graph and return a callable that replays it: one hipGraphLaunch instead of ~200 kernel launches from the
         C call.  The step counter, the periodic error-word check and the results (``self._logits``, ``self._loss``) behave as in
         ``train_step``.  At least one eager step must have run (the first SGD step has no momentum buffer to read, and the
         library's one-time attribute calls are not stream operations).  Same kernels, same order: bit-identical to eager
-        (tests/test_gpu_mirror.py::test_graph_replay_equals_eager).  Measured: profiles/r05_graph_capture.md."""
+        (tests/test_gpu_mirror.py::test_graph_replay_equals_eager).  Measured: profiles/r05_graph_capture.md.
+        Plain SGD only: the Adam step count ``t`` is kept by the host and reaches the kernel by value, so a captured launch would
+        replay one fixed ``t``; an ``optimizer`` plan (``optimizer_step``) raises here until a device-side counter exists."""
+        if optimizer is not None:
+            raise _lib.PevitError("capture_train_step captures the plain-SGD step only: the planned optimizers (Adam, AdamW, "
+                                  "per-group SGD) take their step count and hyper-parameters by value on every launch")
+        if lr is None:
+            raise TypeError("capture_train_step: lr is required")
         if self._steps == 0:
             raise _lib.PevitError("capture_train_step: run one eager train_step first (first-step flag, one-time kernel attributes)")
         import torch.distributed as dist
@@ -757,11 +870,17 @@ class HipEngine:
         return self._logits[:B], self._loss
 
     def sync_replicas(self, process_group=None, src: int = 0):
-        """Make every rank's trainable state identical to rank ``src``'s (parameters, momentum, BatchNorm running
-        statistics, step counter semantics): call once after the engines have been loaded and before the first DP step."""
+        """Make every rank's trainable state identical to rank ``src``'s (parameters, momentum / exp_avg, exp_avg_sq, BatchNorm
+        running statistics, step counter semantics): call once after the engines have been loaded and before the first DP step.
+        ``exp_avg_sq`` travels only where it exists, that is after the first Adam / AdamW step, which every rank takes together;
+        before it the buffer is unallocated on all of them and starts from zero, so a plain-SGD run allocates and sends nothing more
+        than it did."""
         self.dp_flush()
         import torch.distributed as dist
-        for t in (self.params, self.momentum, self.running_mean, self.running_var):
+        state = [self.params, self.momentum, self.running_mean, self.running_var]
+        if self.exp_avg_sq is not None:
+            state.append(self.exp_avg_sq)
+        for t in state:
             dist.broadcast(t, src=src, group=process_group)
 
     def average_bn_buffers(self, process_group=None):

@@ -33,6 +33,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import _lib
+from ..engine import OptimPlan, _group_hypers
 from ..optim import build_optimizer
 from . import clip_load
 from .feature import create_dataloader, extract_text_features
@@ -339,6 +341,7 @@ class ClassifierBase(nn.Module):
         self.normalize_visual_output = config.TRAIN.NORMALIZE_VISUAL_FEATURE
         if not config.TRAIN.USE_CHANNEL_BN:
             self.channel_bn = nn.Identity()
+        self._fused_optimizer = bool(config.TRAIN.FUSED_OPTIMIZER)     # fused_optimizer_plan
 
         visual = self.backbone.visual
         # MODEL.WEIGHT_FORMAT, when the config has the key, is authoritative (an explicit "bf16" is not overridden by the
@@ -386,9 +389,9 @@ class ClassifierBase(nn.Module):
         return self.layers(outputs)
 
     # ---- fused step ----------------------------------------------------------------------
-    def can_fuse(self, criterion, optimizer) -> bool:
-        """True when one ``pevit_train_forward_backward`` (cross-entropy) or ``pevit_train_forward_backward_bce`` (multi-label
-        BCEWithLogitsLoss) + ``pevit_sgd_step`` is exactly the reference step."""
+    def _fusable_step(self, criterion) -> bool:
+        """The part of the reference step the engine's fused forward/backward computes exactly: the criterion, BatchNorm and
+        head conditions shared by ``can_fuse`` and ``fused_optimizer_plan``."""
         if isinstance(criterion, nn.BCEWithLogitsLoss):
             if criterion.weight is not None or criterion.pos_weight is not None or criterion.reduction != "mean":
                 return False
@@ -396,11 +399,18 @@ class ClassifierBase(nn.Module):
             return False
         elif criterion.reduction != "mean" or getattr(criterion, "label_smoothing", 0.0) != 0.0 or criterion.ignore_index >= 0:
             return False
-        if type(optimizer) is not torch.optim.SGD or not isinstance(self.channel_bn, nn.BatchNorm1d):
+        if not isinstance(self.channel_bn, nn.BatchNorm1d):
             return False
         if self.normalize_visual_output or self.logit_scale.requires_grad:
             return False
         if self.channel_bn.momentum != 0.1 or self.channel_bn.eps != 1e-5:
+            return False
+        return True
+
+    def can_fuse(self, criterion, optimizer) -> bool:
+        """True when one ``pevit_train_forward_backward`` (cross-entropy) or ``pevit_train_forward_backward_bce`` (multi-label
+        BCEWithLogitsLoss) + ``pevit_sgd_step`` is exactly the reference step."""
+        if type(optimizer) is not torch.optim.SGD or not self._fusable_step(criterion):
             return False
         live = [g for g in optimizer.param_groups if len(g["params"]) > 0]
         if not live:
@@ -416,16 +426,51 @@ class ClassifierBase(nn.Module):
         theirs = {id(p) for g in live for p in g["params"]}
         return mine == theirs
 
-    def fused_train_step(self, images, target, optimizer, logits_out=None, loss_out=None):
+    def _flat_layout(self):
+        """The engine's flat parameter buffer as ordered (parameter, offset, numel): the tower's trainable tensors, then the head."""
+        out, off = [], 0
+        for p in list(self.backbone.visual._trainable_params()) + [self.layers[0].weight, self.layers[0].bias]:
+            out.append((p, off, p.numel()))
+            off += p.numel()
+        return out
+
+    def fused_optimizer_plan(self, criterion, optimizer):
+        """An ``OptimPlan`` when the step ``can_fuse`` refuses only because of its optimizer is still one engine call: the same
+        fused forward/backward, then ``pevit_optim_step`` (torch.optim.Adam / AdamW, SGD whose groups differ in lr or weight decay:
+        ``plan_fused_optimizer``).  None otherwise, when ``can_fuse`` has been overridden to refuse a step it would take, and
+        with ``TRAIN.FUSED_OPTIMIZER False`` (torch's own ``step()`` on the engine's gradients).  On this route the torch optimizer's
+        ``state`` stays empty, as it does for fused SGD: the moments live in the engine."""
+        if not self._fused_optimizer or not self._fusable_step(criterion):
+            return None
+        visual = self.backbone.visual
+        if visual.class_embedding.device.type == "cuda":
+            self.engine()                             # (attaching fills in which tensors never receive a gradient)
+        layout = self._flat_layout()
+        dead = {id(p) for n, p in zip(visual._trainable_names, visual._trainable_params()) if not visual._has_grad.get(n, True)}
+        mask = torch.ones(sum(k for _, _, k in layout), dtype=torch.uint8)
+        for p, off, k in layout:
+            if id(p) in dead:
+                mask[off:off + k] = 0
+        if {id(p) for p in self.parameters() if p.requires_grad} != {id(p) for p, _, _ in layout}:
+            return None                               # a trainable tensor the engine's flat buffer does not hold
+        return plan_fused_optimizer(optimizer, layout, mask)
+
+    def fused_train_step(self, images, target, optimizer, logits_out=None, loss_out=None, plan=None):
         """One reference train_one iteration as one engine call.  ``logits_out`` (B, C) / ``loss_out`` (1,): rows of the caller's
-        epoch buffers the engine writes straight into; without them the results are copies of the engine's per-step buffers."""
+        epoch buffers the engine writes straight into; without them the results are copies of the engine's per-step buffers.
+        ``plan`` (``fused_optimizer_plan``): the update is the planned optimizer's instead of plain SGD's; either way the
+        hyper-parameters are read from ``optimizer.param_groups`` on every step."""
         eng = self.engine()
         eng.ensure_batch(images.shape[0])
         g = next(g for g in optimizer.param_groups if len(g["params"]) > 0)
         img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
-        logits, loss = eng.train_step(img, target.contiguous(), lr=g["lr"], momentum=g["momentum"],
-                                      weight_decay=g["weight_decay"], bn_training=self.channel_bn.training,
-                                      nesterov=bool(g["nesterov"]), logits_out=logits_out, loss_out=loss_out)
+        if plan is not None:
+            logits, loss = eng.train_step(img, target.contiguous(), bn_training=self.channel_bn.training, logits_out=logits_out,
+                                          loss_out=loss_out, optimizer=plan.refresh(optimizer))
+        else:
+            logits, loss = eng.train_step(img, target.contiguous(), lr=g["lr"], momentum=g["momentum"],
+                                          weight_decay=g["weight_decay"], bn_training=self.channel_bn.training,
+                                          nesterov=bool(g["nesterov"]), logits_out=logits_out, loss_out=loss_out)
         if self.channel_bn.training:
             self._bn_steps = getattr(self, "_bn_steps", 0) + 1       # folded into num_batches_tracked once per epoch
         if logits_out is None:
@@ -469,6 +514,61 @@ class ClassifierBase(nn.Module):
         if n and isinstance(self.channel_bn, nn.BatchNorm1d):
             self.channel_bn.num_batches_tracked += n
         self._bn_steps = 0
+
+
+def plan_fused_optimizer(optimizer, layout, grad_mask=None):
+    """``OptimPlan`` of a torch optimizer over the engine's flat parameter buffer, or None when the fused kernel
+    (csrc/optim.hip) does not compute its ``step()``.  Pure: no GPU, no engine.
+
+    ``layout``: the ordered (parameter, offset, numel) list of the flat buffer.  ``grad_mask``: optional uint8 over the buffer, 0
+    where a parameter never receives a gradient (KAdaptation's v_proj_adapter1_*).  Planned: ``torch.optim.SGD`` (no dampening,
+    not ``maximize``) whose live groups DIFFER in lr or weight decay -- one set of hyper-parameters is ``can_fuse``'s case and
+    keeps the plain-SGD kernel -- and exact-type ``torch.optim.Adam`` / ``torch.optim.AdamW`` without ``amsgrad``, ``maximize``,
+    ``differentiable`` or a tensor ``lr``.  None: any other optimizer (RMSprop, ...), more than 8 live groups, a parameter outside
+    the layout (frozen ones apart: torch skips them, ``TRAIN.TWO_LR`` puts the whole trunk in a group) or in two groups.
+    Elements of parameters in no live group, and where ``grad_mask`` is 0, get 255: the kernel leaves them alone, as torch leaves
+    a parameter whose ``.grad`` is None."""
+    live = [(j, g) for j, g in enumerate(optimizer.param_groups) if len(g["params"]) > 0]
+    if not live or len(live) > _lib.OPTIM_MAX_GROUPS:
+        return None
+    if type(optimizer) is torch.optim.SGD:
+        kind = "sgd"
+        for _, g in live:
+            if g["dampening"] != 0 or g.get("maximize", False) or g.get("differentiable", False):
+                return None
+        g0 = live[0][1]
+        if any((g["momentum"], g["nesterov"]) != (g0["momentum"], g0["nesterov"]) for _, g in live):
+            return None                                       # (one first-step rule and one momentum buffer form per launch)
+        if all((g["lr"], g["weight_decay"]) == (g0["lr"], g0["weight_decay"]) for _, g in live):
+            return None                                       # can_fuse's case
+    elif type(optimizer) in (torch.optim.Adam, torch.optim.AdamW):
+        # torch >= 2.2 builds AdamW as an Adam subclass with decoupled_weight_decay=True; an Adam given that flag is AdamW too
+        kind = "adamw" if type(optimizer) is torch.optim.AdamW else "adam"
+        for _, g in live:
+            if g.get("amsgrad", False) or g.get("maximize", False) or g.get("differentiable", False) or g.get("capturable", False):
+                return None
+            if torch.is_tensor(g["lr"]) or torch.is_tensor(g["betas"][0]) or torch.is_tensor(g["betas"][1]):
+                return None
+            if bool(g.get("decoupled_weight_decay", kind == "adamw")) != (kind == "adamw"):
+                return None
+    else:
+        return None
+    where = {id(p): (off, k) for p, off, k in layout}
+    n = sum(k for _, _, k in layout)
+    group_of = torch.full((n,), _lib.OPTIM_NO_GRAD, dtype=torch.uint8)
+    seen = set()
+    for idx, (_, g) in enumerate(live):
+        for p in g["params"]:
+            if not p.requires_grad and id(p) not in where:
+                continue                                      # frozen tensors in a group (TWO_LR's trunk): .grad stays None, torch skips them
+            if id(p) not in where or id(p) in seen:
+                return None
+            seen.add(id(p))
+            off, k = where[id(p)]
+            group_of[off:off + k] = idx
+    if grad_mask is not None:
+        group_of[torch.as_tensor(grad_mask).cpu().reshape(-1) == 0] = _lib.OPTIM_NO_GRAD
+    return OptimPlan(kind, [_group_hypers(kind, g) for _, g in live], group_of, [j for j, _ in live])
 
 
 def adjust_learning_rate(optimizer, epoch, config):
@@ -623,6 +723,9 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
     metric = get_metric(config.TEST.METRIC)
     outputs, targets, step_losses, step_sizes = [], [], [], []
     fused = model.can_fuse(criterion, optimizer)
+    # the optimizers can_fuse leaves out (Adam, AdamW, SGD with several lr / weight decays) keep the same one-call step through a plan
+    plan = None if fused else model.fused_optimizer_plan(criterion, optimizer)
+    fused = fused or plan is not None
     dev = config.GPUS[0]
     single = len(config.GPUS) == 1
     # epoch buffers the fused step writes its logits / loss straight into (no per-step copies of the engine's buffers)
@@ -659,7 +762,7 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
                 direct = out_buf is not None and row + n <= out_buf.shape[0] and step < loss_buf.shape[0]
                 output, loss = model.fused_train_step(images, target, optimizer,
                                                       out_buf[row:row + n] if direct else None,
-                                                      loss_buf[step:step + 1] if direct else None)
+                                                      loss_buf[step:step + 1] if direct else None, plan=plan)
                 row += n if direct else 0
                 step += 1 if direct else 0
             else:

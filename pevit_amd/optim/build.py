@@ -2,10 +2,14 @@
 
 The object returned is a stock ``torch.optim`` optimizer over the *same Parameter objects* the model
 exposes, so schedulers / ``adjust_learning_rate`` keep working on ``param_groups``.  When the
-configuration is the plain one the reference's yaml files use (SGD, momentum, no Nesterov, one weight
-decay for every trainable tensor) the harness executes the update with the fused HIP kernel
-(``pevit_sgd_step``) and reads ``lr`` / ``momentum`` / ``weight_decay`` from ``param_groups`` each step;
-any other configuration runs this optimizer's own ``step()`` on the gradients the engine produced.
+configuration is the plain one the reference's yaml files use (SGD, momentum, one weight decay for
+every trainable tensor) the harness executes the update with the fused HIP kernel
+(``pevit_sgd_step``); for ``adam`` / ``adamW``, ``TRAIN.TWO_LR`` and ``TRAIN.WITHOUT_WD_LIST`` (SGD groups
+that differ in learning rate or weight decay) with the fused per-group kernel (``pevit_optim_step``,
+``ClassifierBase.fused_optimizer_plan``).  Either way ``lr`` / ``weight_decay`` / momentum / betas are read
+from ``param_groups`` each step and this optimizer's own ``state`` stays empty: the moments live in the
+engine.  Any other configuration (``rmsprop``, ``TRAIN.FUSED_OPTIMIZER False``) runs this optimizer's own
+``step()`` on the gradients the engine produced.
 """
 import torch.nn as nn
 import torch.optim as optim
