@@ -218,6 +218,27 @@ int pevit_predict(pevit_ctx* ctx, void* stream, const float* images, const float
                   float* logits, float* feat_or_null, int batch);
 int pevit_predict_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const float* running_mean, const float* running_var,
                      float* logits, float* feat_or_null, int batch);   /* needs pevit_set_input_norm */
+/* ---- the CLIP text tower (CLIP.encode_text, model.py:1153-1168): token ids (S x N) int64 -> text features (S x D) f32 in one call.
+ * A text context is a pevit_ctx like any other -- method PEVIT_NONE, H = width / 64 heads, N = context_length tokens per prompt,
+ * causal attention -- so pevit_arena_bytes, pevit_bind, pevit_load_block (q rows pre-scaled by 1/8 as for the image tower) and
+ * pevit_ctx_destroy work on it unchanged.  It is inference-only: pevit_workspace_bytes returns the size of the inference layout
+ * (one set of activation slots for all layers) and max_batch of pevit_bind counts PROMPTS.  Limits: width a multiple of 128 up to
+ * 1024, out_dim a multiple of 8, 1 <= context_length <= 128, weight_format PEVIT_W_BF16 or PEVIT_W_F32_VERIFY (the fp8 formats
+ * are refused).  Every image-side and training entry point refuses a text context with a message, and pevit_encode_text refuses
+ * an image context. */
+typedef struct pevit_text_dims {
+    int32_t width, layers, context_length, vocab_size, out_dim, weight_format;
+} pevit_text_dims;
+int pevit_text_create(const pevit_text_dims* dims, pevit_ctx** out);
+/* device pointers, f32: token_embedding [V][E] (kept f32 in the arena: the embedding is exact), positional_embedding [N][E],
+ * ln_final weight / bias [E], text_projection [E][D] */
+int pevit_load_text_stem(pevit_ctx* ctx, void* stream, const float* token_embedding, const float* positional_embedding,
+                         const float* ln_final_weight, const float* ln_final_bias, const float* text_projection);
+/* embed -> the L blocks in their inference forms with causal attention -> the row of each prompt's FIRST largest token id (the
+ * end-of-text marker; torch.argmax) through ln_final -> @ text_projection.  tokens: device int64 [prompts][N]; ids outside
+ * [0, V - 1] are clamped by the embedding kernel (callers check the range).  prompts in [1, max_batch]; larger sets are split
+ * by the caller. */
+int pevit_encode_text(pevit_ctx* ctx, void* stream, const int64_t* tokens, float* features, int prompts);
 /* whole fine-tune step: zero_grad -> forward -> CE -> backward -> (caller all-reduces) -> SGD */
 int pevit_train_forward_backward(pevit_ctx* ctx, void* stream, const float* images, const int64_t* labels,
                                  float* running_mean, float* running_var, int bn_training, float* logits,
@@ -293,6 +314,9 @@ int pevit_op_attn_fwd(void* stream, const void* q, const void* k, const void* v,
                       int B, int H, int N);
 int pevit_op_attn_bwd(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
                       const void* dout, int lddo, const float* lse, void* dqkv, int ld, int B, int H, int N);
+/* causal attention of the text tower (query x sees the keys y <= x), forward only, 1 <= N <= 128: operands as pevit_op_attn_fwd,
+ * no log-sum-exp */
+int pevit_op_attn_fwd_causal(void* stream, const void* q, const void* k, const void* v, void* out, int ldo, int B, int H, int N);
 int pevit_op_cast_bf16(void* stream, const float* src, void* dst, size_t n, float scale);
 /* q16: Q as a bf16 panel [E][64] (Q_q | Q_v), the production operand of the forward delta */
 int pevit_op_delta_add(void* stream, void* qbuf, void* vbuf, const float* t, const void* q16_bf16, const float* bias,

@@ -25,6 +25,11 @@ GEMM_KNOBS = ("config", "stagger", "big", "ksplit", "ksplit_small", "ksplit_stag
               "skinny_slices", "streamk", "persistent")           # enum pevit_gemm_knob
 
 
+class PevitTextDims(C.Structure):
+    """pevit_text_dims of include/pevit_hip.h"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "layers", "context_length", "vocab_size", "out_dim", "weight_format")]
+
+
 class PevitGemmExArgs(C.Structure):
     """pevit_gemm_ex_args of include/pevit_hip.h (the test-only pevit_op_gemm_ex); zero-initialised = nothing set"""
     _fields_ = ([(n, c_void_p) for n in ("A", "B", "B2", "bias", "resid", "bscale", "oscale", "out_f32", "out_f32_2", "out_bf16",
@@ -100,6 +105,9 @@ SIGNATURES = {
     "pevit_head_forward_backward": (c_int, [P, P, P, P, P, P, c_int, P, P, P, c_int]),
     "pevit_predict": (c_int, [P, P, P, P, P, P, P, c_int]),
     "pevit_predict_u8": (c_int, [P, P, P, P, P, P, P, c_int]),
+    "pevit_text_create": (c_int, [C.POINTER(PevitTextDims), C.POINTER(c_void_p)]),
+    "pevit_load_text_stem": (c_int, [P, P] + [P] * 5),
+    "pevit_encode_text": (c_int, [P, P, P, P, c_int]),
     "pevit_zero_grads": (c_int, [P, P]),
     "pevit_sgd_step": (c_int, [P, P, c_float, c_float, c_float, c_float, c_int]),
     "pevit_set_optim_state": (c_int, [P, P, P]),
@@ -130,6 +138,7 @@ SIGNATURES = {
     "pevit_op_ln_bwd_scaled": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, P]),
     "pevit_op_attn_fwd": (c_int, [P, P, P, P, P, c_int, P, c_int, c_int, c_int]),
     "pevit_op_attn_bwd": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int]),
+    "pevit_op_attn_fwd_causal": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int]),
     "pevit_op_cast_bf16": (c_int, [P, P, P, c_size_t, c_float]),
     "pevit_op_delta_add": (c_int, [P, P, P, P, P, P, c_float, c_int, c_int, c_int]),
     "pevit_op_attn_fwd_delta": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int, P, c_int, c_int, c_int]),

@@ -103,6 +103,10 @@ struct pevit_ctx {
     bool fp8 = false;         // frozen block weights as e4m3 codes + per-channel scales (fp8.hip)
     bool fp8act = false;      // ... and fp8 A operands in the forward frozen products (PEVIT_W_FP8_ACT)
     bool f32 = false;         // f32-class verification mode: every bf16-declared buffer holds f32 (verify.hip)
+    bool text = false;        // CLIP text tower (pevit_text_create): N = context_length, inference only, pevit_encode_text is its one forward
+    bool causal = false;      // ... its attention is causal (attn_core_fwd passes this to the attention launch)
+    int V = 0;                // ... vocabulary size (rows of the token-embedding table)
+    size_t a_tok = 0;         // ... arena offset of the f32 token-embedding table [V][E]
     size_t es = 2;            // bytes per element of those buffers
     float ascale;             // 160 (model.py:564) or alpha/r (lora_model.py:491)
     // arena
@@ -290,6 +294,47 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer = false) {
     return w;
 }
 
+// the per-layer weight slots of the arena (c->blk must hold c->L entries): what pevit_load_block fills
+void carve_block_arena(pevit_ctx* c, Carver& cv) {
+    const size_t E = c->E;
+    for (int l = 0; l < c->L; ++l) {
+        BlockArena& b = c->blk[l];
+        b.wpan = b.sqkv = b.so = b.sfc = b.spr = 0;
+        if (c->fp8) {
+            // one byte per weight; rows padded to the largest tile (256) so that clamped tile rows stay readable
+            const size_t r1 = align_up(E, 256), r3 = align_up(3 * E, 256), r4 = align_up(4 * E, 256);
+            b.wqkv = cv.take(r3 * E);
+            b.wpan = cv.take(128 * E * 2);
+            b.wqkvT = cv.take(E * (size_t)c->NQ * 2);          // QKV backward keeps bf16: its K mixes frozen rows with the adapter panel
+            b.wo = cv.take(r1 * E);       b.woT = cv.take(r1 * E);
+            b.wfc = cv.take(r4 * E);      b.wfcT = cv.take(r1 * 4 * E);
+            b.wpr = cv.take(r1 * 4 * E);  b.wprT = cv.take(r4 * E);
+            b.sqkv = cv.take(3 * E * 4); b.so = cv.take(E * 4); b.sfc = cv.take(4 * E * 4); b.spr = cv.take(E * 4);
+        } else {
+            const size_t es = c->es;
+            b.wqkv = cv.take((size_t)c->NQpad * E * es);
+            b.wqkvT = cv.take(E * (size_t)c->NQ * es);
+            b.wo = cv.take(E * E * es);   b.woT = cv.take(E * E * es);
+            b.wfc = cv.take(4 * E * E * es); b.wfcT = cv.take(4 * E * E * es);
+            b.wpr = cv.take(4 * E * E * es); b.wprT = cv.take(4 * E * E * es);
+        }
+        b.bqkv = cv.take(3 * E * 4); b.bo = cv.take(E * 4); b.bfc = cv.take(4 * E * 4); b.bpr = cv.take(E * 4);
+        b.ln1w = cv.take(E * 4); b.ln1b = cv.take(E * 4); b.ln2w = cv.take(E * 4); b.ln2b = cv.take(E * 4);
+        b.q32 = cv.take(E * 64 * 4); b.qT = cv.take(64 * E * c->es); b.q16 = cv.take(E * 64 * 2);
+        b.wd = cv.take(64 * E * c->es); b.wdT = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); b.wuT = cv.take(64 * E * c->es);
+    }
+}
+
+// the image-side and training entry points on a text context (its workspace holds the inference layout only, it has no stem, no
+// head and no parameters), checked on the host before anything else
+int refuse_text(const pevit_ctx* c, const char* who) {
+    if (c && c->text) {
+        pevit_set_error("%s: this is a text context (pevit_text_create); it runs pevit_encode_text only", who);
+        return -1;
+    }
+    return 0;
+}
+
 template <typename T>
 inline T* at(char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
 // advance a bf16-declared pointer by `elems` elements of the context's storage type (bf16, or f32 in verification mode)
@@ -344,32 +389,7 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
     if (!c->blk) { pevit_set_error("ctx_create: out of host memory"); pevit_ctx_destroy(c); return -1; }
     Carver cv;
     const size_t E = c->E;
-    for (int l = 0; l < c->L; ++l) {
-        BlockArena& b = c->blk[l];
-        b.wpan = b.sqkv = b.so = b.sfc = b.spr = 0;
-        if (c->fp8) {
-            // one byte per weight; rows padded to the largest tile (256) so that clamped tile rows stay readable
-            const size_t r1 = align_up(E, 256), r3 = align_up(3 * E, 256), r4 = align_up(4 * E, 256);
-            b.wqkv = cv.take(r3 * E);
-            b.wpan = cv.take(128 * E * 2);
-            b.wqkvT = cv.take(E * (size_t)c->NQ * 2);          // QKV backward keeps bf16: its K mixes frozen rows with the adapter panel
-            b.wo = cv.take(r1 * E);       b.woT = cv.take(r1 * E);
-            b.wfc = cv.take(r4 * E);      b.wfcT = cv.take(r1 * 4 * E);
-            b.wpr = cv.take(r1 * 4 * E);  b.wprT = cv.take(r4 * E);
-            b.sqkv = cv.take(3 * E * 4); b.so = cv.take(E * 4); b.sfc = cv.take(4 * E * 4); b.spr = cv.take(E * 4);
-        } else {
-            const size_t es = c->es;
-            b.wqkv = cv.take((size_t)c->NQpad * E * es);
-            b.wqkvT = cv.take(E * (size_t)c->NQ * es);
-            b.wo = cv.take(E * E * es);   b.woT = cv.take(E * E * es);
-            b.wfc = cv.take(4 * E * E * es); b.wfcT = cv.take(4 * E * E * es);
-            b.wpr = cv.take(4 * E * E * es); b.wprT = cv.take(4 * E * E * es);
-        }
-        b.bqkv = cv.take(3 * E * 4); b.bo = cv.take(E * 4); b.bfc = cv.take(4 * E * 4); b.bpr = cv.take(E * 4);
-        b.ln1w = cv.take(E * 4); b.ln1b = cv.take(E * 4); b.ln2w = cv.take(E * 4); b.ln2b = cv.take(E * 4);
-        b.q32 = cv.take(E * 64 * 4); b.qT = cv.take(64 * E * c->es); b.q16 = cv.take(E * 64 * 2);
-        b.wd = cv.take(64 * E * c->es); b.wdT = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); b.wuT = cv.take(64 * E * c->es);
-    }
+    carve_block_arena(c, cv);
     c->a_conv = cv.take(align_up(E, 128) * (size_t)c->Kpatch * c->es);
     c->a_cls = cv.take(E * 4);
     c->a_pos = cv.take((size_t)c->N * E * 4);
@@ -407,6 +427,56 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
     return 0;
 }
 
+// The CLIP text tower as a context: the block arena of pevit_ctx_create (method PEVIT_NONE) and, in place of the image stem, the f32
+// token-embedding table, the positional embedding, ln_final and text_projection^T.  No HIP call: sizes only.
+extern "C" int pevit_text_create(const pevit_text_dims* dims, pevit_ctx** out) {
+    if (!dims || !out) { pevit_set_error("text_create: null argument"); return -1; }
+    const pevit_text_dims d = *dims;
+    if (d.width <= 0 || d.width % 128 != 0 || d.width > 1024) {
+        pevit_set_error("text_create: width %d must be a multiple of 128 in (0,1024]", d.width); return -1;
+    }
+    if (d.layers <= 0) { pevit_set_error("text_create: bad layer count %d", d.layers); return -1; }
+    if (d.context_length < 1 || d.context_length > 128) {
+        pevit_set_error("text_create: context_length %d outside [1,128] (the causal attention kernel keeps K and V of a prompt in LDS)", d.context_length); return -1;
+    }
+    if (d.vocab_size < 1) { pevit_set_error("text_create: bad vocab_size %d", d.vocab_size); return -1; }
+    if (d.out_dim <= 0 || d.out_dim % 8 != 0) { pevit_set_error("text_create: out_dim %d must be a positive multiple of 8", d.out_dim); return -1; }
+    if (d.weight_format == PEVIT_W_FP8_E4M3 || d.weight_format == PEVIT_W_FP8_ACT) {
+        pevit_set_error("text_create: the fp8 weight formats were built for the image towers; the text tower takes bf16 or f32-verify"); return -1;
+    }
+    if (d.weight_format != PEVIT_W_BF16 && d.weight_format != PEVIT_W_F32_VERIFY) {
+        pevit_set_error("text_create: unknown weight_format %d", d.weight_format); return -1;
+    }
+    pevit_ctx* c = new (std::nothrow) pevit_ctx();
+    if (!c) { pevit_set_error("text_create: out of host memory"); return -1; }
+    c->d = pevit_dims{};
+    c->d.width = d.width; c->d.layers = d.layers; c->d.out_dim = d.out_dim; c->d.method = PEVIT_NONE; c->d.num_classes = 1;
+    c->d.weight_format = d.weight_format;
+    c->text = true; c->causal = true; c->V = d.vocab_size;
+    c->E = d.width; c->L = d.layers; c->H = d.width / 64; c->P = 0; c->R = 0;
+    c->G2 = 0; c->N = d.context_length; c->D = d.out_dim; c->C = 1; c->Kpatch = 0;
+    c->NQ = 3 * c->E + 64; c->NQpad = (int)align_up((size_t)c->NQ, 128);
+    c->ascale = 0.f;
+    c->f32 = d.weight_format == PEVIT_W_F32_VERIFY;
+    c->es = c->f32 ? 4 : 2;
+    c->sk_slots = c->f32 ? 0 : pevit_gemm_sk_slots();
+    c->blk = new (std::nothrow) BlockArena[c->L];
+    if (!c->blk) { pevit_set_error("text_create: out of host memory"); pevit_ctx_destroy(c); return -1; }
+    Carver cv;
+    const size_t E = c->E;
+    carve_block_arena(c, cv);
+    c->a_tok = cv.take((size_t)c->V * E * 4);                          // f32: the embedding is exact
+    c->a_pos = cv.take((size_t)c->N * E * 4);
+    c->a_lnpost_w = cv.take(E * 4); c->a_lnpost_b = cv.take(E * 4);    // ln_final
+    c->a_proj = cv.take(align_up((size_t)c->D, 128) * E * c->es);      // [D][E]  (text_projection^T)
+    c->a_conv = c->a_cls = c->a_lnpre_w = c->a_lnpre_b = c->a_projT = c->a_phm = 0;
+    c->arena_bytes = cv.off;
+    c->p_layer0 = 0; c->p_layer_stride = 0;
+    c->n_tower = 0; c->p_head_w = 0; c->p_head_b = 0; c->n_total = 0;
+    *out = c;
+    return 0;
+}
+
 extern "C" void pevit_ctx_destroy(pevit_ctx* c) {
     if (!c) return;
     for (int i = 0; i < 2 * c->prof_cap; ++i) (void)hipEventDestroy(c->prof_ev[i]);
@@ -422,7 +492,7 @@ extern "C" void pevit_ctx_destroy(pevit_ctx* c) {
 extern "C" size_t pevit_arena_bytes(const pevit_ctx* c) { return c ? c->arena_bytes : 0; }
 extern "C" size_t pevit_workspace_bytes(const pevit_ctx* c, int batch) {
     if (!c || batch <= 0) return 0;
-    return layout_workspace(c, batch).total;
+    return layout_workspace(c, batch, c->text).total;      // a text context is inference-only: batch counts prompts
 }
 extern "C" size_t pevit_num_tower_params(const pevit_ctx* c) { return c ? c->n_tower : 0; }
 extern "C" size_t pevit_num_params(const pevit_ctx* c) { return c ? c->n_total : 0; }
@@ -739,7 +809,10 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
         }
         AttnArgs a = attn_args(c, B, l);
         a.out_fp8 = attn8;
-        if (c->f32) {
+        if (c->causal) {        // the text tower (attn_causal.hip): q, k, v in, out written, nothing else
+            if (c->f32) CHECK(pevit_launch_attn_fwd_causal_f32(a, s));
+            else PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2, pevit_launch_attn_fwd_causal(a, s));
+        } else if (c->f32) {
             CHECK(pevit_launch_attn_fwd_f32(a, s));
         } else {
             if (pl.infer) a.lse = nullptr;
@@ -1168,6 +1241,7 @@ int reduce_adapter_grads(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl,
 // walked one call at a time (reference-side code that iterates visual.transformer.resblocks) and differentiated in reverse.
 extern "C" int pevit_blocks_forward(pevit_ctx* c, void* stream, const float* x_nbe, float* y_nbe, int B, int save_for_backward,
                                     int l_lo, int l_hi) {
+    CHECK(refuse_text(c, "blocks_forward"));
     CHECK(check_ready(c, B, "blocks_forward"));
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("blocks_forward: bad block range [%d, %d)", l_lo, l_hi); return -1; }
     hipStream_t s = (hipStream_t)stream;
@@ -1189,6 +1263,7 @@ extern "C" int pevit_transformer_forward(pevit_ctx* c, void* stream, const float
 // dy (gradient of the output of block l_hi-1) -> dx (gradient of the input of block l_lo, may be NULL); the adapter gradients of
 // exactly these blocks are accumulated into the flat gradient buffer
 extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy_nbe, float* dx_nbe, int B, int l_lo, int l_hi) {
+    CHECK(refuse_text(c, "blocks_backward"));
     CHECK(check_ready(c, B, "blocks_backward"));
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("blocks_backward: bad block range [%d, %d)", l_lo, l_hi); return -1; }
     CHECK(check_saved(c, Saved::blocks, B, -1, "blocks_backward"));
@@ -1211,6 +1286,7 @@ extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy
 // the activations; the softmax probabilities are recomputed from q, k and lse (attn_probs.hip) when asked for.
 extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, const float* x_nbe, float* y_nbe, int B,
                                        int save_for_backward, float* weights, int average_weights) {
+    CHECK(refuse_text(c, "attention_forward"));
     CHECK(check_ready(c, B, "attention_forward"));
     if (layer < 0 || layer >= c->L) { pevit_set_error("attention_forward: layer %d outside [0, %d)", layer, c->L); return -1; }
     if (c->fp8act) {
@@ -1250,6 +1326,7 @@ extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, co
 // accumulated into the flat gradient buffer exactly as pevit_blocks_backward over [layer, layer + 1) does (incl. its share of the
 // shared phm_rule factors).  Adapter / Compacter / the frozen tower: stock attention with frozen weights, dx only.
 extern "C" int pevit_attention_backward(pevit_ctx* c, void* stream, int layer, const float* dy_nbe, float* dx_nbe, int B) {
+    CHECK(refuse_text(c, "attention_backward"));
     CHECK(check_ready(c, B, "attention_backward"));
     if (layer < 0 || layer >= c->L) { pevit_set_error("attention_backward: layer %d outside [0, %d)", layer, c->L); return -1; }
     CHECK(check_saved(c, Saved::attention, B, layer, "attention_backward"));
@@ -1367,6 +1444,7 @@ extern "C" int pevit_set_step_gate(pevit_ctx* c, void* event) {
 extern "C" int pevit_load_stem(pevit_ctx* c, void* stream, const float* conv_w, const float* cls, const float* pos,
                                const float* lnpre_w, const float* lnpre_b, const float* lnpost_w, const float* lnpost_b,
                                const float* proj) {
+    CHECK(refuse_text(c, "load_stem"));
     if (!c || !c->arena) { pevit_set_error("load_stem: context not bound"); return -1; }
     hipStream_t s = (hipStream_t)stream;
     char* A = c->arena;
@@ -1385,6 +1463,7 @@ extern "C" int pevit_load_stem(pevit_ctx* c, void* stream, const float* conv_w, 
 }
 
 extern "C" int pevit_load_phm_rule(pevit_ctx* c, void* stream, const float* phm_rule) {
+    CHECK(refuse_text(c, "load_phm_rule"));
     if (!c || !c->arena) { pevit_set_error("load_phm_rule: context not bound"); return -1; }
     HIP_OK(hipMemcpyAsync(c->arena + c->a_phm, phm_rule, 64 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
@@ -1393,6 +1472,7 @@ extern "C" int pevit_load_phm_rule(pevit_ctx* c, void* stream, const float* phm_
 // Preprocessing constants of the uint8 entry points: x = (u8 / 255 - mean[c]) / std[c], the dataset transforms of the reference
 // (ToTensor + Normalize(INPUT.MEAN, INPUT.STD), feature.py:537-542; resources/model/vitb32_CLIP.yaml:4-6)
 extern "C" int pevit_set_input_norm(pevit_ctx* c, const float* mean3, const float* std3) {
+    CHECK(refuse_text(c, "set_input_norm"));
     if (!c || !mean3 || !std3) { pevit_set_error("set_input_norm: null argument"); return -1; }
     for (int i = 0; i < 3; ++i) {
         if (!(std3[i] > 0.f)) { pevit_set_error("set_input_norm: std[%d] = %g must be positive", i, (double)std3[i]); return -1; }
@@ -1412,6 +1492,7 @@ extern "C" int pevit_visual_forward(pevit_ctx* c, void* stream, const float* ima
 // the same from uint8 pixels (B,3,R,R): the reference's ToTensor + Normalize run inside the patch gather (pevit_set_input_norm)
 extern "C" int pevit_visual_forward_u8(pevit_ctx* c, void* stream, const uint8_t* images, float* feat, int B,
                                        int save_for_backward) {
+    CHECK(refuse_text(c, "visual_forward_u8"));
     if (c && !c->img_norm_set) { pevit_set_error("visual_forward_u8: call pevit_set_input_norm first"); return -1; }
     return visual_forward_impl(c, stream, images, 1, feat, B, save_for_backward);
 }
@@ -1419,6 +1500,7 @@ extern "C" int pevit_visual_forward_u8(pevit_ctx* c, void* stream, const uint8_t
 static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_any, int u8, float* feat, int B, int save_for_backward,
                                bool infer) {
     const float* images = (const float*)images_any;
+    CHECK(refuse_text(c, infer ? "predict" : "visual_forward"));
     CHECK(check_ready(c, B, infer ? "predict" : "visual_forward"));
     hipStream_t s = (hipStream_t)stream;
     if (infer) c->saved = SavedForward{};
@@ -1478,6 +1560,7 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
 // buffer, not last_loss.  batch 1 is legal (eval-mode BatchNorm takes no batch statistics).
 static int predict_impl(pevit_ctx* c, void* stream, const void* images, int u8, const float* running_mean, const float* running_var,
                         float* logits, float* feat_or_null, int B) {
+    CHECK(refuse_text(c, "predict"));
     CHECK(check_ready(c, B, "predict"));
     if (!c->params) { pevit_set_error("predict: parameters not set (the Linear head lives in the flat parameter buffer)"); return -1; }
     if (!images || !running_mean || !running_var || !logits) { pevit_set_error("predict: null argument"); return -1; }
@@ -1497,14 +1580,73 @@ extern "C" int pevit_predict(pevit_ctx* c, void* stream, const float* images, co
 }
 extern "C" int pevit_predict_u8(pevit_ctx* c, void* stream, const uint8_t* images, const float* running_mean, const float* running_var,
                                 float* logits, float* feat_or_null, int B) {
+    CHECK(refuse_text(c, "predict_u8"));
     if (c && !c->img_norm_set) { pevit_set_error("predict_u8: call pevit_set_input_norm first"); return -1; }
     return predict_impl(c, stream, images, 1, running_mean, running_var, logits, feat_or_null, B);
+}
+
+// ---- the CLIP text tower (pevit_text_create) ---------------------------------------------------------------------------------
+extern "C" int pevit_load_text_stem(pevit_ctx* c, void* stream, const float* token_embedding, const float* positional_embedding,
+                                    const float* ln_final_weight, const float* ln_final_bias, const float* text_projection) {
+    if (!c || !c->text) { pevit_set_error("load_text_stem: not a text context (pevit_text_create)"); return -1; }
+    if (!c->arena) { pevit_set_error("load_text_stem: context not bound"); return -1; }
+    if (!token_embedding || !positional_embedding || !ln_final_weight || !ln_final_bias || !text_projection) {
+        pevit_set_error("load_text_stem: null argument"); return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* A = c->arena;
+    const size_t E = c->E;
+    HIP_OK(hipMemcpyAsync(A + c->a_tok, token_embedding, (size_t)c->V * E * 4, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(A + c->a_pos, positional_embedding, (size_t)c->N * E * 4, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(A + c->a_lnpost_w, ln_final_weight, E * 4, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(A + c->a_lnpost_b, ln_final_bias, E * 4, hipMemcpyDeviceToDevice, s));
+    // text_projection is (E, D): features = x @ text_projection  ->  B operand [D][E] = its transpose, like visual.proj
+    HIP_OK(hipMemsetAsync(A + c->a_proj, 0, align_up((size_t)c->D, 128) * E * c->es, s));
+    CHECK(pevit_launch_transpose_bf16(text_projection, c->E, c->D, at<bf16>(A, c->a_proj), c->E, 0, 1.0f, s, c->f32));
+    return 0;
+}
+
+// tokens (S,N) int64 -> features (S,D) f32                              model.py:1153-1168
+extern "C" int pevit_encode_text(pevit_ctx* c, void* stream, const int64_t* tokens, float* features, int S) {
+    if (c && !c->text) { pevit_set_error("encode_text: this is an image context (pevit_ctx_create); text contexts come from pevit_text_create"); return -1; }
+    CHECK(check_ready(c, S, "encode_text"));
+    if (!tokens || !features) { pevit_set_error("encode_text: null argument"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    c->saved = SavedForward{};
+    c->lay = layout_workspace(c, S, true);
+    if (c->lay.total > c->ws_bytes_for_max) { pevit_set_error("encode_text: workspace too small (%zu < %zu)", c->ws_bytes_for_max, c->lay.total); return -1; }
+    const StepPlan pl = plan_step(c, S, true);
+    char* W = c->ws; char* A = c->arena;
+    const int E = c->E, N = c->N;
+    {
+        TextEmbedArgs a;     // straight into the first block's input slot
+        a.tokens = tokens; a.table = at<float>(A, c->a_tok); a.pos = at<float>(A, c->a_pos); a.x = at<float>(W, c->lay.sav[0].x_in);
+        a.S = S; a.N = N; a.E = E; a.V = c->V;
+        CHECK(pevit_launch_text_embed(a, s));
+    }
+    CHECK(blocks_forward(c, s, S, pl, false));
+    // the end-of-text row of every prompt -> ln_final -> @ text_projection
+    float* eot = at<float>(W, c->lay.w_dxn);                // [S][E] f32 scratch (free in a forward pass)
+    CHECK(pevit_launch_text_eot_gather(tokens, at<float>(W, c->lay.w_xfinal), eot, S, N, E, s));
+    {
+        LnFwdArgs a;
+        a.x = eot; a.gamma = at<float>(A, c->a_lnpost_w); a.beta = at<float>(A, c->a_lnpost_b); a.rows = S; a.E = E;
+        a.y_bf16 = at<bf16>(W, c->lay.w_xpost); a.f32 = c->f32;
+        CHECK(pevit_launch_ln_fwd(a, s));
+    }
+    {
+        GemmParams p = gp(at<bf16>(W, c->lay.w_xpost), E, at<bf16>(A, c->a_proj), E, c->D, S, c->D, E);
+        p.outf = features; p.ldo = c->D;
+        CHECK(gemm(c, EPI_F32, p, s));
+    }
+    return 0;
 }
 
 // dfeat (B,D) f32 -> adapter gradients (nothing below the first block is trainable).
 // Layers l_hi-1 .. l_lo; the entry work (proj^T, ln_post backward) belongs to the part that starts at L.  Data
 // parallelism calls (L, L/2) then (L/2, 0) and all-reduces the first part's gradients while the second runs.
 extern "C" int pevit_visual_backward_part(pevit_ctx* c, void* stream, const float* dfeat, int B, int l_hi, int l_lo) {
+    CHECK(refuse_text(c, "visual_backward"));
     CHECK(check_ready(c, B, "visual_backward"));
     CHECK(check_saved(c, Saved::visual, B, -1, "visual_backward"));
     if (l_lo < 0 || l_hi > c->L || l_lo >= l_hi) { pevit_set_error("visual_backward: bad layer range [%d, %d)", l_lo, l_hi); return -1; }
@@ -1553,6 +1695,7 @@ extern "C" int pevit_visual_backward(pevit_ctx* c, void* stream, const float* df
 // labels (B) int64 -> cross-entropy, targets (B x C) f32 -> BCE with logits, neither -> forward only; never both
 static int head_fb_impl(pevit_ctx* c, void* stream, const float* feat, const int64_t* labels, const float* targets,
                         float* running_mean, float* running_var, int bn_training, float* logits, float* loss, float* dfeat, int B) {
+    CHECK(refuse_text(c, "head_forward_backward"));
     if (!c || !c->ws || !c->params || !c->grads) { pevit_set_error("head: context not ready"); return -1; }
     if (B <= 0 || B > c->max_batch) { pevit_set_error("head: batch %d outside [1,%d]", B, c->max_batch); return -1; }
     if (!feat || !running_mean || !running_var || !logits) { pevit_set_error("head: null argument"); return -1; }
@@ -1585,6 +1728,7 @@ extern "C" int pevit_head_forward_backward(pevit_ctx* c, void* stream, const flo
 extern "C" int pevit_head_forward_backward_bce(pevit_ctx* c, void* stream, const float* feat, const float* targets,
                                                float* running_mean, float* running_var, int bn_training, float* logits,
                                                float* loss, float* dfeat, int B) {
+    CHECK(refuse_text(c, "head_forward_backward_bce"));
     if (!targets) { pevit_set_error("head_bce: targets is null (the forward alone is pevit_head_forward_backward with no labels)"); return -1; }
     return head_fb_impl(c, stream, feat, nullptr, targets, running_mean, running_var, bn_training, logits, loss, dfeat, B);
 }
@@ -1599,6 +1743,7 @@ extern "C" int pevit_train_forward_backward(pevit_ctx* c, void* stream, const fl
 extern "C" int pevit_train_forward_backward_u8(pevit_ctx* c, void* stream, const uint8_t* images, const int64_t* labels,
                                                float* running_mean, float* running_var, int bn_training, float* logits,
                                                float* loss, int B) {
+    CHECK(refuse_text(c, "train_forward_backward_u8"));
     if (c && !c->img_norm_set) { pevit_set_error("train_forward_backward_u8: call pevit_set_input_norm first"); return -1; }
     return train_fb_impl(c, stream, images, 1, labels, nullptr, running_mean, running_var, bn_training, logits, loss, B);
 }
@@ -1610,11 +1755,13 @@ extern "C" int pevit_train_forward_backward_bce(pevit_ctx* c, void* stream, cons
 extern "C" int pevit_train_forward_backward_bce_u8(pevit_ctx* c, void* stream, const uint8_t* images, const float* targets,
                                                    float* running_mean, float* running_var, int bn_training, float* logits,
                                                    float* loss, int B) {
+    CHECK(refuse_text(c, "train_forward_backward_bce_u8"));
     if (c && !c->img_norm_set) { pevit_set_error("train_forward_backward_bce_u8: call pevit_set_input_norm first"); return -1; }
     return train_fb_impl(c, stream, images, 1, nullptr, targets, running_mean, running_var, bn_training, logits, loss, B);
 }
 static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, const float* targets,
                          float* running_mean, float* running_var, int bn_training, float* logits, float* loss, int B) {
+    CHECK(refuse_text(c, "train_forward_backward"));
     CHECK(check_ready(c, B, "train_forward_backward"));
     if (!labels == !targets) { pevit_set_error("train_forward_backward: exactly one of labels and targets must be given"); return -1; }
     c->gate_now = c->step_gate != nullptr;              // with a gate the gradients are cleared behind it, inside the forward pass
@@ -1801,6 +1948,11 @@ extern "C" int pevit_op_attn_fwd(void* stream, const void* q, const void* k, con
     AttnArgs a;
     a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.ldo = ldo; a.lse = lse; a.B = B; a.H = H; a.N = N;
     return pevit_launch_attn_fwd(a, (hipStream_t)stream);
+}
+extern "C" int pevit_op_attn_fwd_causal(void* stream, const void* q, const void* k, const void* v, void* out, int ldo, int B, int H, int N) {
+    AttnArgs a;
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.ldo = ldo; a.B = B; a.H = H; a.N = N;
+    return pevit_launch_attn_fwd_causal(a, (hipStream_t)stream);
 }
 extern "C" int pevit_op_attn_bwd(void* stream, const void* q, const void* k, const void* v, const void* out, int ldo,
                                  const void* dout, int lddo, const float* lse, void* dqkv, int ld, int B, int H, int N) {

@@ -130,6 +130,8 @@ struct AttnArgs {
     float* probs = nullptr; int average = 0;
 };
 int pevit_launch_attn_fwd(const AttnArgs& a, hipStream_t s);
+// attn_causal.hip: the text tower's attention (query x sees keys y <= x), 1 <= N <= 128, forward only: reads q, k, v, writes out
+int pevit_launch_attn_fwd_causal(const AttnArgs& a, hipStream_t s);
 int pevit_launch_attn_bwd(const AttnArgs& a, hipStream_t s);
 int pevit_launch_attn_probs(const AttnArgs& a, hipStream_t s);
 
@@ -355,12 +357,23 @@ int pevit_launch_chain_compacter(const ChainCompacterArgs& a, hipStream_t s);
 // Each twin takes its production sibling's struct; the members declared bf16 (and lowrank_grad's xn) hold f32 there.
 int pevit_launch_gemm_f32(int epi, const GemmParams& p, hipStream_t s);      // A, B and the bf16-declared buffers hold f32
 int pevit_launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s);             // (out_fp8 is not written)
+int pevit_launch_attn_fwd_causal_f32(const AttnArgs& a, hipStream_t s);      // (no lse)
 int pevit_launch_attn_bwd_f32(const AttnArgs& a, hipStream_t s);             // (every row of dout is read: dout_cls_only has no effect)
 int pevit_launch_attn_probs_f32(const AttnArgs& a, hipStream_t s);
 int pevit_launch_lowrank_u_f32(const LowrankArgs& a, hipStream_t s);         // reads the f32 panel q32, not qT
 // G[e][j] = sum_r X[r][e] Y[r][j], partial / column-sum layout of tn_gemm64 (adapter.hip)
 int pevit_launch_tn_gemm64_f32(const TnGemm64Args& a, hipStream_t s);
 int pevit_launch_lowrank_grad_f32(const LowrankArgs& a, hipStream_t s);      // (no workgroup-order knob)
+
+// ---- text.hip (CLIP text tower: token-embedding stem and the end-of-text gather) ---------------------------------
+// x[s*N + n][:] = table[clamp(tokens[s][n], 0, V - 1)][:] + pos[n][:]   (f32; model.py:1154)
+struct TextEmbedArgs {
+    const int64_t* tokens = nullptr; const float* table = nullptr; const float* pos = nullptr; float* x = nullptr;
+    int S = 0, N = 0, E = 0, V = 0;
+};
+int pevit_launch_text_embed(const TextEmbedArgs& a, hipStream_t s);
+// rows_out[s][:] = x[s*N + argmax_n tokens[s][n]][:], the first maximum (model.py:1166); ln_final runs on the compact rows
+int pevit_launch_text_eot_gather(const int64_t* tokens, const float* x, float* rows_out, int S, int N, int E, hipStream_t s);
 
 // ---- stem_head.hip -----------------------------------------------------------------
 int pevit_launch_im2col(const float* img, bf16* out, int B, int R, int P, int Kp, hipStream_t s, int f32 = 0);

@@ -318,6 +318,52 @@ int pevit_launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s) {
     return 0;
 }
 
+namespace {
+// causal attention of the text tower (attn_causal.hip) in f32: attn_fwd_f32_kernel with query i bounded to the keys j <= i, no lse
+__global__ __launch_bounds__(128) void attn_fwd_causal_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                  const float* __restrict__ v, float* __restrict__ out, int ldo,
+                                                                  int H, int N) {
+    const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+    const float* kh = k + (size_t)bh * N * 64;
+    const float* vh = v + (size_t)bh * N * 64;
+    for (int i = threadIdx.x; i < N; i += 128) {
+        float qi[64];
+#pragma unroll
+        for (int d = 0; d < 64; ++d) qi[d] = q[((size_t)bh * N + i) * 64 + d];
+        float m = -3.0e38f;
+        for (int j = 0; j <= i; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) s = fmaf(qi[d], kh[(size_t)j * 64 + d], s);
+            m = fmaxf(m, s);
+        }
+        float l = 0.f, o[64];
+#pragma unroll
+        for (int d = 0; d < 64; ++d) o[d] = 0.f;
+        for (int j = 0; j <= i; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) s = fmaf(qi[d], kh[(size_t)j * 64 + d], s);
+            const float pj = expf(s - m);
+            l += pj;
+#pragma unroll
+            for (int d = 0; d < 64; ++d) o[d] = fmaf(pj, vh[(size_t)j * 64 + d], o[d]);
+        }
+        const float inv = 1.0f / l;
+        float* dst = out + ((size_t)b * N + i) * ldo + h * 64;
+#pragma unroll
+        for (int d = 0; d < 64; ++d) dst[d] = o[d] * inv;
+    }
+}
+}  // namespace
+
+int pevit_launch_attn_fwd_causal_f32(const AttnArgs& a, hipStream_t s) {
+    if (a.N < 1 || a.N > 128) { pevit_set_error("attn_fwd_causal (f32 verification): N=%d outside [1,128]", a.N); return -1; }
+    hipLaunchKernelGGL(attn_fwd_causal_f32_kernel, dim3(a.B * a.H), dim3(128), 0, s, f32p(a.q), f32p(a.k), f32p(a.v), f32p(a.out), a.ldo, a.H, a.N);
+    LAUNCH_OK("attn_fwd_causal_f32_kernel");
+    return 0;
+}
+
 int pevit_launch_attn_bwd_f32(const AttnArgs& a, hipStream_t s) {
     if (a.N < 1 || a.N > 320) { pevit_set_error("attn_bwd (f32 verification): N=%d outside [1,320]", a.N); return -1; }
     hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(a.B * a.H), dim3(256), 0, s, f32p(a.q), f32p(a.k), f32p(a.v), f32p(a.out), a.ldo, f32p(a.dout), a.lddo,

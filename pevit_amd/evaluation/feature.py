@@ -1,7 +1,8 @@
 """Zero-shot head initialisation and loader helpers (reference: evaluation/feature.py:405-531,585-608).
 
 Only what ``Classifier(INIT_HEAD_WITH_TEXT_ENCODER=True)`` needs is here: prompts per class -> text tower
-(host PyTorch, run once) -> normalise / mean over templates / normalise -> (D, C) weight matrix.  The
+(host PyTorch, one call per class; with ``TRAIN.TEXT_TOWER_ENGINE`` the HIP engine's text tower, all prompts
+in chunks) -> normalise / mean over templates / normalise -> (D, C) weight matrix.  The
 reference's class-name tables, prompt templates, tokenizer vocabulary and knowledge sources are data of
 its dataset layer and are not shipped: the caller supplies them through ``config.DATASET.CLASS_NAMES`` /
 ``config.DATASET.TEMPLATES`` (or the keyword arguments) and a ``tokenizer(texts, context_length=...)``.
@@ -12,6 +13,33 @@ import logging
 import time
 
 import torch
+
+
+def reduce_class_features(features, class_index, num_classes):
+    """The reference's per-class reduction (feature.py:513-520) over a stacked tensor: features (S, D), class_index (S,) int64
+    with the class of every row -> (D, C): normalise every row, mean over the rows of a class, normalise."""
+    e = features / features.norm(dim=-1, keepdim=True)
+    idx = class_index.to(device=e.device, dtype=torch.int64)
+    sums = torch.zeros((num_classes, e.shape[1]), dtype=e.dtype, device=e.device).index_add_(0, idx, e)
+    counts = torch.bincount(idx, minlength=num_classes).to(e.dtype)
+    if bool((counts == 0).any()):
+        raise RuntimeError("reduce_class_features: a class without prompts")
+    m = sums / counts[:, None]
+    return (m / m.norm(dim=-1, keepdim=True)).t().contiguous()
+
+
+def _class_tokens(config, tokenizer, classname, templates, device):
+    """token ids (T, context) of one class's prompts, or the formatted prompts themselves with MODEL.SPEC.TEXT.SKIP_TOKENIZE"""
+    if type(classname) == list:
+        classname = classname[0]
+    if torch.is_tensor(classname):                    # already tokenised prompts of this class: (T, context)
+        return classname.to(device)
+    texts = [t.format(classname) for t in templates]
+    if not config.MODEL.SPEC.TEXT.get("SKIP_TOKENIZE", False):
+        if tokenizer is None:
+            raise RuntimeError("a tokenizer callable is required to turn prompts into token ids")
+        texts = tokenizer(texts, context_length=config.MODEL.SPEC.TEXT.CONTEXT_LENGTH).to(device)
+    return texts
 
 
 @torch.no_grad()
@@ -30,25 +58,33 @@ def extract_text_features(config, tokenizer, args=None, model=None, return_numpy
     device = next(model.parameters()).device
     start = time.time()
     model.eval()
-    cols = []
-    ctx_len = config.MODEL.SPEC.TEXT.CONTEXT_LENGTH
-    for classname in class_names:
-        if type(classname) == list:
-            classname = classname[0]
-        if torch.is_tensor(classname):                    # already tokenised prompts of this class: (T, context)
-            texts = classname.to(device)
-        else:
-            texts = [t.format(classname) for t in templates]
-            if not config.MODEL.SPEC.TEXT.get("SKIP_TOKENIZE", False):
-                if tokenizer is None:
-                    raise RuntimeError("a tokenizer callable is required to turn prompts into token ids")
-                texts = tokenizer(texts, context_length=ctx_len).to(device)
-        emb = model.encode_text(texts)
-        emb = emb / emb.norm(dim=-1, keepdim=True)
-        emb = emb.mean(dim=0)
-        cols.append(emb / emb.norm())
-    zeroshot_weights = torch.stack(cols, dim=1).to(device)
-    logging.info(f"=> Feature extraction duration time: {time.time() - start:.2f}s")
+    from ..text_engine import text_engine_ok
+    train_cfg = config.get("TRAIN", None) if hasattr(config, "get") else getattr(config, "TRAIN", None)
+    engine = bool(train_cfg is not None and train_cfg.get("TEXT_TOWER_ENGINE", False)) and hasattr(model, "encode_text_engine") \
+        and text_engine_ok(model)
+    if engine:
+        # every class tokenised, the prompts stacked into one (S, context) tensor with the class of every row, encoded in chunks
+        per_class = [_class_tokens(config, tokenizer, c, templates, device) for c in class_names]
+        engine = all(torch.is_tensor(t) for t in per_class)           # (SKIP_TOKENIZE hands strings to encode_text: torch route)
+    if engine:
+        tokens = torch.cat(per_class, dim=0)
+        index = torch.cat([torch.full((t.shape[0],), i, dtype=torch.int64) for i, t in enumerate(per_class)]).to(device)
+        try:
+            feats = model.encode_text_engine(tokens).to(model.text_projection.dtype)
+            zeroshot_weights = reduce_class_features(feats, index, len(per_class)).to(device)
+        finally:
+            model.release_text_engine()       # its arena must not stay allocated next to the training contexts
+    else:
+        cols = []
+        for classname in class_names:
+            texts = _class_tokens(config, tokenizer, classname, templates, device)
+            emb = model.encode_text(texts)
+            emb = emb / emb.norm(dim=-1, keepdim=True)
+            emb = emb.mean(dim=0)
+            cols.append(emb / emb.norm())
+        zeroshot_weights = torch.stack(cols, dim=1).to(device)
+    logging.info(f"=> Feature extraction duration time: {time.time() - start:.2f}s "
+                 f"(text tower: {'HIP engine, %d prompts in chunks' % tokens.shape[0] if engine else 'torch, one call per class'})")
     return zeroshot_weights.cpu().detach().numpy() if return_numpy else zeroshot_weights
 
 

@@ -11,7 +11,9 @@ these names in the harness) -- while the vision tower itself executes in
 HIP library / a GPU, ``encode_image`` raises.
 
 The text tower (``encode_text``, used once to initialise the zero-shot head) is plain host
-PyTorch, as SURVEY 8f-4 prescribes; it is not on the accelerated path.
+PyTorch, as SURVEY 8f-4 prescribes.  ``encode_text_engine`` runs the same tower on the engine
+(``pevit_amd/text_engine.py``: causal attention, one call per chunk of prompts) where
+``text_engine_ok`` allows it; ``encode_text`` itself is unchanged.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ from torch import nn
 from .. import _lib
 from ..engine import HipEngine, adapter_param_spec
 from ..synth import VitArch
+from ..text_engine import TextEngine, text_engine_ok, text_engine_refusal
 
 
 # --------------------------------------------------------------------------- host-side pieces
@@ -514,6 +517,8 @@ class CLIP(nn.Module):
         self.vocab_size = vocab_size
         self.token_embedding = nn.Embedding(vocab_size, transformer_width)
         self.ln_final = LayerNorm(transformer_width)
+        self._text_arch = arch
+        self._text_engine: TextEngine | None = None
 
     def build_attention_mask(self):
         mask = torch.empty(self.context_length, self.context_length)
@@ -536,6 +541,28 @@ class CLIP(nn.Module):
         x = self.transformer(x.permute(1, 0, 2)).permute(1, 0, 2)
         x = self.ln_final(x).type(self.dtype)
         return x[torch.arange(x.shape[0]), text.argmax(dim=-1)] @ self.text_projection
+
+    def encode_text_engine(self, text, max_prompts: int = 256):
+        """``encode_text`` on the HIP engine: (S, context_length) token ids -> (S, embed_dim) f32 on the device, no autograd.
+        Builds a ``TextEngine`` from this model's text weights on first use and keeps it (``release_text_engine`` drops it, and
+        must be called after the text weights change); raises where ``text_engine_ok(self)`` is false."""
+        why = text_engine_refusal(self)
+        if why is not None:
+            raise _lib.PevitError(f"encode_text_engine: {why}; use encode_text")
+        dev = self.token_embedding.weight.device
+        wf = getattr(self.visual, "weight_format", "bf16")
+        wf = wf if wf == "f32-verify" else "bf16"           # the fp8 formats belong to the image tower
+        eng = self._text_engine
+        if eng is None or eng.device != dev or eng.weight_format != wf or eng.max_prompts != int(max_prompts):
+            self._text_engine = eng = None                   # (the old arena goes before the new one is allocated)
+            eng = TextEngine(self._text_arch, max_prompts=max_prompts, device=dev, weight_format=wf)
+            eng.load_state_dict({k: p for k, p in self.state_dict().items() if not k.startswith("visual.")})
+            self._text_engine = eng
+        return eng.encode(text)
+
+    def release_text_engine(self):
+        """Drop the cached text engine (its weight arena and workspace go back to the allocator)."""
+        self._text_engine = None
 
     def forward(self, image, text):
         img, txt = self.encode_image(image), self.encode_text(text)
