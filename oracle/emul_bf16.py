@@ -4,7 +4,7 @@
 operands rounded to bf16").  Two different bf16 roundings of the same randomly initialised tower
 differ from each other about as much as each differs from fp32, so that mode can only calibrate a
 wide gate.  This module rounds at EXACTLY the points where the engine stores a bf16 value
-(``pevit_amd/csrc/capi.hip`` blocks_forward / blocks_backward) and nowhere
+(``pevit_amd/csrc/walk.hip`` blocks_forward / blocks_backward) and nowhere
 else, forward AND backward, so that the HIP path and this emulation differ only by the f32
 summation order inside the contractions.  ``tests/test_gpu_emulation.py`` holds the production
 kernels to it at logits <= 5e-3, gradients <= 2e-2 relative L2.
@@ -22,7 +22,7 @@ Storage points reproduced (engine buffer -> here):
             class-token LayerNorm bf16 -> proj bf16      RoundSTE, LinearE
   backward  bf16 copy of the gradient stream (dyb)       every LinearE rounds its upstream gradient
             the residual gradient stream ITSELF bf16     RoundGrad at x_mid and at the block output (round 5; attention-site
-            (LayerNorm backward read-modify-writes dyb)  and fused post-MLP adapters: capi.hip gstream16_on; the dx of the lowest
+            (LayerNorm backward read-modify-writes dyb)  and fused post-MLP adapters: ctx.hip plan_step, StepPlan::gstream16; the dx of the lowest
                                                          block walked leaves in f32)
             dh = bf16(acc * gelu'(h))                    QuickGeluE.backward
             dxn2, dO, dxn1 bf16 (dX GEMM outputs)        LinearE(round_dx) / QKVAug.backward

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (capi.hip) and the kernel files.
+// Internal launcher interface between the C-ABI layer (ctx.hip, profile.hip, walk.hip, step.hip, ops.hip) and the kernel files.
 // Convention: a launcher with many operands takes ONE parameter struct (GemmParams, XxxArgs) plus the stream, filled by name at the
 // call site.  Every XxxArgs member is default-initialised and an unset member means "absent / off".  The f32 verification twins
 // (verify.hip, *_f32) take the SAME struct as their production sibling and reinterpret its bf16-declared members as f32 inside.

@@ -760,7 +760,7 @@ int pevit_launch_lowrank_grad(const LowrankArgs& a, hipStream_t s) {
     return 0;
 }
 
-// partial: [layers][chunks+? ...] see capi.hip; G: [layers][4][E][32]; rule_scratch: [layers][4096]
+// partial: [layers][chunks+? ...] see ctx.hip layout_workspace; G: [layers][4][E][32]; rule_scratch: [layers][4096]
 int pevit_launch_chain_kadapt(const ChainKadaptArgs& a, hipStream_t s) {
     const int E = a.E;
     if (64 + 2 * (E / 32) > 256) { pevit_set_error("chain_kadapt: width %d too large", E); return -1; }

@@ -10,7 +10,7 @@ taken with a synchronise on both sides; next to it the median over the batches o
 of the two routes are compared once per configuration (the tower bits are the same; the f32 head is computed by different code).
 
 --profile: additionally one batch per route under the engine's own per-launch events (HipEngine.profile_gemms(all_kernels=True)):
-per kernel kind / GEMM shape the launches, milliseconds and ALGORITHMIC bytes (capi.hip prof_close) of a whole forward.
+per kernel kind / GEMM shape the launches, milliseconds and ALGORITHMIC bytes (profile.hip prof_close) of a whole forward.
 --one-pass ROUTE: nothing but a warm-up and one pass of ROUTE at batch 128 (the process to put under rocprofv3 --kernel-trace --stats).
 Prints one JSON object.  usage: python scripts/predict_rate.py [--steps 20] [--reps 3] [--profile] [--out FILE]"""
 import argparse

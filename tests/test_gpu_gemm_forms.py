@@ -59,7 +59,7 @@ def lib():
 
 @pytest.fixture(scope="module")
 def ws(lib):
-    """the stream-K workspace, sized as op_sk_workspace (capi.hip) sizes it: one flag word per slot + the error word, one 128x128 f32
+    """the stream-K workspace, sized as op_sk_workspace (ops.hip) sizes it: one flag word per slot + the error word, one 128x128 f32
     slab per slot.  The slabs start as NaN: a partial tile read before it was written shows."""
     slots = lib.pevit_op_gemm_sk_slots()
     assert 8 <= slots <= 1024 and slots % 8 == 0

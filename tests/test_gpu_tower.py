@@ -753,7 +753,7 @@ def test_combined_lowrank_backward_equals_the_two_launches(method, arch_name, B)
 @pytest.mark.parametrize("method,knob", [("adapter", "adapter_fused"), ("compacter", "adapter_fused"), ("kadaptation", "lowrank_combo"),
                                          ("kadaptation", "gstream_bf16")])
 def test_a_knob_changed_between_forward_and_backward_takes_effect_at_the_next_forward(method, knob):
-    """The launch paths of a step are planned once per forward (capi.hip plan_step) and the backward runs on its forward's plan:
+    """The launch paths of a step are planned once per forward (ctx.hip plan_step) and the backward runs on its forward's plan:
     a `tune` between visual_forward and visual_backward leaves that backward's gradients bit-identical to the unchanged pair
     (the fused adapter forward leaves hf32 without its bias, which the separate launches' backward would read as LayerNorm
     input), and the next forward takes the new path -- bit-identical to an engine tuned before its first forward."""
