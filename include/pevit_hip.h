@@ -218,6 +218,31 @@ int pevit_predict(pevit_ctx* ctx, void* stream, const float* images, const float
                   float* logits, float* feat_or_null, int batch);
 int pevit_predict_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const float* running_mean, const float* running_var,
                      float* logits, float* feat_or_null, int batch);   /* needs pevit_set_input_norm */
+/* ---- zero-shot classification (commands/zeroshot.py, clip_zeroshot_evaluator.py:16-20 of the reference): images -> features, and
+ * images -> class probabilities softmax(scale * normalize(features) @ text) in one call.
+ * pevit_encode_image: the tower in the inference forms of pevit_predict, without a head -- CLIP.encode_image for evaluation; the
+ * features are the bits pevit_predict returns in feat_or_null.
+ * pevit_zeroshot: the same walk, then ONE launch of the zero-shot head on the features: s_b = scale / max(||feat_b||_2, 1e-12) (the
+ * eps clamp of F.normalize), logits[b][c] = s_b * <feat_b, text_c>, probs[b][:] = softmax(logits[b][:]) with the row maximum
+ * subtracted -- all f32 on the f32 matrix instruction, no bf16 rounding.  text_cd: device f32 (num_classes x D), CLASS-major, one
+ * unit vector per row (the transpose of the reference's (D, C) text_features, made once per evaluation); num_classes is
+ * independent of pevit_dims.num_classes.  probs_or_null / logits_or_null: (batch x num_classes) f32, either may be null, not both;
+ * feat_or_null: (batch x D), or null to keep the features in workspace scratch.  Every reduction of the head runs in a fixed order
+ * that depends on D and num_classes only, so a row's outputs are bit-identical alone and inside any batch; a zero feature row gives
+ * uniform probabilities.  Limits: 1 <= num_classes <= 1024, D a multiple of 8 up to 1024, text_cd (and feat) 16-byte aligned;
+ * anything else is refused before any launch.  All four read the parameters and write their outputs and workspace scratch only;
+ * they leave no saved forward behind (a backward issued afterwards is refused), work with every method (PEVIT_NONE is the plain
+ * CLIP the reference scores) and every weight format, refuse a text context and an unbound one, and take batch in
+ * [1, max_batch] of the bound workspace.  The _u8 forms need pevit_set_input_norm. */
+int pevit_encode_image(pevit_ctx* ctx, void* stream, const float* images, float* feat, int batch);
+int pevit_encode_image_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, float* feat, int batch);
+int pevit_zeroshot(pevit_ctx* ctx, void* stream, const float* images, const float* text_cd, int num_classes, float scale,
+                   float* probs_or_null, float* logits_or_null, float* feat_or_null, int batch);
+int pevit_zeroshot_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const float* text_cd, int num_classes, float scale,
+                      float* probs_or_null, float* logits_or_null, float* feat_or_null, int batch);
+/* the zero-shot head alone, context-free (parity tests): feat (B x D), text_cd (C x D), outputs (B x C) */
+int pevit_op_zeroshot_head(void* stream, const float* feat, const float* text_cd, float scale, float* probs_or_null,
+                           float* logits_or_null, int B, int D, int C);
 /* ---- the CLIP text tower (CLIP.encode_text, model.py:1153-1168): token ids (S x N) int64 -> text features (S x D) f32 in one call.
  * A text context is a pevit_ctx like any other -- method PEVIT_NONE, H = width / 64 heads, N = context_length tokens per prompt,
  * causal attention -- so pevit_arena_bytes, pevit_bind, pevit_load_block (q rows pre-scaled by 1/8 as for the image tower) and

@@ -105,6 +105,11 @@ SIGNATURES = {
     "pevit_head_forward_backward": (c_int, [P, P, P, P, P, P, c_int, P, P, P, c_int]),
     "pevit_predict": (c_int, [P, P, P, P, P, P, P, c_int]),
     "pevit_predict_u8": (c_int, [P, P, P, P, P, P, P, c_int]),
+    "pevit_encode_image": (c_int, [P, P, P, P, c_int]),
+    "pevit_encode_image_u8": (c_int, [P, P, P, P, c_int]),
+    "pevit_zeroshot": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int]),
+    "pevit_zeroshot_u8": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int]),
+    "pevit_op_zeroshot_head": (c_int, [P, P, P, c_float, P, P, c_int, c_int, c_int]),
     "pevit_text_create": (c_int, [C.POINTER(PevitTextDims), C.POINTER(c_void_p)]),
     "pevit_load_text_stem": (c_int, [P, P] + [P] * 5),
     "pevit_encode_text": (c_int, [P, P, P, P, c_int]),

@@ -99,7 +99,8 @@ def default_config() -> CfgNode:
         DATASET=dict(DATASET="cifar100", ROOT="", NUM_CLASSES=100, NUM_SAMPLES_PER_CLASS=-1, RANDOM_SEED_SAMPLING=0,
                      MERGE_TRAIN_VAL_FINAL_RUN=True, CENTER_CROP=True, IMAGE_SIZE=(224,)),
         KNOWLEDGE=dict(WORDNET=dict(USE_HIERARCHY=False, USE_DEFINITION=False), WIKITIONARY=dict(USE_DEFINITION=False),
-                       GPT3=dict(USE_GPT3=False)),
+                       GPT3=dict(USE_GPT3=False),
+                       AGGREGATION=dict(MEHTOD="WIKI_AND_GPT3", NUM_GPT3_ITEMS=1)),     # (the reference's spelling: zeroshot.py:90)
         INPUT=dict(MEAN=[0.48145466, 0.4578275, 0.40821073], STD=[0.26862954, 0.26130258, 0.27577711]),
         TRAIN=dict(LR=0.001, SCHEDULE=[], SEARCH_WD_LOG_LOWER=-6, SEARCH_WD_LOG_UPPER=6, FREEZE_IMAGE_BACKBONE=False,
                    TWO_LR=False, USE_CHANNEL_BN=True, INIT_HEAD_WITH_TEXT_ENCODER=False, LOGIT_SCALE_INIT="none",

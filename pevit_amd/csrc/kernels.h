@@ -395,3 +395,15 @@ struct HeadArgs {
     bf16* dfeat_bf16 = nullptr;     // bf16 copy of dfeat written by the BatchNorm backward (no cast launch)
 };
 int pevit_launch_head(const HeadArgs& a, hipStream_t s);
+
+// ---- zeroshot.hip (the CLIP zero-shot head: cosine logits and their softmax in one launch, exact f32) ------------
+// logits[b][c] = scale / max(||feat_b||, 1e-12) * <feat_b, text_c> ; probs[b][:] = softmax(logits[b][:])
+// feat [B][D], text [C][D] (class-major unit rows), outputs [B][C], all f32; either output may be null, not both.
+// 1 <= C <= 1024, D a multiple of 8 up to 1024, B >= 1, feat and text 16-byte aligned: pevit_zeroshot_check refuses the rest.
+struct ZeroshotArgs {
+    const float* feat = nullptr; const float* text = nullptr; float* probs = nullptr; float* logits = nullptr;
+    float scale = 100.f;
+    int B = 0, D = 0, C = 0;
+};
+int pevit_zeroshot_check(const ZeroshotArgs& a);      // 0, or -1 with the error text set; launches nothing
+int pevit_launch_zeroshot_head(const ZeroshotArgs& a, hipStream_t s);

@@ -222,5 +222,12 @@ extern "C" int pevit_op_im2col_u8(void* stream, const uint8_t* images, const flo
 extern "C" int pevit_op_im2col(void* stream, const float* images, void* patches_bf16, int B, int R, int P, int Kpad) {
     return pevit_launch_im2col(images, (bf16*)patches_bf16, B, R, P, Kpad, (hipStream_t)stream);
 }
+// the zero-shot head alone (zeroshot.hip): the seam its parity tests use
+extern "C" int pevit_op_zeroshot_head(void* stream, const float* feat, const float* text_cd, float scale, float* probs_or_null,
+                                      float* logits_or_null, int B, int D, int C) {
+    ZeroshotArgs a;
+    a.feat = feat; a.text = text_cd; a.scale = scale; a.probs = probs_or_null; a.logits = logits_or_null; a.B = B; a.D = D; a.C = C;
+    return pevit_launch_zeroshot_head(a, (hipStream_t)stream);
+}
 
 extern "C" int pevit_debug_last_gemm_path(void) { return pevit_gemm_last_path(); }

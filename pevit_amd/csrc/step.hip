@@ -300,6 +300,47 @@ extern "C" int pevit_predict_u8(pevit_ctx* c, void* stream, const uint8_t* image
     return predict_impl(c, stream, images, 1, running_mean, running_var, logits, feat_or_null, B);
 }
 
+// images (B,3,R,R) -> features (B,D) through the inference forms, without a head (CLIP.encode_image for evaluation).  Like
+// pevit_predict it leaves no saved forward behind.
+static int encode_image_impl(pevit_ctx* c, void* stream, const void* images, int u8, float* feat, int B) {
+    CHECK(refuse_text(c, "encode_image"));
+    CHECK(check_ready(c, B, "encode_image"));
+    if (!images || !feat) { pevit_set_error("encode_image: null argument"); return -1; }
+    return visual_forward_impl(c, stream, images, u8, feat, B, 0, true, false);
+}
+extern "C" int pevit_encode_image(pevit_ctx* c, void* stream, const float* images, float* feat, int B) {
+    return encode_image_impl(c, stream, images, 0, feat, B);
+}
+extern "C" int pevit_encode_image_u8(pevit_ctx* c, void* stream, const uint8_t* images, float* feat, int B) {
+    CHECK(check_u8_input(c, "encode_image_u8"));
+    return encode_image_impl(c, stream, images, 1, feat, B);
+}
+
+// images (B,3,R,R) -> zero-shot class probabilities (B x num_classes) in one call: the same walk, then the cosine head and its
+// softmax in one launch (zeroshot.hip) on the features.  text_cd: (num_classes x D) f32, one unit vector per class; num_classes is
+// independent of pevit_dims.num_classes.  The head's limits are checked before the tower runs.
+static int zeroshot_impl(pevit_ctx* c, void* stream, const void* images, int u8, const float* text_cd, int num_classes, float scale,
+                         float* probs, float* logits, float* feat_or_null, int B) {
+    CHECK(refuse_text(c, "zeroshot"));
+    CHECK(check_ready(c, B, "zeroshot"));
+    if (!images) { pevit_set_error("zeroshot: null argument"); return -1; }
+    ZeroshotArgs a;
+    a.feat = feat_or_null ? feat_or_null : at<float>(c->ws, 0);     // (for the check: the w_feat slot is known after the walk)
+    a.text = text_cd; a.scale = scale; a.probs = probs; a.logits = logits; a.B = B; a.D = c->D; a.C = num_classes;
+    CHECK(pevit_zeroshot_check(a));
+    CHECK(visual_forward_impl(c, stream, images, u8, feat_or_null, B, 0, true, false));
+    a.feat = feat_or_null ? feat_or_null : at<float>(c->ws, c->lay.w_feat);
+    return pevit_launch_zeroshot_head(a, (hipStream_t)stream);
+}
+extern "C" int pevit_zeroshot(pevit_ctx* c, void* stream, const float* images, const float* text_cd, int num_classes, float scale,
+                              float* probs_or_null, float* logits_or_null, float* feat_or_null, int B) {
+    return zeroshot_impl(c, stream, images, 0, text_cd, num_classes, scale, probs_or_null, logits_or_null, feat_or_null, B);
+}
+extern "C" int pevit_zeroshot_u8(pevit_ctx* c, void* stream, const uint8_t* images, const float* text_cd, int num_classes, float scale,
+                                 float* probs_or_null, float* logits_or_null, float* feat_or_null, int B) {
+    CHECK(check_u8_input(c, "zeroshot_u8"));
+    return zeroshot_impl(c, stream, images, 1, text_cd, num_classes, scale, probs_or_null, logits_or_null, feat_or_null, B);
+}
 
 // tokens (S,N) int64 -> features (S,D) f32                              model.py:1153-1168
 extern "C" int pevit_encode_text(pevit_ctx* c, void* stream, const int64_t* tokens, float* features, int S) {

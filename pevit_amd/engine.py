@@ -412,6 +412,55 @@ class HipEngine:
                       _lib.ptr(logits), _lib.ptr(feat), B), "pevit_predict")
         return (logits, feat) if return_features else logits
 
+    def _inference_walk(self, images):
+        """What ``predict`` does before its engine call: flush a pipelined DP step, check the batch, bump the generations (the
+        walk overwrites the activations a pending backward would read)."""
+        self.dp_flush()
+        img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
+        self._check_batch(img)
+        self.forward_generation += 1
+        for l in range(self.arch.layers):
+            self.block_generation[l] = self.block_generation.get(l, 0) + 1
+        return img
+
+    def encode_image(self, images: torch.Tensor) -> torch.Tensor:
+        """images -> features (B, D) through the inference forms of the tower, without a head (``pevit_encode_image``;
+        CLIP.encode_image for evaluation).  The bits ``predict(..., return_features=True)`` returns; nothing is stored for a
+        backward pass; no synchronise."""
+        img = self._inference_walk(images)
+        B = img.shape[0]
+        feat = torch.empty((B, self.arch.embed_dim), dtype=torch.float32, device=self.device)
+        fn = self.lib.pevit_encode_image_u8 if img.dtype == torch.uint8 else self.lib.pevit_encode_image
+        _lib.check(fn(self._ctx, _lib.stream_ptr(), _lib.ptr(img), _lib.ptr(feat), B), "pevit_encode_image")
+        return feat
+
+    def zeroshot(self, images: torch.Tensor, text_cd: torch.Tensor, scale: float = 100.0, probs_out=None,
+                 return_logits: bool = False, return_features: bool = False):
+        """images -> zero-shot class probabilities ``softmax(scale * normalize(features) @ text_cd.T)`` in ONE engine call
+        (``pevit_zeroshot``): the inference walk, then the cosine head and its softmax in one exact-f32 launch.  ``text_cd``:
+        contiguous f32 (C, D) on this device, CLASS-major, one unit vector per row -- the transpose of the reference's (D, C)
+        text features; C is independent of ``num_classes``, 1 <= C <= 1024.  Returns the probabilities (B, C) as a device tensor
+        without synchronising (``probs_out``: a caller-owned f32 destination), followed by the logits with ``return_logits``
+        and the features (B, D) with ``return_features``.  Parameters, gradients and running statistics are only read."""
+        D = self.arch.embed_dim
+        if text_cd.device != self.device or text_cd.dtype != torch.float32 or not text_cd.is_contiguous() or text_cd.dim() != 2 \
+                or text_cd.shape[1] != D:
+            raise _lib.PevitError(f"text_cd must be a contiguous float32 tensor (C, {D}) on {self.device}; got "
+                                  f"{tuple(text_cd.shape)} {text_cd.dtype} on {text_cd.device}")
+        img = self._inference_walk(images)
+        B, Cc = img.shape[0], text_cd.shape[0]
+        if probs_out is None:
+            probs = torch.empty((B, Cc), dtype=torch.float32, device=self.device)
+        else:
+            probs = self._out_buf(probs_out, (B, Cc))
+        logits = torch.empty((B, Cc), dtype=torch.float32, device=self.device) if return_logits else None
+        feat = torch.empty((B, D), dtype=torch.float32, device=self.device) if return_features else None
+        fn = self.lib.pevit_zeroshot_u8 if img.dtype == torch.uint8 else self.lib.pevit_zeroshot
+        _lib.check(fn(self._ctx, _lib.stream_ptr(), _lib.ptr(img), _lib.ptr(text_cd), Cc, float(scale), _lib.ptr(probs),
+                      _lib.ptr(logits), _lib.ptr(feat), B), "pevit_zeroshot")
+        out = (probs,) + ((logits,) if return_logits else ()) + ((feat,) if return_features else ())
+        return out if len(out) > 1 else probs
+
     def visual_backward(self, dfeat: torch.Tensor):
         self.dp_flush()
         B = dfeat.shape[0]

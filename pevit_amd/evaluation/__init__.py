@@ -5,4 +5,5 @@ head, loss and optimiser execute in ``libpevit_hip.so``.  Dataset download/manif
 vocabulary and the knowledge-augmented prompt sources of the reference are not part of this path.
 """
 from .dataloader import construct_dataloader  # noqa: E402,F401
-from .feature import extract_text_features  # noqa: E402,F401
+from .feature import extract_features, extract_text_features, zeroshot_scores  # noqa: E402,F401
+from .clip_zeroshot_evaluator import clip_zeroshot_evaluator  # noqa: E402,F401

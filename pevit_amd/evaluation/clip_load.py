@@ -143,3 +143,9 @@ def lora_load(name: str, device: Union[str, torch.device] = _DEFAULT_DEVICE, jit
 
 def compacter_load(name: str, device: Union[str, torch.device] = _DEFAULT_DEVICE, jit: bool = False, download_root: str = None):
     return _load(build_compacter_model, name, device, jit, download_root)
+
+
+def plain_load(name: str, device: Union[str, torch.device] = _DEFAULT_DEVICE, jit: bool = False, download_root: str = None):
+    """CLIP without any adapter (engine method ``none``): the model the reference's zero-shot command scores."""
+    from .model import build_peft_model
+    return _load(lambda sd: build_peft_model(sd, "none"), name, device, jit, download_root)

@@ -88,6 +88,55 @@ def extract_text_features(config, tokenizer, args=None, model=None, return_numpy
     return zeroshot_weights.cpu().detach().numpy() if return_numpy else zeroshot_weights
 
 
+def _image_engine(config, model, loader):
+    """The HIP context of ``model.visual``, sized for the loader's batches and told the preprocessing constants of uint8 sets."""
+    visual = model.visual
+    if getattr(visual, "_input_norm", None) is None and hasattr(config, "INPUT") and getattr(config.INPUT, "MEAN", None) is not None:
+        visual.set_input_normalization(config.INPUT.MEAN, config.INPUT.STD)
+    eng = visual.engine()
+    eng.ensure_batch(int(loader.batch_size))
+    return eng
+
+
+def _engine_features(eng, loader):
+    feats, labels = [], []
+    for x, y in loader:
+        feats.append(eng.encode_image(x.to(eng.device, non_blocking=True)))
+        labels.append(y)
+    return torch.cat(feats).cpu().numpy(), torch.cat(labels).cpu().numpy()
+
+
+@torch.no_grad()
+def extract_features(config, model=None, test_split_only=True):
+    """Image features of the dataset's splits through ``HipEngine.encode_image`` (reference: feature.py:329-376, which builds the
+    model itself; here the caller hands the CLIP model in).  ``test_split_only``: (features (N, D), labels) of the test loader as
+    numpy; otherwise the six arrays train / val / test of the reference."""
+    from .dataloader import construct_dataloader
+    if model is None:
+        raise RuntimeError("extract_features needs the CLIP model whose image tower is to be used")
+    if test_split_only:
+        test = construct_dataloader(config, test_split_only=True)
+        return _engine_features(_image_engine(config, model, test), test)
+    out = []
+    for loader in construct_dataloader(config):
+        out += list(_engine_features(_image_engine(config, model, loader), loader))
+    return tuple(out)
+
+
+@torch.no_grad()
+def zeroshot_scores(config, model, loader, text_features):
+    """The fused zero-shot route: ONE ``HipEngine.zeroshot`` call per batch of ``loader`` (tower + cosine head + softmax).
+    text_features: (D, C) as ``extract_text_features`` returns them (numpy or tensor).  Returns (probabilities (N, C), features
+    (N, D), labels) as numpy."""
+    eng = _image_engine(config, model, loader)
+    text_cd = torch.as_tensor(text_features).to(device=eng.device, dtype=torch.float32).t().contiguous()    # class-major, once
+    probs, feats, labels = [], [], []
+    for x, y in loader:
+        p, f = eng.zeroshot(x.to(eng.device, non_blocking=True), text_cd, scale=100.0, return_features=True)
+        probs.append(p); feats.append(f); labels.append(y)
+    return torch.cat(probs).cpu().numpy(), torch.cat(feats).cpu().numpy(), torch.cat(labels).cpu().numpy()
+
+
 def create_dataloader(dataset, batch_size, shuffle=True, num_workers=6, pin_memory=True):
     """feature.py:585-608: a plain DataLoader without sampler / drop_last."""
     return torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers,
