@@ -404,6 +404,19 @@ typedef struct pevit_gemm_ex_args {
 } pevit_gemm_ex_args;
 int pevit_op_gemm_ex(void* stream, const pevit_gemm_ex_args* args);
 int pevit_op_gemm_sk_slots(void);           /* residency slots of the stream-K workspace on this device (pevit_op_gemm sizes its own by it) */
+/* Debug seams of the GEMM planner (csrc/gemm_plan.hip), callable without a GPU: neither makes a HIP call or touches a pointer.
+ *   pevit_debug_gemm_plan: the plan pevit_op_gemm_ex would launch for `args` on a device of `cus` compute units -- the kernel family
+ *       (path, as pevit_debug_last_gemm_path), operand form, tile configuration and grid.  The planner reads pointers only as set /
+ *       unset and as the B2 - B distance, so made-up non-null addresses do.  Returns 0 with err empty, or -1 with the planner's
+ *       message in err and in pevit_last_error.
+ *   pevit_debug_gemm_epi_traits: which families have an instantiation for an epilogue: bit 0 fp8 B, bit 1 fp8 x fp8, bit 2 the few-row
+ *       kernel, bit 3 the k-split / phased k-split / stream-K kernels; -1 for an unknown epilogue */
+typedef struct pevit_gemm_plan_info {
+    int32_t path, ops, cfg, wm, nl, stag, tiles, grid, band, sk_share, sk_band, tiles_n, nslices, ksl;
+    char err[160];
+} pevit_gemm_plan_info;
+int pevit_debug_gemm_plan(const pevit_gemm_ex_args* args, int cus, pevit_gemm_plan_info* out);
+int pevit_debug_gemm_epi_traits(int epilogue);
 /* Test-only form of the fused post-MLP adapter launches (adapter_fused.hip; tests/test_gpu_adapter_fused.py): EVERY member of the
  * launchers' parameter structs, by name, from one flat argument struct each (zero-initialised = nothing set).  They add no kernel.
  *   act_kind 0 = ReLU (Adapter), 1 = gelu_new (Compacter); E in {256, 512, 768, 1024} (pevit_op_adapter_fused_ok), T >= 1

@@ -46,6 +46,12 @@ class PevitGemmExArgs(C.Structure):
             self.tune_set |= 1 << i
 
 
+class PevitGemmPlanInfo(C.Structure):
+    """pevit_gemm_plan_info of include/pevit_hip.h (pevit_debug_gemm_plan)"""
+    _fields_ = ([(n, C.c_int32) for n in ("path", "ops", "cfg", "wm", "nl", "stag", "tiles", "grid", "band", "sk_share", "sk_band",
+                                          "tiles_n", "nslices", "ksl")] + [("err", C.c_char * 160)])
+
+
 class PevitAdapterFwdArgs(C.Structure):
     """pevit_adapter_fwd_args of include/pevit_hip.h (the test-only pevit_op_adapter_fwd_ex); zero-initialised = nothing set"""
     _fields_ = ([(n, c_void_p) for n in ("hraw", "bpr", "x_mid", "gamma", "beta", "wd", "b_down", "wu", "b_up", "z", "mean_a",
@@ -149,13 +155,15 @@ SIGNATURES = {
     "pevit_op_attn_fwd_delta": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int, P, c_int, c_int, c_int]),
     "pevit_op_attn_delta_hpw": (c_int, [c_int, c_int, c_int]),
     "pevit_op_attn_probs": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int]),
-    # test-only forms (csrc/verify.hip): the step-only members of the launchers' parameter structs
+    # test-only forms (csrc/verify.hip; the GEMM ones csrc/ops.hip): the step-only members of the launchers' parameter structs
     "pevit_op_ln_fwd_ex": (c_int, [P, P, P, P, c_int, c_int, c_size_t, P, P, P, P, P]),
     "pevit_op_ln_bwd_ex": (c_int, [P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, c_int, c_int, c_size_t, P, P]),
     "pevit_op_attn_fwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, c_int, c_int, P]),
     "pevit_op_attn_bwd_ex": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int]),
     "pevit_op_gemm_ex": (c_int, [P, C.POINTER(PevitGemmExArgs)]),
     "pevit_op_gemm_sk_slots": (c_int, []),
+    "pevit_debug_gemm_plan": (c_int, [C.POINTER(PevitGemmExArgs), c_int, C.POINTER(PevitGemmPlanInfo)]),
+    "pevit_debug_gemm_epi_traits": (c_int, [c_int]),
     "pevit_op_adapter_fwd_ex": (c_int, [P, C.POINTER(PevitAdapterFwdArgs)]),
     "pevit_op_adapter_bwd_ex": (c_int, [P, C.POINTER(PevitAdapterBwdArgs)]),
     "pevit_op_adapter_blocks": (c_int, [c_int]),

@@ -9,7 +9,7 @@
 // Compacter: down/up = PHMLinear, H = sum_{i<4} kron(rule_i (4x4), Wl_i Wr_i), act = gelu_new; the
 //            shared rule (4,4,4) is frozen (its name lacks "compacter": compacter_clip.py:122).
 // Both reduce to two dense E x 64 panels, so they share every kernel: the contractions are the MFMA
-// GEMM (gemm.hip, epilogues BIAS_RELU / BIAS_GELUNEW / DRELU / DGELUNEW), and this file holds
+// GEMM (gemm.hip; epilogues BIAS_RELU / BIAS_GELUNEW / DRELU / DGELUNEW of gemm_epilogue.h), and this file holds
 //   * the panel builders (f32 master parameters -> bf16 panels in both orientations, every step),
 //   * the token-contracted weight gradients  G = X^T Y  (LDS-transposed panels + bf16 MFMA),
 //   * LayerNorm backward with gradients for the trainable affine (adapter_norm_before),

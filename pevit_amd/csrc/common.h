@@ -131,7 +131,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 // fp8 (OCP e4m3) operands of the MX matrix instruction are stored k-permuted inside every group of 128 channels, so that the 32
-// codes one MFMA lane needs of a 64-wide k-step are contiguous: [k-step of 64][lane half][16-group][8] (fp8.hip, gemm.hip)
+// codes one MFMA lane needs of a 64-wide k-step are contiguous: [k-step of 64][lane half][16-group][8] (fp8.hip; gemm_tile.hip, gemm_stag8.hip)
 __host__ __device__ __forceinline__ int fp8_kperm(int k) {
     const int grp = k & ~127, kk = k & 127;
     const int par = kk >> 6, ks = (kk >> 4) & 3, half = (kk >> 3) & 1, j = kk & 7;

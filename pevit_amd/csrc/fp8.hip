@@ -9,7 +9,7 @@
 // subnormal range (2^-9 * s).
 //
 // Storage: codes are k-permuted inside every group of 128 input channels (fp8_kperm) so that the 32 codes one MFMA lane
-// needs of a 64-wide k-tile are contiguous (gemm.hip).  The backward GEMMs (dX = dY W) use the TRANSPOSED code matrix;
+// needs of a 64-wide k-tile are contiguous (gemm_tile.hip, gemm_stag8.hip).  The backward GEMMs (dX = dY W) use the TRANSPOSED code matrix;
 // there the contraction runs over the output channels, whose scales are folded into dY by its producer (exact again).
 #include "common.h"
 #include "kernels.h"

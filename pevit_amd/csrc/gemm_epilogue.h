@@ -1,4 +1,4 @@
-// Fused GEMM epilogues, shared by the MFMA kernel (gemm.hip, bf16 storage) and the f32-class verification GEMM
+// Fused GEMM epilogues, shared by the MFMA kernels (the family units of gemm.hip, bf16 storage) and the f32-class verification GEMM
 // (verify.hip, f32 storage): identical arithmetic, the storage type of the bf16-declared buffers is the template
 // parameter ST.
 #pragma once

@@ -43,7 +43,7 @@ struct LayerSaved {        // byte offsets inside the workspace, one per layer (
 
 struct WsLayout {          // byte offsets inside the workspace for one batch (layout_workspace)
     std::vector<LayerSaved> sav;
-    size_t w_skflag, w_skslab;      // stream-K workspace (gemm.hip)
+    size_t w_skflag, w_skslab;      // stream-K workspace (gemm_streamk.hip, gemm_skinny.hip, gemm_split.hip)
     size_t w_a8, w_attn8;           // e4m3 copies of the LayerNorm output / the attention output (fp8act)
     size_t w_xfinal, w_xn2, w_g, w_dqkv, w_u32, w_u32b, w_dO, w_dh, w_dxn, w_dxa, w_dxb, w_dyb, w_partial, w_dbias, w_G, w_rule;
     size_t w_dpre, w_dpre2, w_dht, w_dhb, w_tnU, w_tnD, w_csx, w_csy, w_lnp, w_Gd, w_Gu;
@@ -108,7 +108,7 @@ struct pevit_ctx {
     char* arena = nullptr;
     // workspace: the layout of the batch in flight
     pevit_host::WsLayout lay;
-    int sk_slots = 0;         // stream-K slots (gemm.hip), 0: disabled
+    int sk_slots = 0;         // stream-K slots (gemm_plan.h sk_slots), 0: disabled
     // post-MLP adapter parameter offsets inside one layer's block of the flat buffer (floats)
     size_t o_nw, o_nb, o_dw, o_db, o_uw, o_ub, o_dWl, o_dWr, o_uWl, o_uWr;
     size_t ws_bytes_for_max = 0;

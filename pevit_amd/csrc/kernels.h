@@ -48,17 +48,17 @@ struct GemmParams {
     size_t head_stride;   // elements between the q, k and v planes
     int E, H, Ntok;
     int dbg;              // measurement only: bit 0 skips the k-loop, bit 1 the epilogue stores, bit 2 the operand stream, bit 3 ds_read + MFMA
-    // stream-K workspace (gemm.hip gemm_streamk_kernel): one 128x128 f32 slab and one flag per residency slot, or null
+    // stream-K workspace (gemm_streamk.hip gemm_streamk_kernel): one 128x128 f32 slab and one flag per residency slot, or null
     float* sk_slab; unsigned* sk_flag; int sk_slots;
     int sk_share, sk_band;   // set by the launcher: k-iterations per workgroup, m-tiles per band of the tile walk
-    int band;                // set by the launcher: m-tiles per band of gemm.hip tile_origin (0 = TILE_BAND)
-    int kz;                  // set by the launcher: K slices per tile across WORKGROUPS (gemm_kphase_kernel<..., KZ = true>: 2), else 0
+    int band;                // set by the launcher: m-tiles per band of gemm_device.h tile_origin (0 = TILE_BAND)
+    int kz;                  // set by the launcher: K slices per tile across WORKGROUPS (gemm_split.hip gemm_kphase_kernel<..., KZ = true>: 2), else 0
 };
 
 // A/B-measurement knobs.  They live in the context (pevit_tune(ctx, ...)); the single-kernel pevit_op_* entry
 // points use one process-wide default instance.
 struct GemmTune {
-    int config = -1;      // -1: per-problem heuristic, >= 0: force a tile configuration (gemm.hip kConfigs)
+    int config = -1;      // -1: per-problem heuristic, >= 0: force a tile configuration (gemm_plan.h kConfigs)
     int persistent = 1;
     int ablate = 0;       // GemmParams::dbg
     int kswitch = 2048;   // K from which the few-tile problems use the 128x128 tile instead of 64x128

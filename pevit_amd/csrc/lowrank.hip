@@ -6,7 +6,7 @@
 // (SURVEY 9.5), so the same delta is  ascale * (x P) Q^T + b  with P,Q in R^{E x 32}.  LoRA
 // (lora_model.py:490-514) is the same shape with P = A1^T, Q = A2, rank r <= 32.
 //
-//   t = xn P            fused into the QKV GEMM as 64 extra output columns (gemm.hip)
+//   t = xn P            fused into the QKV GEMM as 64 extra output columns (gemm.hip; EPI_QKV_HEADS, gemm_epilogue.h)
 //   delta-add           q_flat[i] += ascale * t[row] . Q[e] + b[e]        (this file)
 //   u = dDelta Q        16-row MFMA tiles, K = E                          (this file)
 //   dxn += ascale*u P^T fused into the QKV-backward GEMM as 64 extra K columns

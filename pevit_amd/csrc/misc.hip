@@ -69,7 +69,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     // a stream-K hand-off that timed out in this step's GEMMs left a wrong tile behind and raised the context's error
-    // word (gemm.hip): the update is skipped, parameters and momentum stay as they were, and the host finds the word at
+    // word (gemm_streamk.hip): the update is skipped, parameters and momentum stay as they were, and the host finds the word at
     // its next check (engine.check_streamk) -- corrupted gradients never reach the parameters
     // poison2: an error word owned by somebody else (pevit_set_external_poison: the gradient exchange of data parallelism,
     // allreduce.hip) -- a bucket that was never reduced must not reach the parameters either

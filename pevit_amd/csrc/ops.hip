@@ -5,6 +5,7 @@
 #include "../../include/pevit_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "gemm_plan.h"
 
 // What two context calls reach into when they are given no context (host_ctx.h declares both): pevit_tune(nullptr, ...) sets this
 // tune, pevit_streamk_error(nullptr, ...) reads the error word of this workspace.
@@ -230,4 +231,50 @@ extern "C" int pevit_op_zeroshot_head(void* stream, const float* feat, const flo
     return pevit_launch_zeroshot_head(a, (hipStream_t)stream);
 }
 
+// Every member of GemmParams by name, a tune of its own (default-constructed, the set knobs overwritten: the process-wide default tune
+// is not touched) and the caller's stream-K workspace (tests/test_gpu_gemm_forms.py, tests/test_gemm_forms_host.py).
+static void gemm_ex_problem(const pevit_gemm_ex_args* a, GemmParams& p, GemmTune& t) {
+    p = GemmParams{};      // every member zero / null
+    p.A = (const bf16*)a->A; p.lda = a->lda; p.B = a->B; p.ldb = a->ldb; p.Nb = a->b_rows;
+    p.B2 = (const bf16*)a->B2; p.ldb2 = a->ldb2; p.Nb2 = a->b2_rows; p.n_fp8 = a->n_fp8;
+    p.b_fp8 = a->b_fp8; p.a_fp8 = a->a_fp8; p.bscale = a->bscale; p.oscale = a->oscale;
+    p.M = a->M; p.N = a->N; p.K = a->K;
+    p.bias = a->bias; p.resid = a->resid; p.ldr = a->ldr;
+    p.outf = a->out_f32; p.ldo = a->ldo; p.outf2 = a->out_f32_2; p.ldo2 = a->ldo2;
+    p.outb = (bf16*)a->out_bf16; p.ldob = a->ldob; p.outb2 = (bf16*)a->out2_bf16; p.ldob2 = a->ldob2;
+    p.aux = (const bf16*)a->aux_bf16; p.ldaux = a->ldaux;
+    p.head_stride = a->head_stride; p.E = a->E; p.H = a->H; p.Ntok = a->tokens;
+    p.sk_slab = a->sk_slab; p.sk_flag = a->sk_flag; p.sk_slots = a->sk_slots;
+    t = GemmTune{};
+    int* const knob[PEVIT_KNOB_COUNT] = {&t.config, &t.stagger, &t.big, &t.ksplit, &t.ksplit_small, &t.ksplit_stagger, &t.ksplit_mink,
+                                         &t.kphase_nl, &t.kz2, &t.skinny, &t.skinny_slices, &t.streamk, &t.persistent};
+    for (int i = 0; i < PEVIT_KNOB_COUNT; ++i)
+        if (a->tune_set >> i & 1u) *knob[i] = a->tune[i];
+}
+extern "C" int pevit_op_gemm_ex(void* stream, const pevit_gemm_ex_args* a) {
+    if (!a) { pevit_set_error("gemm_ex: null argument struct"); return -1; }
+    GemmParams p; GemmTune t;
+    gemm_ex_problem(a, p, t);
+    return pevit_launch_gemm(a->epilogue, p, t, (hipStream_t)stream);
+}
+extern "C" int pevit_op_gemm_sk_slots(void) { return pevit_gemm_sk_slots(); }
+
 extern "C" int pevit_debug_last_gemm_path(void) { return pevit_gemm_last_path(); }
+// The plan of the problem pevit_op_gemm_ex would launch, on a device of `cus` compute units.  No HIP call, no pointer touched: the
+// planner reads pointers as set / unset and as the B2 - B distance, so this runs without a GPU (tests/test_gemm_forms_host.py).
+extern "C" int pevit_debug_gemm_plan(const pevit_gemm_ex_args* a, int cus, pevit_gemm_plan_info* out) {
+    if (!a || !out) { pevit_set_error("gemm_plan: null argument"); return -1; }
+    GemmParams p; GemmTune t;
+    gemm_ex_problem(a, p, t);
+    const pevit_gemm::GemmPlan pl = pevit_gemm::plan_gemm(a->epilogue, p, t, cus);
+    *out = pevit_gemm_plan_info{pl.path, pl.ops, pl.cfg, pl.wm, pl.nl, pl.stag, pl.tiles, pl.grid, pl.band, pl.sk.share, pl.sk.band,
+                                pl.tiles_n, pl.nslices, pl.ksl, {}};
+    memcpy(out->err, pl.err, sizeof(out->err));
+    if (pl.err[0]) { pevit_set_error("%s", pl.err); return -1; }
+    return 0;
+}
+extern "C" int pevit_debug_gemm_epi_traits(int epilogue) {
+    if (epilogue < EPI_QKV_HEADS || epilogue > EPI_LAST) return -1;
+    const pevit_gemm::EpiTraits tr = pevit_gemm::epi_traits(epilogue);
+    return (int)tr.fp8b | (int)tr.fp8a << 1 | (int)tr.skinny << 2 | (int)tr.ksplit << 3;
+}

@@ -435,29 +435,6 @@ extern "C" int pevit_op_attn_bwd_ex(void* stream, const void* q, const void* k, 
     a.dout_cls_only = dout_cls_only;
     return pevit_launch_attn_bwd(a, (hipStream_t)stream);
 }
-// Every member of GemmParams by name, a tune of its own (default-constructed, the set knobs overwritten: the process-wide default tune
-// is not touched) and the caller's stream-K workspace (tests/test_gpu_gemm_forms.py).
-extern "C" int pevit_op_gemm_ex(void* stream, const pevit_gemm_ex_args* a) {
-    if (!a) { pevit_set_error("gemm_ex: null argument struct"); return -1; }
-    GemmParams p{};      // every member zero / null
-    p.A = (const bf16*)a->A; p.lda = a->lda; p.B = a->B; p.ldb = a->ldb; p.Nb = a->b_rows;
-    p.B2 = (const bf16*)a->B2; p.ldb2 = a->ldb2; p.Nb2 = a->b2_rows; p.n_fp8 = a->n_fp8;
-    p.b_fp8 = a->b_fp8; p.a_fp8 = a->a_fp8; p.bscale = a->bscale; p.oscale = a->oscale;
-    p.M = a->M; p.N = a->N; p.K = a->K;
-    p.bias = a->bias; p.resid = a->resid; p.ldr = a->ldr;
-    p.outf = a->out_f32; p.ldo = a->ldo; p.outf2 = a->out_f32_2; p.ldo2 = a->ldo2;
-    p.outb = (bf16*)a->out_bf16; p.ldob = a->ldob; p.outb2 = (bf16*)a->out2_bf16; p.ldob2 = a->ldob2;
-    p.aux = (const bf16*)a->aux_bf16; p.ldaux = a->ldaux;
-    p.head_stride = a->head_stride; p.E = a->E; p.H = a->H; p.Ntok = a->tokens;
-    p.sk_slab = a->sk_slab; p.sk_flag = a->sk_flag; p.sk_slots = a->sk_slots;
-    GemmTune t;
-    int* const knob[PEVIT_KNOB_COUNT] = {&t.config, &t.stagger, &t.big, &t.ksplit, &t.ksplit_small, &t.ksplit_stagger, &t.ksplit_mink,
-                                         &t.kphase_nl, &t.kz2, &t.skinny, &t.skinny_slices, &t.streamk, &t.persistent};
-    for (int i = 0; i < PEVIT_KNOB_COUNT; ++i)
-        if (a->tune_set >> i & 1u) *knob[i] = a->tune[i];
-    return pevit_launch_gemm(a->epilogue, p, t, (hipStream_t)stream);
-}
-extern "C" int pevit_op_gemm_sk_slots(void) { return pevit_gemm_sk_slots(); }
 // The fused post-MLP adapter launches (adapter_fused.hip; tests/test_gpu_adapter_fused.py): every member of AdapterFwdArgs /
 // AdapterBwdArgs by name, the contraction range of the backward included.
 extern "C" int pevit_op_adapter_fwd_ex(void* stream, const pevit_adapter_fwd_args* a) {

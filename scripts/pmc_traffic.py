@@ -40,7 +40,7 @@ def family(stats, needles):
     return n, tot
 
 
-GEMM_FAMILY = ("gemm_kernel<", "gemm8_kernel<", "gemm_streamk_kernel<", "gemm_ksplit_kernel<", "gemm_kphase_kernel<")   # every kernel of pevit_amd/csrc/gemm.hip
+GEMM_FAMILY = ("gemm_kernel<", "gemm8_kernel<", "gemm_streamk_kernel<", "gemm_ksplit_kernel<", "gemm_kphase_kernel<")   # every kernel of the family units of pevit_amd/csrc/gemm.hip: gemm_tile.hip, gemm_stag8.hip, gemm_streamk.hip, gemm_split.hip
 
 
 def main():

@@ -1,8 +1,9 @@
 """Host side of tests/test_gpu_gemm_forms.py (no GPU): the case table of the GEMM family, the operand generator, the float64
-references of the fifteen epilogues, and the evidence that the comparison can see what it is meant to see.  The kernel is nowhere
-in sight.
+references of the fifteen epilogues, and the evidence that the comparison can see what it is meant to see.  No kernel is
+launched: the last section calls the planner (csrc/gemm_plan.hip, pure host code) through pevit_debug_gemm_plan.
 
-gemm.hip instantiates kernels from fifteen epilogues, seven kernel families (GemmPlan::path 1..7) and three operand forms (bf16 x
+The family units of gemm.hip (gemm_tile.hip, gemm_stag8.hip, gemm_split.hip, gemm_streamk.hip, gemm_skinny.hip) instantiate kernels
+from fifteen epilogues, seven kernel families (GemmPlan::path 1..7) and three operand forms (bf16 x
 bf16, bf16 x fp8 B -- with or without a bf16 tail --, fp8 x fp8).  The GPU file launches every (family, epilogue, operand form)
 combination that has an instantiation and compares it BIT FOR BIT with the float64 reference stated here.  That is possible because
 the operands are small integers times powers of two:
@@ -28,15 +29,25 @@ statement `exists` admits and none twice; and the bite: for each epilogue the re
 would be wrong (one k-tile dropped, bias of column n + 1, residual / aux / positional row m + 1, PATCH_EMBED without its + 1, the
 `which` and `h` indices of the head layout swapped, KEEP's outputs exchanged, the t columns taken with the bias) and must differ
 from the true one -- the generated inputs are not degenerate for that fault.
+
+The planner: the hand-written trait sets below equal epi_traits of the library for all fifteen epilogues; for every case of the table
+plan_gemm at 256 CUs takes the family the case names, with the configuration, slice count, grid and band the variant and the shape
+comments state; every absent combination is refused or falls to another family as absent_outcome says; and the plain-tile cases plan
+without error at 304 and at 64 CUs within the residency slots of their configuration (the CU count is the only device fact the planner
+is given).
 """
 import collections
+import ctypes as C
 import functools
+import os
+import types
 
 import pytest
 import torch
 
 from conftest import max_rel
-from pevit_amd import fp8
+from pevit_amd import _lib, fp8
+from pevit_amd._lib import PevitGemmExArgs, PevitGemmPlanInfo
 
 # ---------------------------------------------------------------------------------------------------- epilogues, operand forms
 (QKV, BIAS_RESID, BIAS_GELU, DGELU, F32, BF16, BIAS_BF16, PATCH, BIAS_RELU, KEEP, BIAS_GELUNEW, DRELU, DGELUNEW, BIAS_F32,
@@ -48,7 +59,7 @@ OPS_BF16, OPS_FP8B, OPS_FP8A, OPS_TAIL = 0, 1, 2, 3        # TAIL: fp8 B with a 
 OPS_NAMES = ("bf16", "fp8b", "fp8xfp8", "fp8b+tail")
 NONLINEAR_GATE = 1e-2                                       # tests/test_gpu_ops.py: bf16 outputs, relative to the largest magnitude
 
-# gemm.hip epi_traits, restated: which families have an instantiation for an epilogue
+# gemm_plan.h epi_traits, restated: which families have an instantiation for an epilogue (checked against the library below)
 FP8B_EPIS = frozenset((QKV, BIAS_RESID, BIAS_GELU, GELU_ONLY, DGELU, F32, BF16, BIAS_F32))
 FP8A_EPIS = frozenset((QKV, BIAS_RESID, BIAS_GELU, GELU_ONLY, F32))
 FEWROW_EPIS = frozenset((BIAS_RESID, F32, BF16, KEEP, BIAS_GELU, GELU_ONLY, DGELU))
@@ -58,7 +69,7 @@ SPLIT_PATHS = (3, 4, 5, 7)
 
 
 def exists(path, epi, ops):
-    """does gemm.hip (launch_plan) instantiate family `path` for this epilogue and operand form?"""
+    """do the family units of gemm.hip (FAMILY::launch) instantiate family `path` for this epilogue and operand form?"""
     if ops == OPS_FP8A:
         return path == 2 and epi in FP8A_EPIS            # always the 160x256 tile of the staggered kernel
     if ops == OPS_TAIL:
@@ -211,6 +222,35 @@ def geometry(epi, M, N, ops=OPS_BF16):
         G2 = _divisor(M)                 # 333 = 37 x 9, 3828 = 348 x 11, 3971 = 361 x 11, 2296 = 328 x 7, 300 = 30 x 10, 37 = 1 x 37
         return dict(E=0, H=0, Ntok=G2 + 1, Bt=M // G2)
     return dict(E=0, H=0, Ntok=0, Bt=0)
+
+
+# ---------------------------------------------------------------------------------------------------- pitches of one launch
+TAIL_ROWS = 64                      # rows of the bf16 tail B2 (P_q^T | P_v^T)
+
+
+def pitches(c):
+    """row pitches of one launch: pairwise different, none equal to a width of the problem"""
+    widths, taken, p = {c.N, c.K, 64}, set(), {}
+
+    def take(name, base):
+        v = base + 16
+        while v in taken or v in widths:
+            v += 16
+        taken.add(v)
+        p[name] = v
+
+    if path_of(c) == 6:
+        p["lda"] = 3 * c.K                       # the class-token rows of the step: every third row of a [3M][K] buffer
+        taken.add(p["lda"])
+    else:
+        take("lda", c.K)
+    take("ldb", c.K); take("ldb2", c.K)
+    for name in ("ldr", "ldo", "ldo2", "ldob", "ldob2", "ldaux"):
+        take(name, c.N)
+    if c.epi == QKV:
+        take("ldo", 64)
+    assert len(set(p.values())) == len(p) and not set(p.values()) & widths
+    return types.SimpleNamespace(**p)
 
 
 # ---------------------------------------------------------------------------------------------------- operands
@@ -469,3 +509,100 @@ def test_nonlinear_operands_cover_the_live_range():
     h = accumulate(o) + o["bias"].double()
     assert float(h.min()) < -3 and float(h.max()) > 3 and float(((h.abs() > 0.2) & (h.abs() < 1.5)).double().mean()) > 0.05
     assert float(o["aux"].min()) == -3 and float(o["aux"].max()) == 3
+
+
+# ---------------------------------------------------------------------------------------------------- the planner itself, no GPU
+# pevit_debug_gemm_plan runs plan_gemm (csrc/gemm_plan.hip) on the argument struct pevit_op_gemm_ex would launch.  The planner reads
+# pointers only as set / unset and as the B2 - B distance, so the addresses are made up: B2 behind B at the distance b_buffer of
+# the GPU file gives it, a workspace of sk_slots(256) slots, the pitches of pitches(c).
+CUS = 256
+WGS = {0: 2, 1: 3, 2: 4, 3: 1, 4: 1, 5: 1, 6: 3, 7: 2, 8: 2}      # gemm_plan.h kConfigs: workgroups per CU of a tile configuration
+_A0, _B0, _WS0 = 0x10000000, 0x20000000, 0x40000000
+
+
+def sk_slots(cus):
+    return min(2 * cus, 1024) & ~7
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _lib.load()
+
+
+def plan_args(c):
+    p = pitches(c)
+    a = PevitGemmExArgs()
+    a.set_tune(**tune_of(c))
+    n8 = TAIL_NFP8 if c.ops == OPS_TAIL else c.N
+    a.epilogue, a.M, a.N, a.K = c.epi, c.M, c.N, c.K
+    a.A, a.lda, a.B, a.ldb, a.b_rows = _A0, p.lda, _B0, p.ldb, n8 + 8
+    a.b_fp8, a.a_fp8 = int(c.ops != OPS_BF16), int(c.ops == OPS_FP8A)
+    if c.ops == OPS_TAIL:                                        # the tail behind the codes, 256-byte aligned (b_buffer)
+        a.B2, a.ldb2, a.b2_rows, a.n_fp8 = _B0 + ((n8 + 8) * p.ldb + 255) // 256 * 256, p.ldb2, TAIL_ROWS + 8, n8
+    a.ldr, a.ldo, a.ldo2, a.ldob, a.ldob2, a.ldaux = p.ldr, p.ldo, p.ldo2, p.ldob, p.ldob2, p.ldaux
+    slots = sk_slots(CUS)
+    a.sk_flag, a.sk_slab, a.sk_slots = _WS0, _WS0 + (slots + 1) * 4, slots
+    return a
+
+
+def plan(lib, c, cus=CUS):
+    """(rc, pevit_gemm_plan_info) of case c on a device of `cus` compute units"""
+    a, info = plan_args(c), PevitGemmPlanInfo()
+    rc = lib.pevit_debug_gemm_plan(C.byref(a), cus, C.byref(info))
+    assert (rc == 0 and info.err == b"") or (rc == -1 and info.err and info.err == lib.pevit_last_error())
+    return rc, info
+
+
+def test_trait_sets_are_the_librarys(lib):
+    for e in ALL_EPIS:
+        want = int(e in FP8B_EPIS) | int(e in FP8A_EPIS) << 1 | int(e in FEWROW_EPIS) << 2 | int(e in SPLIT_EPIS) << 3
+        assert lib.pevit_debug_gemm_epi_traits(e) == want, EPI_NAMES[e]
+    assert lib.pevit_debug_gemm_epi_traits(-1) == -1 and lib.pevit_debug_gemm_epi_traits(len(ALL_EPIS)) == -1
+    assert PATCH not in FEWROW_EPIS and KEEP in FEWROW_EPIS
+
+
+@pytest.mark.parametrize("c", CASES, ids=case_id)
+def test_planner_takes_the_named_family(lib, c):
+    rc, pl = plan(lib, c)
+    assert rc == 0, pl.err
+    assert pl.path == path_of(c), f"the planner takes family {pl.path} at {CUS} CUs, the case names {path_of(c)}"
+    kind, _, arg = c.variant.partition("-")
+    if kind in ("stag", "tile"):
+        assert pl.cfg == int(arg[3:])                                   # the forced configuration
+    if kind == "kphase":
+        assert pl.nl == int(arg[2:])
+    if kind in ("ksplit", "kphase"):
+        assert pl.wm == (3 if c.M == 2296 else 5)                       # SPLIT_SHAPES: 2296 rows take the 96x128 tile
+        assert pl.band == {3828: 3, 3971: 0}.get(c.M, pl.band)          # ... and the XCD-aligned bands stated there
+    if kind == "ksplit":
+        assert pl.stag == int(arg == "s1" or pl.wm == 3)                # 96x128 is always staggered
+    if kind == "fewrow":
+        assert c.K == FEWROW_K and pl.nslices == (int(arg[1:]) or 2)    # s0: the automatic rule, two slices at 24 k-tiles
+    if (c.M, c.N, c.K) == MANY_TILES:
+        assert (pl.tiles, pl.grid) == (306, 256)                        # the persistent walk takes a second tile
+    if kind == "streamk" and c.K == 2112:
+        assert (pl.sk_share, pl.grid) == (18, 16)                       # LONG_KS
+
+
+@pytest.mark.parametrize("c", ABSENT, ids=case_id)
+def test_planner_on_absent_combinations(lib, c):
+    rc, pl = plan(lib, c)
+    if absent_outcome(path_of(c), c.epi, c.ops) == "refused":
+        assert rc == -1 and pl.err
+    else:
+        assert rc == 0 and pl.path != path_of(c)
+
+
+def test_cus_is_the_only_device_fact_the_planner_uses(lib):
+    """the plain-tile cases plan on any device: no error, and never more workgroups than the residency slots of the configuration"""
+    n = 0
+    for c in CASES:
+        if c.variant.startswith("tile-"):
+            for cus in (304, 64):
+                rc, pl = plan(lib, c, cus)
+                assert rc == 0 and pl.path == 1 and 0 < pl.grid <= WGS[pl.cfg] * cus, (case_id(c), cus, pl.grid)
+                n += 1
+    assert n >= 2 * 9 * len(ALL_EPIS)

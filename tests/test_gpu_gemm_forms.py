@@ -1,8 +1,10 @@
-"""Every GEMM epilogue on every kernel family and operand form that gemm.hip instantiates, bit for bit.
+"""Every GEMM epilogue on every kernel family and operand form that the family units of gemm.hip (gemm_tile.hip, gemm_stag8.hip,
+gemm_split.hip, gemm_streamk.hip, gemm_skinny.hip) instantiate, bit for bit.
 
-Everything runs through the test-only pevit_op_gemm_ex (csrc/verify.hip: it fills GemmParams by name, takes a tune of its own --
+Everything runs through the test-only pevit_op_gemm_ex (csrc/ops.hip: it fills GemmParams by name, takes a tune of its own --
 the process-wide default tune is never touched -- and the caller's stream-K workspace).  The case table, the operands and the
-float64 references come from tests/test_gemm_forms_host.py, which also proves on the CPU that the operands make every sum exact in
+float64 references come from tests/test_gemm_forms_host.py, which also asks the planner itself (csrc/gemm_plan.hip, no GPU needed) for
+the family of every case, and proves on the CPU that the operands make every sum exact in
 f32 and that the comparison sees the faults it is meant to see.
 
 Gates.  Linear outputs (f32, and bf16 as round-to-nearest-even of an exact value -- the pre-activation h of the GELU epilogues and
@@ -39,7 +41,8 @@ from conftest import max_rel
 from pevit_amd._lib import PevitGemmExArgs
 from test_gemm_forms_host import (ABSENT, BIAS_GELU, BIAS_GELUNEW, BIAS_RESID, CASES, DGELU, DGELUNEW, DRELU, EPI_NAMES, F32, GELU_ONLY,
                                   KEEP, LINEAR_BF16, LINEAR_F32, NONLINEAR_GATE, OPS_BF16, OPS_FP8A, OPS_FP8B, OPS_TAIL, PATCH, QKV,
-                                  VARIANTS, Case, absent_outcome, activation, case_id, geometry, operands, path_of, reference)
+                                  TAIL_ROWS, VARIANTS, Case, absent_outcome, activation, case_id, geometry, operands, path_of, pitches,
+                                  reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -119,9 +122,6 @@ def a_buffer(M, N, K, ops, lda):
     return buf
 
 
-TAIL_ROWS = 64
-
-
 @functools.lru_cache(maxsize=4)
 def b_buffer(M, N, K, ops, ldb, ldb2, b2_first=False):
     """(allocation, B view, B2 view or None).  B has 8 readable rows more than it has columns of the product; they hold NaN."""
@@ -146,31 +146,6 @@ def b_buffer(M, N, K, ops, ldb, ldb2, b2_first=False):
     tail.fill_(NAN)
     tail[:TAIL_ROWS, :K] = d["W"][n8:].to(torch.bfloat16)
     return raw, codes, tail
-
-
-def pitches(c):
-    """row pitches of one launch: pairwise different, none equal to a width of the problem"""
-    widths, taken, p = {c.N, c.K, 64}, set(), {}
-
-    def take(name, base):
-        v = base + 16
-        while v in taken or v in widths:
-            v += 16
-        taken.add(v)
-        p[name] = v
-
-    if path_of(c) == 6:
-        p["lda"] = 3 * c.K                       # the class-token rows of the step: every third row of a [3M][K] buffer
-        taken.add(p["lda"])
-    else:
-        take("lda", c.K)
-    take("ldb", c.K); take("ldb2", c.K)
-    for name in ("ldr", "ldo", "ldo2", "ldob", "ldob2", "ldaux"):
-        take(name, c.N)
-    if c.epi == QKV:
-        take("ldo", 64)
-    assert len(set(p.values())) == len(p) and not set(p.values()) & widths
-    return types.SimpleNamespace(**p)
 
 
 # ------------------------------------------------------------------------------------------------ one launch
