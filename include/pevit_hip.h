@@ -243,6 +243,45 @@ int pevit_zeroshot_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const
 /* the zero-shot head alone, context-free (parity tests): feat (B x D), text_cd (C x D), outputs (B x C) */
 int pevit_op_zeroshot_head(void* stream, const float* feat, const float* text_cd, float scale, float* probs_or_null,
                            float* logits_or_null, int B, int D, int C);
+/* ---- the linear probe on CACHED features (evaluation/full_model_finetune.py with FREEZE_IMAGE_BACKBONE: nothing below the head
+ * trains, so every image needs the tower once per checkpoint -- pevit_encode_image -- and every step and every validation after
+ * that is head-only work on rows of a feature matrix).  Both entries need a bound image context of method PEVIT_NONE with
+ * parameters set (pevit_set_params: the head weight [C][D] and bias [C] are the whole flat buffer); a text context, another
+ * method and an unbound context are refused.  Limits, refused before any launch: D (pevit_dims.out_dim) a multiple of 16 up to
+ * 1024, num_classes <= 1024, feat 16-byte aligned.
+ * pevit_probe_step: ONE training step as two launches.  x = feat[index[b]] (index values are clamped to [0, rows) on the device),
+ * logits = scale * (BatchNorm1d(x) W^T + bias) in exact f32 (scale = exp(logit_scale), frozen: reference line 156; 1 for the plain
+ * head), mean cross-entropy over labels[index[b]] (int64, ignore_index -100 as torch) or mean BCE-with-logits over
+ * targets[index[b]][:] (f32) -- exactly one of labels / targets.  bn_training: batch statistics + PyTorch's running-statistics
+ * update (unbiased variance, momentum 0.1, eps 1e-5), else the running statistics.  The head's gradients are WRITTEN to the
+ * gradient buffer (pevit_zero_grads is not needed before).  update != 0: torch.optim.SGD on the head inside the second launch
+ * with lr / momentum / weight_decay and the flags of pevit_sgd_step (bit 0 first step, bit 1 Nesterov); the stream-K and external
+ * error words do not gate it (no stream-K product ran).  update == 0: parameters and momentum are untouched and the caller follows
+ * with pevit_optim_step.  Writes logits (batch x C) and loss (1), which may be rows of the caller's epoch buffers.
+ * 2 <= batch <= max_batch of the bound workspace (its head slots hold the hand-over between the two launches; a saved forward is
+ * dropped).  Every reduction runs in a fixed order: the same call from the same state gives the same bits.
+ * pevit_probe_predict: logits = scale * (BatchNorm1d_eval(x) W^T + bias) for `count` rows in ONE launch: x = feat[index[i]], or
+ * feat[first_row + i] with a null index.  count >= 1 is not bounded by max_batch (nothing is staged in the workspace); a row's
+ * bits do not depend on the other rows of the call.  Reads parameters and running statistics, writes logits (count x C) only. */
+typedef struct pevit_probe_args {
+    const float* feat; int64_t rows;           /* cached features (rows x D) */
+    const int64_t* index;                      /* (batch) rows of feat */
+    const int64_t* labels;                     /* (rows) class indices, or NULL */
+    const float* targets;                      /* (rows x C) multi-hot / soft targets, or NULL */
+    float* running_mean; float* running_var;   /* (D) */
+    float* logits; float* loss;                /* (batch x C), (1) */
+    int batch, bn_training, update, flags;
+    float scale, lr, momentum, weight_decay;
+} pevit_probe_args;
+int pevit_probe_step(pevit_ctx* ctx, void* stream, const pevit_probe_args* args);
+typedef struct pevit_probe_predict_args {
+    const float* feat; int64_t rows;
+    const int64_t* index_or_null; int64_t first_row; int count;
+    const float* running_mean; const float* running_var;
+    float scale;
+    float* logits;                             /* (count x C) */
+} pevit_probe_predict_args;
+int pevit_probe_predict(pevit_ctx* ctx, void* stream, const pevit_probe_predict_args* args);
 /* ---- the CLIP text tower (CLIP.encode_text, model.py:1153-1168): token ids (S x N) int64 -> text features (S x D) f32 in one call.
  * A text context is a pevit_ctx like any other -- method PEVIT_NONE, H = width / 64 heads, N = context_length tokens per prompt,
  * causal attention -- so pevit_arena_bytes, pevit_bind, pevit_load_block (q rows pre-scaled by 1/8 as for the image tower) and

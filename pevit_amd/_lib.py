@@ -72,6 +72,20 @@ class PevitOptimGroup(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("lr", "weight_decay", "momentum", "beta1", "beta2", "eps")] + [("nesterov", C.c_int)]
 
 
+class PevitProbeArgs(C.Structure):
+    """pevit_probe_args of include/pevit_hip.h (pevit_probe_step); zero-initialised = nothing set"""
+    _fields_ = ([("feat", c_void_p), ("rows", C.c_int64), ("index", c_void_p), ("labels", c_void_p), ("targets", c_void_p),
+                 ("running_mean", c_void_p), ("running_var", c_void_p), ("logits", c_void_p), ("loss", c_void_p)] +
+                [(n, C.c_int) for n in ("batch", "bn_training", "update", "flags")] +
+                [(n, C.c_float) for n in ("scale", "lr", "momentum", "weight_decay")])
+
+
+class PevitProbePredictArgs(C.Structure):
+    """pevit_probe_predict_args of include/pevit_hip.h (pevit_probe_predict)"""
+    _fields_ = [("feat", c_void_p), ("rows", C.c_int64), ("index_or_null", c_void_p), ("first_row", C.c_int64), ("count", C.c_int),
+                ("running_mean", c_void_p), ("running_var", c_void_p), ("scale", C.c_float), ("logits", c_void_p)]
+
+
 OPTIM_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}           # enum pevit_optim_kind
 OPTIM_MAX_GROUPS = 8                                       # PEVIT_OPTIM_MAX_GROUPS
 OPTIM_NO_GRAD = 255                                        # group_of value of an element whose parameter has .grad None
@@ -116,6 +130,8 @@ SIGNATURES = {
     "pevit_zeroshot": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int]),
     "pevit_zeroshot_u8": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int]),
     "pevit_op_zeroshot_head": (c_int, [P, P, P, c_float, P, P, c_int, c_int, c_int]),
+    "pevit_probe_step": (c_int, [P, P, C.POINTER(PevitProbeArgs)]),
+    "pevit_probe_predict": (c_int, [P, P, C.POINTER(PevitProbePredictArgs)]),
     "pevit_text_create": (c_int, [C.POINTER(PevitTextDims), C.POINTER(c_void_p)]),
     "pevit_load_text_stem": (c_int, [P, P] + [P] * 5),
     "pevit_encode_text": (c_int, [P, P, P, P, c_int]),

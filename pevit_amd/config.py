@@ -108,6 +108,7 @@ def default_config() -> CfgNode:
                    SEARCH_RESULT_ON_LAST_EPOCH=False, OPTIMIZER="sgd", MOMENTUM=0.9, WD=0.0001, WD_SEARCH_LEFT=False,
                    SWEEP_CONCURRENCY=2,      # sweep runs at a time, each on its own stream (not a reference key; 1 = sequential)
                    FUSED_OPTIMIZER=True,     # Adam / AdamW / SGD with several groups as one fused launch (not a reference key; False: torch's own step())
+                   CACHE_FEATURES=True,      # linear probe: encode every image once per checkpoint and train the head on the cached rows (not a reference key; False: every step runs the tower)
                    TEXT_TOWER_ENGINE=False,  # INIT_HEAD_WITH_TEXT_ENCODER: all prompts through the engine's text tower in chunks instead of one torch call per class (not a reference key)
                    WITHOUT_WD_LIST=[], NESTEROV=True, BEGIN_EPOCH=0, END_EPOCH=100, EXTRA_FINAL_TRAIN_EPOCH=0,
                    EMULATE_ZERO_SHOT=False, BATCH_SIZE_PER_GPU=32, SHUFFLE=True, RMSPROP_ALPHA=0.99, RMSPROP_CENTERED=False),

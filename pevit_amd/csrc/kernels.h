@@ -407,3 +407,22 @@ struct ZeroshotArgs {
 };
 int pevit_zeroshot_check(const ZeroshotArgs& a);      // 0, or -1 with the error text set; launches nothing
 int pevit_launch_zeroshot_head(const ZeroshotArgs& a, hipStream_t s);
+
+// ---- probe.hip (the linear probe's head on cached feature rows: a two-launch training step and a one-launch predict) ----
+// feat [rows][D] f32 (16-byte aligned); index [B] int64 rows of feat, or null: rows row0 .. row0 + B - 1; labels [rows] int64
+// (cross-entropy) or targets [rows][C] f32 (BCE with logits), indexed like feat.  pW / pB, gW / gB, mW / mB: the head's weight
+// [C][D] and bias [C] in the parameter, gradient and momentum buffers.  xhat [B][D], dlogits [B][C], rowloss [B + 1] (the row losses, then the count of non-ignored rows): scratch that
+// launch 1 hands to launch 2.  D a multiple of 16 up to 1024, C <= 1024: pevit_probe_check refuses the rest.
+struct ProbeArgs {
+    const float* feat = nullptr; const int64_t* index = nullptr; const int64_t* labels = nullptr; const float* targets = nullptr;
+    const float* W = nullptr; const float* bias = nullptr;
+    float* pW = nullptr; float* pB = nullptr; float* gW = nullptr; float* gB = nullptr; float* mW = nullptr; float* mB = nullptr;
+    float* running_mean = nullptr; float* running_var = nullptr;
+    float* xhat = nullptr; float* dlogits = nullptr; float* rowloss = nullptr; float* logits = nullptr; float* loss = nullptr;
+    long rows = 0, row0 = 0;
+    int B = 0, D = 0, C = 0, training = 0, update = 0, flags = 0;      // flags: bit 0 = first step, bit 1 = Nesterov (pevit_sgd_step)
+    float scale = 1.f, lr = 0.f, momentum = 0.f, wd = 0.f;
+};
+int pevit_probe_check(int D, int C, const char* who);      // 0, or -1 with the error text set; launches nothing
+int pevit_launch_probe_step(const ProbeArgs& a, hipStream_t s);
+int pevit_launch_probe_predict(const ProbeArgs& a, hipStream_t s);

@@ -342,6 +342,72 @@ extern "C" int pevit_zeroshot_u8(pevit_ctx* c, void* stream, const uint8_t* imag
     return zeroshot_impl(c, stream, images, 1, text_cd, num_classes, scale, probs_or_null, logits_or_null, feat_or_null, B);
 }
 
+// ---- the linear probe on cached feature rows (probe.hip): context checks in the order a caller can meet them without a device
+static int probe_check_ctx(const pevit_ctx* c, const char* who) {
+    if (!c) { pevit_set_error("%s: null context", who); return -1; }
+    CHECK(refuse_text(c, who));
+    if (c->d.method != PEVIT_NONE) {
+        pevit_set_error("%s: the context's method is not PEVIT_NONE (the probe trains the head over a frozen tower; the adapter "
+                        "methods train through pevit_train_forward_backward)", who);
+        return -1;
+    }
+    return pevit_probe_check(c->D, c->C, who);
+}
+static int probe_check_bound(const pevit_ctx* c, const char* who) {
+    if (!c->arena || !c->ws) { pevit_set_error("%s: context not bound", who); return -1; }
+    if (!c->params || !c->grads || !c->mom) { pevit_set_error("%s: parameters not set (pevit_set_params)", who); return -1; }
+    return 0;
+}
+extern "C" int pevit_probe_step(pevit_ctx* c, void* stream, const pevit_probe_args* p) {
+    CHECK(probe_check_ctx(c, "probe_step"));
+    if (!p) { pevit_set_error("probe_step: null argument struct"); return -1; }
+    // torch.nn.BatchNorm1d refuses one value per channel in training mode and the reference's train_one skips such batches
+    // (full_model_finetune.py:316); the harness skips them too, so a batch of one is a caller's mistake in either mode
+    if (p->batch < 2) { pevit_set_error("probe_step: batch %d must be at least 2", p->batch); return -1; }
+    CHECK(probe_check_bound(c, "probe_step"));
+    if (p->batch > c->max_batch) { pevit_set_error("probe_step: batch %d exceeds max_batch %d of the bound workspace", p->batch, c->max_batch); return -1; }
+    if (!p->feat || !p->index || !p->running_mean || !p->running_var || !p->logits || !p->loss) { pevit_set_error("probe_step: null argument"); return -1; }
+    if (!p->labels == !p->targets) { pevit_set_error("probe_step: exactly one of labels and targets must be given"); return -1; }
+    if (p->rows < 1) { pevit_set_error("probe_step: %lld feature rows (at least 1)", (long long)p->rows); return -1; }
+    if (p->rows > 0x7fffffffLL) { pevit_set_error("probe_step: %lld feature rows (at most 2^31 - 1)", (long long)p->rows); return -1; }
+    if (reinterpret_cast<size_t>(p->feat) & 15) { pevit_set_error("probe_step: feat must be 16-byte aligned"); return -1; }
+    c->saved = SavedForward{};                    // the head slots of the workspace are laid out for THIS batch
+    c->lay = layout_workspace(c, p->batch);
+    char* W = c->ws;
+    ProbeArgs a;
+    a.feat = p->feat; a.index = p->index; a.labels = p->labels; a.targets = p->targets; a.rows = (long)p->rows;
+    a.W = a.pW = c->params + c->p_head_w; a.bias = a.pB = c->params + c->p_head_b;
+    a.gW = c->grads + c->p_head_w; a.gB = c->grads + c->p_head_b; a.mW = c->mom + c->p_head_w; a.mB = c->mom + c->p_head_b;
+    a.running_mean = p->running_mean; a.running_var = p->running_var;
+    a.xhat = at<float>(W, c->lay.w_ybn); a.dlogits = at<float>(W, c->lay.w_dlogits); a.rowloss = at<float>(W, c->lay.w_dybn);
+    a.logits = p->logits; a.loss = p->loss;
+    a.B = p->batch; a.D = c->D; a.C = c->C; a.training = p->bn_training != 0; a.update = p->update != 0; a.flags = p->flags;
+    a.scale = p->scale; a.lr = p->lr; a.momentum = p->momentum; a.wd = p->weight_decay;
+    c->last_loss = a.update ? nullptr : p->loss;     // (a following pevit_optim_step writes NaN there when an error word withholds it)
+    return pevit_launch_probe_step(a, (hipStream_t)stream);
+}
+extern "C" int pevit_probe_predict(pevit_ctx* c, void* stream, const pevit_probe_predict_args* p) {
+    CHECK(probe_check_ctx(c, "probe_predict"));
+    if (!p) { pevit_set_error("probe_predict: null argument struct"); return -1; }
+    if (p->count < 1) { pevit_set_error("probe_predict: %d rows (at least 1)", p->count); return -1; }
+    CHECK(probe_check_bound(c, "probe_predict"));
+    if (!p->feat || !p->running_mean || !p->running_var || !p->logits) { pevit_set_error("probe_predict: null argument"); return -1; }
+    if (p->rows < 1) { pevit_set_error("probe_predict: %lld feature rows (at least 1)", (long long)p->rows); return -1; }
+    if (!p->index_or_null && (p->first_row < 0 || p->first_row + p->count > p->rows)) {
+        pevit_set_error("probe_predict: rows [%lld, %lld) outside the %lld feature rows", (long long)p->first_row,
+                        (long long)(p->first_row + p->count), (long long)p->rows);
+        return -1;
+    }
+    if (p->rows > 0x7fffffffLL) { pevit_set_error("probe_predict: %lld feature rows (at most 2^31 - 1)", (long long)p->rows); return -1; }
+    if (reinterpret_cast<size_t>(p->feat) & 15) { pevit_set_error("probe_predict: feat must be 16-byte aligned"); return -1; }
+    ProbeArgs a;
+    a.feat = p->feat; a.index = p->index_or_null; a.rows = (long)p->rows; a.row0 = (long)p->first_row;
+    a.W = c->params + c->p_head_w; a.bias = c->params + c->p_head_b;
+    a.running_mean = const_cast<float*>(p->running_mean); a.running_var = const_cast<float*>(p->running_var);
+    a.logits = p->logits; a.B = p->count; a.D = c->D; a.C = c->C; a.scale = p->scale;
+    return pevit_launch_probe_predict(a, (hipStream_t)stream);
+}
+
 // tokens (S,N) int64 -> features (S,D) f32                              model.py:1153-1168
 extern "C" int pevit_encode_text(pevit_ctx* c, void* stream, const int64_t* tokens, float* features, int S) {
     if (c && !c->text) { pevit_set_error("encode_text: this is an image context (pevit_ctx_create); text contexts come from pevit_text_create"); return -1; }

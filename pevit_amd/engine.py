@@ -461,6 +461,82 @@ class HipEngine:
         out = (probs,) + ((logits,) if return_logits else ()) + ((feat,) if return_features else ())
         return out if len(out) > 1 else probs
 
+    # ------------------------------------------------------------------ linear probe on cached features (csrc/probe.hip)
+    def _check_cache(self, feats, index=None, labels=None):
+        """What the probe entries read through raw pointers: a contiguous f32 (rows, D) feature matrix, int64 row indices, and
+        labels indexed like the matrix -- int64 (rows,) or f32 (rows, num_classes) -- all on this engine's device.  Returns True for
+        multi-label targets."""
+        D = self.arch.embed_dim
+        if feats.device != self.device or feats.dtype != torch.float32 or not feats.is_contiguous() or feats.dim() != 2 \
+                or feats.shape[1] != D or feats.shape[0] < 1:
+            raise _lib.PevitError(f"cached features must be a contiguous float32 tensor (rows, {D}) on {self.device}; got "
+                                  f"{tuple(feats.shape)} {feats.dtype} on {feats.device}")
+        if index is not None and (index.device != self.device or index.dtype != torch.int64 or not index.is_contiguous()
+                                  or index.dim() != 1):
+            raise _lib.PevitError(f"index must be a contiguous int64 vector on {self.device}; got {tuple(index.shape)} {index.dtype} "
+                                  f"on {index.device}")
+        if labels is None:
+            return None
+        return self._check_labels(labels, feats.shape[0])
+
+    def probe_step(self, feats, index, labels, lr=0.0, momentum=0.9, weight_decay=0.0, nesterov=False, bn_training=True,
+                   scale=1.0, update=True, logits_out=None, loss_out=None):
+        """One training step of the linear probe on CACHED feature rows, two launches (``pevit_probe_step``): gather
+        ``feats[index]``, BatchNorm1d, ``scale * Linear``, mean cross-entropy over ``labels[index]`` (int64 (rows,)) or BCE with
+        logits over ``labels[index]`` (f32 (rows, C)), the head's gradients into ``self.grads`` and -- with ``update`` -- torch's
+        SGD on the head.  ``update=False`` leaves parameters and momentum alone for ``optimizer_step(plan)``.  Only on a
+        ``"none"`` engine.  Returns (logits, loss) as device tensors without synchronising."""
+        self.dp_flush()
+        # the matrix and its labels are the same tensors step after step: they are checked once, the index list every time
+        # (keyed on everything _check_cache looks at: another tensor the allocator puts at the same address is checked again)
+        seen = tuple((t.data_ptr(), tuple(t.shape), t.stride(), t.dtype, t.device) for t in (feats, labels))
+        a = getattr(self, "_probe_args", None)
+        if a is None or self._probe_seen != seen:
+            bce = self._check_cache(feats, None, labels)
+            a = self._probe_args = _lib.PevitProbeArgs()
+            a.feat, a.rows = feats.data_ptr(), feats.shape[0]
+            a.labels, a.targets = (None, labels.data_ptr()) if bce else (labels.data_ptr(), None)
+            a.running_mean, a.running_var = self.running_mean.data_ptr(), self.running_var.data_ptr()
+            self._probe_seen = seen
+        if index.dtype != torch.int64 or index.device != self.device or index.dim() != 1 or not index.is_contiguous():
+            raise _lib.PevitError(f"index must be a contiguous int64 vector on {self.device}; got {tuple(index.shape)} {index.dtype} "
+                                  f"on {index.device}")
+        B = index.shape[0]
+        if update and self._optim_kind not in (None, "sgd"):
+            raise _lib.PevitError(f"probe_step: the optimizer state belongs to {self._optim_kind!r}; call reset_optimizer() first")
+        if not 2 <= B <= self.max_batch:
+            raise _lib.PevitError(f"probe_step: batch {B} outside [2, {self.max_batch}] (max_batch of the bound workspace)")
+        logits = self._logits[:B] if logits_out is None else self._out_buf(logits_out, (B, self.num_classes))
+        loss = self._loss if loss_out is None else self._out_buf(loss_out, (1,))
+        a.index, a.logits, a.loss = index.data_ptr(), logits.data_ptr(), loss.data_ptr()
+        a.batch, a.bn_training, a.update = B, int(bn_training), int(update)
+        a.flags = int(self._steps == 0) | (2 if nesterov else 0)
+        a.scale, a.lr, a.momentum, a.weight_decay = float(scale), float(lr), float(momentum), float(weight_decay)
+        _lib.check(self.lib.pevit_probe_step(self._ctx, _lib.stream_ptr(), C.byref(a)), "pevit_probe_step")
+        if update:
+            self._steps += 1
+        return logits, loss
+
+    def probe_predict(self, feats, index=None, first_row=0, count=None, scale=1.0, logits_out=None):
+        """``scale * Linear(BatchNorm1d_eval(rows))`` over cached feature rows in ONE launch for any number of rows
+        (``pevit_probe_predict``): ``feats[index]``, or ``feats[first_row:first_row + count]`` without an index.  A row's bits do
+        not depend on the other rows of the call.  Parameters and running statistics are only read; no synchronise."""
+        self.dp_flush()
+        self._check_cache(feats, index)
+        n = index.shape[0] if index is not None else (feats.shape[0] - first_row if count is None else count)
+        if logits_out is None:
+            logits = torch.empty((n, self.num_classes), dtype=torch.float32, device=self.device)
+        else:
+            logits = self._out_buf(logits_out, (n, self.num_classes))
+        a = _lib.PevitProbePredictArgs()
+        a.feat, a.rows = feats.data_ptr(), feats.shape[0]
+        a.index_or_null = None if index is None else index.data_ptr()
+        a.first_row, a.count = int(first_row), int(n)
+        a.running_mean, a.running_var = self.running_mean.data_ptr(), self.running_var.data_ptr()
+        a.scale, a.logits = float(scale), logits.data_ptr()
+        _lib.check(self.lib.pevit_probe_predict(self._ctx, _lib.stream_ptr(), C.byref(a)), "pevit_probe_predict")
+        return logits
+
     def visual_backward(self, dfeat: torch.Tensor):
         self.dp_flush()
         B = dfeat.shape[0]

@@ -42,7 +42,8 @@ from .metric import get_metric
 
 MULTILABEL_DATASETS = {"voc-2007-classification", "chestx-ray8"}
 
-_LOADERS = {"kadaptation": "load", "lora": "lora_load", "adapter": "adapter_load", "compacter": "compacter_load"}
+_LOADERS = {"kadaptation": "load", "lora": "lora_load", "adapter": "adapter_load", "compacter": "compacter_load",
+            "none": "plain_load"}          # the frozen tower of the linear probe (full_model_finetune.py)
 
 
 def trainable_by_name(method: str, name: str) -> bool:
@@ -815,7 +816,10 @@ def validate(val_loader, model, criterion, epoch, config, return_logits=False):
     return (metric_result, logits) if return_logits else metric_result
 
 
-def train_task(classifier_cls, train_dataloader, test_dataloader, config, sweep_run=False):
+def train_task(classifier_cls, train_dataloader, test_dataloader, config, sweep_run=False, train_one_fn=None, validate_fn=None):
+    """``train_one_fn`` / ``validate_fn``: a module's own epoch and validation loops (the linear probe's cached route), with this
+    module's signatures; by default the loops above."""
+    train_one_fn, validate_fn = train_one_fn or train_one, validate_fn or validate
     best_acc1 = 0
     with ordered_section():                                   # adapter / head initialisation draws from the process-wide generator
         model = classifier_cls(config, 0)
@@ -844,8 +848,8 @@ def train_task(classifier_cls, train_dataloader, test_dataloader, config, sweep_
     for epoch in range(config.TRAIN.BEGIN_EPOCH, config.TRAIN.END_EPOCH):
         adjust_learning_rate(optimizer, epoch, config)
         if not config.TRAIN.EMULATE_ZERO_SHOT:
-            train_one(train_dataloader, model, criterion, optimizer, epoch, config)
-        acc1, logits = validate(test_dataloader, model, criterion, epoch, config, return_logits=True)
+            train_one_fn(train_dataloader, model, criterion, optimizer, epoch, config)
+        acc1, logits = validate_fn(test_dataloader, model, criterion, epoch, config, return_logits=True)
         if acc1 > best_acc1:
             model_info["best_logits"] = logits
         best_acc1 = max(acc1, best_acc1)

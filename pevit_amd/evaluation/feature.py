@@ -98,11 +98,14 @@ def _image_engine(config, model, loader):
     return eng
 
 
-def _engine_features(eng, loader):
-    feats, labels = [], []
+def _engine_feature_chunks(eng, loader):
+    """(features (n, D) on the engine's device, labels as the loader yields them) per batch of ``loader``; no synchronise."""
     for x, y in loader:
-        feats.append(eng.encode_image(x.to(eng.device, non_blocking=True)))
-        labels.append(y)
+        yield eng.encode_image(x.to(eng.device, non_blocking=True)), y
+
+
+def _engine_features(eng, loader):
+    feats, labels = zip(*_engine_feature_chunks(eng, loader))
     return torch.cat(feats).cpu().numpy(), torch.cat(labels).cpu().numpy()
 
 
