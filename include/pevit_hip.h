@@ -487,6 +487,55 @@ int pevit_op_adapter_fwd_ex(void* stream, const pevit_adapter_fwd_args* args);
 int pevit_op_adapter_bwd_ex(void* stream, const pevit_adapter_bwd_args* args);
 int pevit_op_adapter_blocks(int T);         /* workgroups (= blocks of `partial`) of the fused backward */
 int pevit_op_adapter_fused_ok(int E);       /* 1: the fused launches take this width */
+/* Test-only forms of the attention-site low-rank adapter launches (lowrank.hip; tests/test_gpu_lowrank.py): the members of the
+ * launchers' parameter structs, by name, from one flat argument struct each (zero-initialised = nothing set).  They add no kernel.
+ *   pevit_op_lowrank_ex:    form = enum pevit_lowrank_form.  LOWRANK_U: dqkv [T][ld] bf16 (q | k | v gradients in row layout), qT
+ *             [64][E] bf16 -> u32 [T][64] f32 and its bf16 copy at u_bf16_cols (row pitch ld).  LOWRANK_GRAD: xn [T][ldx] bf16, u32,
+ *             dqkv, t [T][64] f32 -> partial [chunks][4][E][32], dbias_partial [chunks][2][E]; chunks = pevit_op_lowrank_chunks(B * N);
+ *             xcd_order = the XCD-contiguous workgroup order.  LOWRANK_COMBO: u and dQ / d bias of this layer (this_layer) and the
+ *             deferred dP = xn_prev^T u32_prev -> partial_prev (prev) in one launch.  LOWRANK_U_F32 / LOWRANK_GRAD_F32: the f32
+ *             verification kernels; dqkv, u_bf16_cols and xn then hold f32 (ld, ldx in floats) and lowrank_u reads q32 [E][64].
+ *   pevit_op_prep_lowrank:  the panels of `layers` layers from the f32 parameters.  method PEVIT_KADAPTATION: rule1_l .. rule2_r
+ *             [32][32], q_left / q_right [32][E / 32] per layer; PEVIT_LORA: a1q, a1v [r][E], a2q, a2v [E][r] per layer.  Panels
+ *             (kernels.h AdapterPanels): w_aug_rows [64][ldw], wT_aug_cols [E][ldwT] (64 columns written), qT [64][E], q16 [E][64]
+ *             in bf16 (f32 = 1: in f32, q16 not written), q32 [E][64] f32.  Layer l reads its parameters param_floats * l floats
+ *             and writes its panels arena_bytes * l bytes behind layer 0's.
+ *   pevit_op_chain_lowrank: the reduce of the per-chunk partials and the chain rule onto the flat gradient buffer, as the backward
+ *             walk fills ChainKadaptArgs / ChainLoraArgs (partial_layer, dbias_layer in floats; p_layer0 = first float of the first
+ *             layer's parameters in params / grads, p_layer_stride floats between layers; params[0:4096] = the four rule factors).
+ *             PEVIT_LORA takes no dbias_partial, rule_scratch or params.
+ *   pevit_op_rule_sum:      grads[0:4096] += rule_scratch[l][0:4096] for l = l_hi - 1 .. l_lo
+ *   pevit_op_lowrank_plan:  out = {es, nu, n12, n0, chunks} of the launch on the current device: 64-column slabs per gradient
+ *             workgroup, u blocks, dQ blocks, dP blocks, 256-row chunks.  this_layer / prev as LOWRANK_COMBO takes them; both 0:
+ *             the plan of LOWRANK_GRAD (nu = 0).  Returns -1 for a width the launchers refuse. */
+enum pevit_lowrank_form {
+    PEVIT_LOWRANK_U = 0, PEVIT_LOWRANK_GRAD = 1, PEVIT_LOWRANK_COMBO = 2, PEVIT_LOWRANK_U_F32 = 3, PEVIT_LOWRANK_GRAD_F32 = 4
+};
+typedef struct pevit_lowrank_args {
+    const void* dqkv; const void* qT; const float* q32; float* u32; void* u_bf16_cols;
+    const void* xn; const float* t; float* partial; float* dbias_partial;
+    const void* xn_prev; const float* u32_prev; float* partial_prev;
+    int32_t form, ld, ldx, chunks, B, H, N, E, xcd_order, this_layer, prev;
+} pevit_lowrank_args;
+typedef struct pevit_prep_lowrank_args {
+    const float* rule1_l; const float* rule1_r; const float* rule2_l; const float* rule2_r; const float* q_left; const float* q_right;
+    const float* a1q; const float* a2q; const float* a1v; const float* a2v;
+    void* w_aug_rows; void* wT_aug_cols; float* q32; void* qT; void* q16;
+    size_t arena_bytes, param_floats;
+    int32_t method, layers, E, r, f32, ldw, ldwT;
+    float ascale;
+} pevit_prep_lowrank_args;
+typedef struct pevit_chain_lowrank_args {
+    const float* partial; const float* dbias_partial; float* G; float* rule_scratch; const float* params; float* grads;
+    size_t partial_layer, dbias_layer, p_layer0, p_layer_stride;
+    int32_t method, chunks, layers, E, r;
+    float ascale;
+} pevit_chain_lowrank_args;
+int pevit_op_lowrank_ex(void* stream, const pevit_lowrank_args* args);
+int pevit_op_prep_lowrank(void* stream, const pevit_prep_lowrank_args* args);
+int pevit_op_chain_lowrank(void* stream, const pevit_chain_lowrank_args* args);
+int pevit_op_rule_sum(void* stream, const float* rule_scratch, float* grads, int l_lo, int l_hi);
+int pevit_op_lowrank_plan(int B, int N, int E, int this_layer, int prev, int32_t out[5]);
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
  * stamps at their phase boundaries (NULL switches it off) */
 int pevit_debug_timeline(void* buf);

@@ -67,6 +67,31 @@ class PevitAdapterBwdArgs(C.Structure):
                 [(n, C.c_int32) for n in ("act_kind", "T", "E", "tn_blocks")])
 
 
+LOWRANK_FORMS = {"u": 0, "grad": 1, "combo": 2, "u_f32": 3, "grad_f32": 4}       # enum pevit_lowrank_form
+
+
+class PevitLowrankArgs(C.Structure):
+    """pevit_lowrank_args of include/pevit_hip.h (the test-only pevit_op_lowrank_ex); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("dqkv", "qT", "q32", "u32", "u_bf16_cols", "xn", "t", "partial", "dbias_partial", "xn_prev",
+                                         "u32_prev", "partial_prev")] +
+                [(n, C.c_int32) for n in ("form", "ld", "ldx", "chunks", "B", "H", "N", "E", "xcd_order", "this_layer", "prev")])
+
+
+class PevitPrepLowrankArgs(C.Structure):
+    """pevit_prep_lowrank_args of include/pevit_hip.h (the test-only pevit_op_prep_lowrank); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("rule1_l", "rule1_r", "rule2_l", "rule2_r", "q_left", "q_right", "a1q", "a2q", "a1v", "a2v",
+                                         "w_aug_rows", "wT_aug_cols", "q32", "qT", "q16")] +
+                [(n, c_size_t) for n in ("arena_bytes", "param_floats")] +
+                [(n, C.c_int32) for n in ("method", "layers", "E", "r", "f32", "ldw", "ldwT")] + [("ascale", c_float)])
+
+
+class PevitChainLowrankArgs(C.Structure):
+    """pevit_chain_lowrank_args of include/pevit_hip.h (the test-only pevit_op_chain_lowrank); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("partial", "dbias_partial", "G", "rule_scratch", "params", "grads")] +
+                [(n, c_size_t) for n in ("partial_layer", "dbias_layer", "p_layer0", "p_layer_stride")] +
+                [(n, C.c_int32) for n in ("method", "chunks", "layers", "E", "r")] + [("ascale", c_float)])
+
+
 class PevitOptimGroup(C.Structure):
     """pevit_optim_group of include/pevit_hip.h: one parameter group of pevit_optim_step (doubles: Python's scalars unrounded)"""
     _fields_ = [(n, C.c_double) for n in ("lr", "weight_decay", "momentum", "beta1", "beta2", "eps")] + [("nesterov", C.c_int)]
@@ -184,6 +209,11 @@ SIGNATURES = {
     "pevit_op_adapter_bwd_ex": (c_int, [P, C.POINTER(PevitAdapterBwdArgs)]),
     "pevit_op_adapter_blocks": (c_int, [c_int]),
     "pevit_op_adapter_fused_ok": (c_int, [c_int]),
+    "pevit_op_lowrank_ex": (c_int, [P, C.POINTER(PevitLowrankArgs)]),
+    "pevit_op_prep_lowrank": (c_int, [P, C.POINTER(PevitPrepLowrankArgs)]),
+    "pevit_op_chain_lowrank": (c_int, [P, C.POINTER(PevitChainLowrankArgs)]),
+    "pevit_op_rule_sum": (c_int, [P, P, P, c_int, c_int]),
+    "pevit_op_lowrank_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, C.POINTER(C.c_int32)]),
     "pevit_debug_timeline": (c_int, [P]),
     "pevit_debug_occupy": (c_int, [P, c_int, c_int, C.c_double]),
     "pevit_op_lowrank_u": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int]),

@@ -209,6 +209,10 @@ int pevit_launch_lowrank_u(const LowrankArgs& a, hipStream_t s);
 int pevit_launch_lowrank_grad(const LowrankArgs& a, hipStream_t s);
 int pevit_lowrank_chunks(int T);
 int pevit_launch_lowrank_combo(const LowrankArgs& a, hipStream_t s);
+// what the two gradient launchers launch for B * N rows on the current device: es 64-column slabs per gradient workgroup (0: none
+// for this width), nu u blocks, n12 dQ blocks, n0 dP blocks, chunks of 256 rows.  combo = 0: lowrank_grad (this_layer, prev ignored)
+struct LowrankPlan { int es = 0, nu = 0, n12 = 0, n0 = 0, chunks = 0; };
+LowrankPlan pevit_lowrank_plan(int B, int N, int E, int combo, int this_layer, int prev);
 // reduce the per-chunk partials of all layers and apply the chain rule onto the reference's
 // parameter tensors (flat gradient buffer, accumulating)
 struct ChainKadaptArgs {

@@ -723,16 +723,29 @@ static int lg_pick_es(int E, int chunks, int kinds, int other_blocks) {
     return best;
 }
 
+// The block ranges of a gradient launch over T = B * N rows.  combo: lowrank_combo with its (this_layer, prev) ranges; otherwise
+// lowrank_grad, the three kinds in one range (n12 + n0 blocks) and no u blocks.  es = 0: no slab grouping for this width.
+LowrankPlan pevit_lowrank_plan(int B, int N, int E, int combo, int this_layer, int prev) {
+    LowrankPlan p;
+    const int T = B * N;
+    p.chunks = ceil_div(T, LG_ROWS);
+    if (!combo) this_layer = prev = 1;
+    p.nu = combo && this_layer ? ceil_div(T, 16 * LC_URG) : 0;
+    p.es = lg_pick_es(E, p.chunks, (this_layer ? 2 : 0) + (prev ? 1 : 0), p.nu);
+    if (!p.es) return p;
+    const int groups = E / 64 / p.es;
+    p.n12 = this_layer ? p.chunks * groups * 2 : 0;
+    p.n0 = prev ? p.chunks * groups : 0;
+    return p;
+}
+
 // see lowrank_combo_kernel.  this_layer = 0: only the deferred dP of the previous layer (end of the layer loop); prev = 0: no deferred work.
 int pevit_launch_lowrank_combo(const LowrankArgs& a, hipStream_t s) {
-    const int this_layer = a.this_layer, prev = a.prev, B = a.B, H = a.H, N = a.N, E = a.E;
-    const int T = B * N, chunks = ceil_div(T, LG_ROWS);
+    const int B = a.B, H = a.H, N = a.N, E = a.E;
     if (E % 64) { pevit_set_error("lowrank_combo: width %d must be a multiple of 64", E); return -1; }
-    const int nu = this_layer ? ceil_div(T, 16 * LC_URG) : 0;
-    const int es = lg_pick_es(E, chunks, (this_layer ? 2 : 0) + (prev ? 1 : 0), nu);
+    const LowrankPlan pl = pevit_lowrank_plan(B, N, E, 1, a.this_layer, a.prev);
+    const int nu = pl.nu, es = pl.es, n12 = pl.n12, n0 = pl.n0;
     if (!es) { pevit_set_error("lowrank_combo: no slab grouping for width %d", E); return -1; }
-    const int groups = E / 64 / es;
-    const int n12 = this_layer ? chunks * groups * 2 : 0, n0 = prev ? chunks * groups : 0;
     const int nu_pad = (nu + 7) & ~7, n12_pad = (n12 + 7) & ~7, n0_pad = (n0 + 7) & ~7;
     if (nu_pad + n12_pad + n0_pad == 0) return 0;
 #define LC_GO(HC, NC) hipLaunchKernelGGL((lowrank_combo_kernel<HC, NC>), dim3(nu_pad + n12_pad + n0_pad), dim3(256), 0, s, a.dqkv, a.ld, a.qT, a.u32, a.u_bf16_cols, a.t, a.partial, \
@@ -752,9 +765,10 @@ int pevit_launch_lowrank_grad(const LowrankArgs& a, hipStream_t s) {
     const int T = a.B * a.N;
     if (chunks != ceil_div(T, LG_ROWS)) { pevit_set_error("lowrank_grad: chunks mismatch"); return -1; }
     if (E % 64) { pevit_set_error("lowrank_grad: width %d must be a multiple of 64", E); return -1; }
-    const int es = lg_pick_es(E, chunks, 3, 0);
+    const LowrankPlan pl = pevit_lowrank_plan(a.B, a.N, E, 0, 1, 1);
+    const int es = pl.es;
     if (!es) { pevit_set_error("lowrank_grad: no slab grouping for width %d", E); return -1; }
-    hipLaunchKernelGGL(lowrank_grad_kernel, dim3(chunks * (E / 64 / es) * 3), dim3(256), 0, s, a.xn, a.ldx, a.u32, a.dqkv, a.ld, a.t,
+    hipLaunchKernelGGL(lowrank_grad_kernel, dim3(pl.n12 + pl.n0), dim3(256), 0, s, a.xn, a.ldx, a.u32, a.dqkv, a.ld, a.t,
                        a.partial, a.dbias_partial, a.B, a.H, a.N, E, a.xcd_order, es);
     LAUNCH_OK("lowrank_grad_kernel");
     return 0;

@@ -458,5 +458,77 @@ extern "C" int pevit_op_adapter_bwd_ex(void* stream, const pevit_adapter_bwd_arg
     p.tn_blocks = a->tn_blocks;
     return pevit_launch_adapter_bwd(p, (hipStream_t)stream);
 }
+// The attention-site low-rank adapter launches (lowrank.hip and its f32 twins above; tests/test_gpu_lowrank.py): every member of
+// LowrankArgs, PrepKadaptArgs / PrepLoraArgs and ChainKadaptArgs / ChainLoraArgs by name.
+extern "C" int pevit_op_lowrank_ex(void* stream, const pevit_lowrank_args* a) {
+    if (!a) { pevit_set_error("lowrank_ex: null argument struct"); return -1; }
+    LowrankArgs p;
+    p.dqkv = (const bf16*)a->dqkv; p.ld = a->ld; p.qT = (const bf16*)a->qT; p.q32 = a->q32; p.u32 = a->u32; p.u_bf16_cols = (bf16*)a->u_bf16_cols;
+    p.xn = (const bf16*)a->xn; p.ldx = a->ldx; p.t = a->t; p.partial = a->partial; p.dbias_partial = a->dbias_partial; p.chunks = a->chunks;
+    p.B = a->B; p.H = a->H; p.N = a->N; p.E = a->E; p.xcd_order = a->xcd_order; p.this_layer = a->this_layer; p.prev = a->prev;
+    p.xn_prev = (const bf16*)a->xn_prev; p.u32_prev = a->u32_prev; p.partial_prev = a->partial_prev;
+    if (p.B < 1 || p.N < 1 || p.H < 1) { pevit_set_error("lowrank_ex: B=%d H=%d N=%d", p.B, p.H, p.N); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    switch (a->form) {
+        case PEVIT_LOWRANK_U: return pevit_launch_lowrank_u(p, s);
+        case PEVIT_LOWRANK_GRAD: return pevit_launch_lowrank_grad(p, s);
+        case PEVIT_LOWRANK_COMBO: return pevit_launch_lowrank_combo(p, s);
+        case PEVIT_LOWRANK_U_F32: return pevit_launch_lowrank_u_f32(p, s);
+        case PEVIT_LOWRANK_GRAD_F32: return pevit_launch_lowrank_grad_f32(p, s);
+    }
+    pevit_set_error("lowrank_ex: unknown form %d", a->form);
+    return -1;
+}
+extern "C" int pevit_op_prep_lowrank(void* stream, const pevit_prep_lowrank_args* a) {
+    if (!a) { pevit_set_error("prep_lowrank: null argument struct"); return -1; }
+    AdapterPanels pan;
+    pan.w_aug_rows = (bf16*)a->w_aug_rows; pan.ldw = a->ldw; pan.wT_aug_cols = (bf16*)a->wT_aug_cols; pan.ldwT = a->ldwT;
+    pan.q32 = a->q32; pan.qT = (bf16*)a->qT; pan.q16 = (bf16*)a->q16;
+    LayerStrides st;
+    st.arena_bytes = a->arena_bytes; st.param_floats = a->param_floats;
+    if (a->method == PEVIT_KADAPTATION) {
+        PrepKadaptArgs p;
+        p.rule1_l = a->rule1_l; p.rule1_r = a->rule1_r; p.rule2_l = a->rule2_l; p.rule2_r = a->rule2_r; p.q_left = a->q_left; p.q_right = a->q_right;
+        p.pan = pan; p.E = a->E; p.ascale = a->ascale; p.layers = a->layers; p.st = st; p.f32 = a->f32;
+        return pevit_launch_prep_kadapt(p, (hipStream_t)stream);
+    }
+    if (a->method == PEVIT_LORA) {
+        PrepLoraArgs p;
+        p.a1q = a->a1q; p.a2q = a->a2q; p.a1v = a->a1v; p.a2v = a->a2v; p.r = a->r;
+        p.pan = pan; p.E = a->E; p.ascale = a->ascale; p.layers = a->layers; p.st = st; p.f32 = a->f32;
+        return pevit_launch_prep_lora(p, (hipStream_t)stream);
+    }
+    pevit_set_error("prep_lowrank: method %d has no attention-site panels", a->method);
+    return -1;
+}
+extern "C" int pevit_op_chain_lowrank(void* stream, const pevit_chain_lowrank_args* a) {
+    if (!a) { pevit_set_error("chain_lowrank: null argument struct"); return -1; }
+    if (a->method == PEVIT_KADAPTATION) {
+        ChainKadaptArgs p;
+        p.partial = a->partial; p.partial_layer = a->partial_layer; p.dbias_partial = a->dbias_partial; p.dbias_layer = a->dbias_layer;
+        p.chunks = a->chunks; p.ascale = a->ascale; p.layers = a->layers; p.G = a->G; p.rule_scratch = a->rule_scratch;
+        p.params = a->params; p.grads = a->grads; p.p_layer0 = a->p_layer0; p.p_layer_stride = a->p_layer_stride; p.E = a->E;
+        return pevit_launch_chain_kadapt(p, (hipStream_t)stream);
+    }
+    if (a->method == PEVIT_LORA) {
+        ChainLoraArgs p;
+        p.partial = a->partial; p.partial_layer = a->partial_layer; p.chunks = a->chunks; p.ascale = a->ascale; p.r = a->r; p.layers = a->layers;
+        p.G = a->G; p.grads = a->grads; p.p_layer0 = a->p_layer0; p.p_layer_stride = a->p_layer_stride; p.E = a->E;
+        return pevit_launch_chain_lora(p, (hipStream_t)stream);
+    }
+    pevit_set_error("chain_lowrank: method %d has no attention-site chain rule", a->method);
+    return -1;
+}
+extern "C" int pevit_op_rule_sum(void* stream, const float* rule_scratch, float* grads, int l_lo, int l_hi) {
+    return pevit_launch_rule_sum(rule_scratch, grads, l_lo, l_hi, (hipStream_t)stream);
+}
+extern "C" int pevit_op_lowrank_plan(int B, int N, int E, int this_layer, int prev, int32_t out[5]) {
+    if (!out || B < 1 || N < 1 || E < 64 || E % 64) { pevit_set_error("lowrank_plan: B=%d N=%d E=%d", B, N, E); return -1; }
+    const int combo = this_layer || prev;
+    const LowrankPlan p = pevit_lowrank_plan(B, N, E, combo, this_layer, prev);
+    if (!p.es) { pevit_set_error("lowrank_plan: no slab grouping for width %d", E); return -1; }
+    out[0] = p.es; out[1] = p.nu; out[2] = p.n12; out[3] = p.n0; out[4] = p.chunks;
+    return 0;
+}
 extern "C" int pevit_op_adapter_blocks(int T) { return pevit_adapter_blocks(T); }
 extern "C" int pevit_op_adapter_fused_ok(int E) { return pevit_adapter_fused_ok(E) ? 1 : 0; }
