@@ -536,6 +536,40 @@ int pevit_op_prep_lowrank(void* stream, const pevit_prep_lowrank_args* args);
 int pevit_op_chain_lowrank(void* stream, const pevit_chain_lowrank_args* args);
 int pevit_op_rule_sum(void* stream, const float* rule_scratch, float* grads, int l_lo, int l_hi);
 int pevit_op_lowrank_plan(int B, int N, int E, int this_layer, int prev, int32_t out[5]);
+/* Test-only forms of the classifier head and of the small exact kernels around it (stem_head.hip, misc.hip, text.hip;
+ * tests/test_gpu_head.py, tests/test_gpu_movers.py).  They add no kernel.
+ *   pevit_op_head_ex: every member of the head launcher's parameter struct by name (zero-initialised = nothing set); all scratch is
+ *             the caller's.  feat [B][D], W [C][D], bias [C] (or NULL), running_mean / running_var [D], ybn [B][D], rstd [D],
+ *             logits [B][C], dlogits [B][C], dybn [B][D], loss [1], all f32.  labels [B] int64 -> cross entropy (ignore_index -100);
+ *             targets [B][C] f32 -> BCE with logits; both NULL -> forward only (nothing behind logits is touched).  gW [C][D] and
+ *             gb [C] ACCUMULATE (gW NULL: neither is written); dfeat [B][D] f32 (NULL: no backward through the BatchNorm, and
+ *             dybn[0:B] keeps the cross-entropy row losses); dfeat_bf16 [B][D]: the bf16 copy of dfeat, or NULL.
+ *             Refused here, before any launch: a NULL struct, B / D / C < 1, labels and targets both set, training with B < 2, a
+ *             missing feat / W / running_mean / running_var / ybn / rstd / logits, a loss without dlogits / dybn / loss.
+ *   the movers: the launchers' arguments as they stand (their own refusals apply).  f32 = 1: the bf16-declared output holds f32
+ *             (the storage of the f32 verification mode).  pevit_op_im2col_ex: u8 = 1 -> uint8 pixels with mean3 / std3 (host
+ *             pointers), u8 = 0 -> f32 pixels. */
+typedef struct pevit_head_args {
+    const float* feat; const int64_t* labels; const float* targets; const float* W; const float* bias; float* gW; float* gb;
+    float* running_mean; float* running_var; float* ybn; float* rstd; float* logits; float* dlogits; float* dybn;
+    float* loss; float* dfeat; void* dfeat_bf16;
+    int32_t training, B, D, Cc;
+} pevit_head_args;
+int pevit_op_head_ex(void* stream, const pevit_head_args* args);
+int pevit_op_conv_weight(void* stream, const float* w, void* out, int E, int K, int Kpad, int f32);
+int pevit_op_cls_row(void* stream, const float* cls, const float* pos, float* x, int B, int N, int E);
+int pevit_op_im2col_ex(void* stream, const void* images, int u8, const float* mean3, const float* std3, void* patches, int B, int R,
+                       int P, int Kpad, int f32);
+int pevit_op_cast_ex(void* stream, const float* src, void* dst, size_t n, float scale, int f32);
+/* dst[c*ldd + r] = src[r*cols + c] * (r < scaled_rows ? scale : 1) */
+int pevit_op_transpose(void* stream, const float* src, int rows, int cols, void* dst, int ldd, int scaled_rows, float scale, int f32);
+/* to_internal: dst[(b*N+n)*E + e] = src[(n*B+b)*E + e]; else the inverse */
+int pevit_op_permute_rows(void* stream, const float* src, float* dst, int N, int B, int E, int to_internal);
+int pevit_op_zero(void* stream, void* ptr, size_t bytes);
+int pevit_op_scale_f32(void* stream, float* p, size_t n, float scale);
+/* x[s*N + n][:] = table[clamp(tokens[s][n], 0, V-1)][:] + pos[n][:] ; rows_out[s][:] = x[s*N + argmax_n tokens[s][n]][:] (first maximum) */
+int pevit_op_text_embed(void* stream, const int64_t* tokens, const float* table, const float* pos, float* x, int S, int N, int E, int V);
+int pevit_op_text_eot_gather(void* stream, const int64_t* tokens, const float* x, float* rows_out, int S, int N, int E);
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
  * stamps at their phase boundaries (NULL switches it off) */
 int pevit_debug_timeline(void* buf);

@@ -92,6 +92,13 @@ class PevitChainLowrankArgs(C.Structure):
                 [(n, C.c_int32) for n in ("method", "chunks", "layers", "E", "r")] + [("ascale", c_float)])
 
 
+class PevitHeadArgs(C.Structure):
+    """pevit_head_args of include/pevit_hip.h (the test-only pevit_op_head_ex); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("feat", "labels", "targets", "W", "bias", "gW", "gb", "running_mean", "running_var", "ybn",
+                                         "rstd", "logits", "dlogits", "dybn", "loss", "dfeat", "dfeat_bf16")] +
+                [(n, C.c_int32) for n in ("training", "B", "D", "Cc")])
+
+
 class PevitOptimGroup(C.Structure):
     """pevit_optim_group of include/pevit_hip.h: one parameter group of pevit_optim_step (doubles: Python's scalars unrounded)"""
     _fields_ = [(n, C.c_double) for n in ("lr", "weight_decay", "momentum", "beta1", "beta2", "eps")] + [("nesterov", C.c_int)]
@@ -214,6 +221,17 @@ SIGNATURES = {
     "pevit_op_chain_lowrank": (c_int, [P, C.POINTER(PevitChainLowrankArgs)]),
     "pevit_op_rule_sum": (c_int, [P, P, P, c_int, c_int]),
     "pevit_op_lowrank_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, C.POINTER(C.c_int32)]),
+    "pevit_op_head_ex": (c_int, [P, C.POINTER(PevitHeadArgs)]),
+    "pevit_op_conv_weight": (c_int, [P, P, P, c_int, c_int, c_int, c_int]),
+    "pevit_op_cls_row": (c_int, [P, P, P, P, c_int, c_int, c_int]),
+    "pevit_op_im2col_ex": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int]),
+    "pevit_op_cast_ex": (c_int, [P, P, P, c_size_t, c_float, c_int]),
+    "pevit_op_transpose": (c_int, [P, P, c_int, c_int, P, c_int, c_int, c_float, c_int]),
+    "pevit_op_permute_rows": (c_int, [P, P, P, c_int, c_int, c_int, c_int]),
+    "pevit_op_zero": (c_int, [P, P, c_size_t]),
+    "pevit_op_scale_f32": (c_int, [P, P, c_size_t, c_float]),
+    "pevit_op_text_embed": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int]),
+    "pevit_op_text_eot_gather": (c_int, [P, P, P, P, c_int, c_int, c_int]),
     "pevit_debug_timeline": (c_int, [P]),
     "pevit_debug_occupy": (c_int, [P, c_int, c_int, C.c_double]),
     "pevit_op_lowrank_u": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int]),

@@ -530,5 +530,64 @@ extern "C" int pevit_op_lowrank_plan(int B, int N, int E, int this_layer, int pr
     out[0] = p.es; out[1] = p.nu; out[2] = p.n12; out[3] = p.n0; out[4] = p.chunks;
     return 0;
 }
+// The classifier head (stem_head.hip; tests/test_gpu_head.py): every member of HeadArgs by name, all scratch the caller's.  What the
+// engine's own callers guarantee by construction is refused here, before the first launch.
+extern "C" int pevit_op_head_ex(void* stream, const pevit_head_args* a) {
+    if (!a) { pevit_set_error("head_ex: null argument struct"); return -1; }
+    if (a->B < 1 || a->D < 1 || a->Cc < 1) { pevit_set_error("head_ex: B=%d D=%d C=%d", a->B, a->D, a->Cc); return -1; }
+    if (a->labels && a->targets) { pevit_set_error("head_ex: labels and targets are both set"); return -1; }
+    if (a->training && a->B < 2) { pevit_set_error("head_ex: training-mode BatchNorm needs B >= 2 (B=%d)", a->B); return -1; }
+    if (!a->feat || !a->W || !a->running_mean || !a->running_var || !a->ybn || !a->rstd || !a->logits) {
+        pevit_set_error("head_ex: feat, W, running_mean, running_var, ybn, rstd and logits are required"); return -1;
+    }
+    if ((a->labels || a->targets) && (!a->dlogits || !a->dybn || !a->loss)) {
+        pevit_set_error("head_ex: a loss needs dlogits, dybn and loss"); return -1;
+    }
+    HeadArgs p;
+    p.feat = a->feat; p.labels = a->labels; p.targets = a->targets; p.W = a->W; p.bias = a->bias; p.gW = a->gW; p.gb = a->gb;
+    p.running_mean = a->running_mean; p.running_var = a->running_var; p.training = a->training;
+    p.ybn = a->ybn; p.rstd = a->rstd; p.logits = a->logits; p.dlogits = a->dlogits; p.dybn = a->dybn; p.loss = a->loss;
+    p.dfeat = a->dfeat; p.dfeat_bf16 = (bf16*)a->dfeat_bf16; p.B = a->B; p.D = a->D; p.Cc = a->Cc;
+    return pevit_launch_head(p, (hipStream_t)stream);
+}
+// The small exact kernels around the towers (stem_head.hip, misc.hip, text.hip; tests/test_gpu_movers.py): the launchers' arguments
+// as they stand, the f32 storage flag included.
+extern "C" int pevit_op_conv_weight(void* stream, const float* w, void* out, int E, int K, int Kpad, int f32) {
+    return pevit_launch_conv_weight(w, (bf16*)out, E, K, Kpad, (hipStream_t)stream, f32);
+}
+extern "C" int pevit_op_cls_row(void* stream, const float* cls, const float* pos, float* x, int B, int N, int E) {
+    return pevit_launch_cls_row(cls, pos, x, B, N, E, (hipStream_t)stream);
+}
+extern "C" int pevit_op_im2col_ex(void* stream, const void* images, int u8, const float* mean3, const float* std3, void* patches, int B,
+                                  int R, int P, int Kpad, int f32) {
+    if (!u8) return pevit_launch_im2col((const float*)images, (bf16*)patches, B, R, P, Kpad, (hipStream_t)stream, f32);
+    Im2colU8Args a;
+    a.img = (const unsigned char*)images; a.mean3 = mean3; a.std3 = std3; a.out = (bf16*)patches; a.B = B; a.R = R; a.P = P; a.Kp = Kpad;
+    a.f32 = f32;
+    return pevit_launch_im2col_u8(a, (hipStream_t)stream);
+}
+extern "C" int pevit_op_cast_ex(void* stream, const float* src, void* dst, size_t n, float scale, int f32) {
+    return pevit_launch_cast_bf16(src, (bf16*)dst, n, scale, (hipStream_t)stream, f32);
+}
+extern "C" int pevit_op_transpose(void* stream, const float* src, int rows, int cols, void* dst, int ldd, int scaled_rows, float scale,
+                                  int f32) {
+    return pevit_launch_transpose_bf16(src, rows, cols, (bf16*)dst, ldd, scaled_rows, scale, (hipStream_t)stream, f32);
+}
+extern "C" int pevit_op_permute_rows(void* stream, const float* src, float* dst, int N, int B, int E, int to_internal) {
+    return pevit_launch_permute_rows(src, dst, N, B, E, to_internal, (hipStream_t)stream);
+}
+extern "C" int pevit_op_zero(void* stream, void* ptr, size_t bytes) { return pevit_launch_zero(ptr, bytes, (hipStream_t)stream); }
+extern "C" int pevit_op_scale_f32(void* stream, float* p, size_t n, float scale) {
+    return pevit_launch_scale_f32(p, n, scale, (hipStream_t)stream);
+}
+extern "C" int pevit_op_text_embed(void* stream, const int64_t* tokens, const float* table, const float* pos, float* x, int S, int N,
+                                   int E, int V) {
+    TextEmbedArgs a;
+    a.tokens = tokens; a.table = table; a.pos = pos; a.x = x; a.S = S; a.N = N; a.E = E; a.V = V;
+    return pevit_launch_text_embed(a, (hipStream_t)stream);
+}
+extern "C" int pevit_op_text_eot_gather(void* stream, const int64_t* tokens, const float* x, float* rows_out, int S, int N, int E) {
+    return pevit_launch_text_eot_gather(tokens, x, rows_out, S, N, E, (hipStream_t)stream);
+}
 extern "C" int pevit_op_adapter_blocks(int T) { return pevit_adapter_blocks(T); }
 extern "C" int pevit_op_adapter_fused_ok(int E) { return pevit_adapter_fused_ok(E) ? 1 : 0; }
