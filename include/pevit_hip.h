@@ -207,6 +207,31 @@ int pevit_visual_forward_u8(pevit_ctx* ctx, void* stream, const uint8_t* images,
 int pevit_train_forward_backward_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const int64_t* labels,
                                     float* running_mean, float* running_var, int bn_training, float* logits,
                                     float* loss, int batch);
+/* ---- native-size uint8 images: the reference's Resize(n_px, bicubic) + CenterCrop (clip_load.py:80-87) on the GPU, bit for bit
+ * what Pillow's 8-bit resize gives, so that a dataset of 32 x 32 or 96 x 96 pixels is stored, kept resident and uploaded at its own
+ * size and every _u8 entry above and below is fed from one launch.  Pillow's algorithm is exact integer arithmetic: per axis a table
+ * of taps with 22 fractional bits, a horizontal pass rounded to uint8, a vertical pass over those bytes.  None of the three entries
+ * takes a context; the two planners are host code and run without a GPU.
+ * pevit_resize_geometry: a source of src_h rows and src_w columns and the target n_px -> the resized size (the shorter side becomes
+ * n_px, the other int(n_px * longer / shorter)) and the crop window's first row and column, round((size - n_px) / 2) with halves
+ * to the even neighbour like Python's round.
+ * pevit_resize_axis: rows first .. first + count of the tables of one axis in_size -> out_size.  k (count x ksize) int32 taps, zero past
+ * a row's tap count; bounds (count x 2) int32 = (first source sample, taps).  With k and bounds both null it returns ksize
+ * (2 ceil(2 max(in_size / out_size, 1)) + 1; 1 for in_size == out_size) and writes nothing; otherwise 0.  An axis of equal size is
+ * not resampled (Pillow skips that pass, and a bicubic pass at equal size is not the identity): its rows are the one tap 2^22 at the
+ * sample itself.  The doubles are Pillow's, in Pillow's order, without contraction.
+ * pevit_resize_u8: ONE launch, uint8 (planes x src_h x src_w) -> uint8 (planes x out_h x out_w), planes = 3 B, both dense, from
+ * DEVICE tables kh (out_w x ksize_h), bh (out_w x 2), kv (out_h x ksize_v), bv (out_h x 2).  The centre crop is the window of table
+ * rows handed in (rows left .. left + n_px of the horizontal axis, top .. top + n_px of the vertical one): no discarded pixel is
+ * computed.  The intermediate of the horizontal pass lives in LDS only.  Source bytes are read one by one: no alignment is asked of
+ * src, and nothing past its last pixel is touched.  Table contents are clamped on the device, so a wrong table gives wrong pixels
+ * and never an access outside the buffers.  Limits, refused before any launch: 1 <= src_h, src_w <= 4096; 1 <= out_h, out_w <= 256;
+ * 1 <= ksize_h, ksize_v <= 33 (a downscale of at most 8x); planes >= 1; no null pointer.  A plane's bytes do not depend on the other
+ * planes of the launch. */
+int pevit_resize_geometry(int src_h, int src_w, int n_px, int* nh, int* nw, int* top, int* left);
+int pevit_resize_axis(int in_size, int out_size, int first, int count, int32_t* k, int32_t* bounds);
+int pevit_resize_u8(void* stream, const uint8_t* src, int planes, int src_h, int src_w, uint8_t* dst, int out_h, int out_w,
+                    const int32_t* kh, const int32_t* bh, int ksize_h, const int32_t* kv, const int32_t* bv, int ksize_v);
 /* ---- evaluation: images (B,3,R,R) -> logits (B x C) in one call.  stem -> blocks -> ln_post -> proj -> BatchNorm1d(affine=False) in
  * EVAL mode on the caller's running statistics -> Linear.  The tower runs its inference forms: the kernels of pevit_visual_forward
  * with every store left out that only a backward pass reads (q' / v', log-sum-exp, the MLP pre-activation, LayerNorm statistics) and

@@ -175,6 +175,9 @@ SIGNATURES = {
     "pevit_set_input_norm": (c_int, [P, P, P]),
     "pevit_visual_forward_u8": (c_int, [P, P, P, P, c_int, c_int]),
     "pevit_train_forward_backward_u8": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
+    "pevit_resize_geometry": (c_int, [c_int, c_int, c_int] + [C.POINTER(c_int)] * 4),
+    "pevit_resize_axis": (c_int, [c_int, c_int, c_int, c_int, P, P]),
+    "pevit_resize_u8": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, P, c_int, P, P, c_int]),
     "pevit_head_forward_backward_bce": (c_int, [P, P, P, P, P, P, c_int, P, P, P, c_int]),
     "pevit_train_forward_backward_bce": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
     "pevit_train_forward_backward_bce_u8": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),

@@ -430,3 +430,18 @@ struct ProbeArgs {
 int pevit_probe_check(int D, int C, const char* who);      // 0, or -1 with the error text set; launches nothing
 int pevit_launch_probe_step(const ProbeArgs& a, hipStream_t s);
 int pevit_launch_probe_predict(const ProbeArgs& a, hipStream_t s);
+
+// ---- resize.hip (Pillow's 8-bit bicubic resize + centre crop of uint8 planes, bit for bit; tables from resize_plan.hip) ----
+// src [planes][src_h][src_w] -> dst [planes][out_h][out_w], both uint8 and dense.  kh [out_w][ksize_h] / kv [out_h][ksize_v]: int32
+// taps with 22 fractional bits; bh [out_w][2] / bv [out_h][2]: (first source sample, taps) per output column / row, all in device
+// memory.  The crop is the choice of table rows.  1 <= src_h, src_w <= 4096, out_h, out_w <= 256, ksize_h, ksize_v <= 33:
+// pevit_resize_check refuses the rest.  Table contents are clamped on the device: a wrong table gives wrong pixels, never an
+// access outside src, dst or the tables.
+struct ResizeArgs {
+    const uint8_t* src = nullptr; uint8_t* dst = nullptr;
+    const int32_t* kh = nullptr; const int32_t* bh = nullptr; const int32_t* kv = nullptr; const int32_t* bv = nullptr;
+    int planes = 0, src_h = 0, src_w = 0, out_h = 0, out_w = 0, ksize_h = 0, ksize_v = 0;
+    int lds_rows = 0, ldw = 0;       // set by the launcher: rows and row pitch of the intermediate in LDS
+};
+int pevit_resize_check(const ResizeArgs& a);          // 0, or -1 with the error text set; launches nothing
+int pevit_launch_resize_u8(ResizeArgs a, hipStream_t s);

@@ -179,6 +179,9 @@ class HipEngine:
         _lib.check(self.lib.pevit_bind(self._ctx, _lib.ptr(self.arena), self.arena.numel(), _lib.ptr(self.workspace),
                                        self.workspace.numel(), batch), "pevit_bind")
         self._logits = torch.empty((batch, self.num_classes), dtype=torch.float32, device=self.device)
+        if getattr(self, "_resize_buf", None) is not None:         # the staging of resize_u8 follows the batch bound
+            self._resize_buf = None
+            self._resize_buf = self._resize_staging(batch)
         self.max_batch = batch
 
     # ------------------------------------------------------------------ parameters
@@ -252,6 +255,73 @@ class HipEngine:
         m = (C.c_float * 3)(*[float(v) for v in mean]); sd = (C.c_float * 3)(*[float(v) for v in std])
         _lib.check(self.lib.pevit_set_input_norm(self._ctx, m, sd), "pevit_set_input_norm")
         self._input_norm = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
+
+    # ---- native-size uint8 batches: the reference's Resize(n_px, bicubic) + CenterCrop in one launch (csrc/resize.hip) ----------
+    def set_input_resize(self, on: bool = True):
+        """With ``on``, every method that takes uint8 pixels also takes contiguous uint8 (B,3,h,w) of ONE other size per batch --
+        the native size of the dataset -- and runs the reference's ``Resize(R, bicubic) + CenterCrop(R)`` (clip_load._Preprocess)
+        on the GPU first, bit for bit what Pillow gives (``resize_u8``); the resized batch then takes the unchanged uint8 path.
+        Off by default: a uint8 batch of another size than (R,R) is refused.  f32 batches of another size, and uint8 batches before
+        ``set_input_normalization``, are refused either way."""
+        self._input_resize = bool(on)
+
+    def _resize_staging(self, batch):
+        R = self.arch.resolution
+        return torch.empty((batch, 3, R, R), dtype=torch.uint8, device=self.device)
+
+    def _resize_tables(self, h, w):
+        """Device tables of the (h, w) -> (R, R) resize + crop, planned by the library and uploaded once per source size."""
+        cache = self.__dict__.setdefault("_resize_cache", {})
+        if (h, w) not in cache:
+            R = self.arch.resolution
+            nh, nw, top, left = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            _lib.check(self.lib.pevit_resize_geometry(h, w, R, C.byref(nh), C.byref(nw), C.byref(top), C.byref(left)),
+                       "pevit_resize_geometry")
+            out = []
+            for in_size, out_size, first in ((w, nw.value, left.value), (h, nh.value, top.value)):
+                ks = self.lib.pevit_resize_axis(in_size, out_size, 0, 0, None, None)
+                if ks < 1:
+                    _lib.check(-1, "pevit_resize_axis")
+                if ks > 33 or in_size > 4096 or R > 256:
+                    raise _lib.PevitError(f"resize_u8: a {h} x {w} source for a {R} x {R} tower is outside what the kernel takes "
+                                          f"(sides up to 4096, a downscale of at most 8x, targets up to 256)")
+                k = torch.empty((R, ks), dtype=torch.int32)
+                b = torch.empty((R, 2), dtype=torch.int32)
+                _lib.check(self.lib.pevit_resize_axis(in_size, out_size, first, R, C.c_void_p(k.data_ptr()), C.c_void_p(b.data_ptr())),
+                           "pevit_resize_axis")
+                out += [k.to(self.device), b.to(self.device), ks]
+            cache[(h, w)] = tuple(out)
+        return cache[(h, w)]
+
+    def resize_u8(self, images: torch.Tensor) -> torch.Tensor:
+        """uint8 (B,3,h,w) -> uint8 (B,3,R,R): Pillow's bicubic resize of the shorter side to R and the centre crop, in ONE launch
+        (``pevit_resize_u8``), bit for bit ``preprocess.resize_center_crop_u8``.  The result is a view of an engine-owned staging
+        tensor (``max_batch`` images) that the next call overwrites; no synchronise."""
+        if images.device != self.device or images.dtype != torch.uint8 or not images.is_contiguous() or images.dim() != 4 \
+                or images.shape[1] != 3 or images.shape[0] < 1:
+            raise _lib.PevitError(f"resize_u8: images must be a contiguous uint8 tensor (B,3,h,w) on {self.device}; got "
+                                  f"{tuple(images.shape)} {images.dtype} on {images.device}")
+        B, _, h, w = images.shape
+        if B > self.max_batch:
+            raise _lib.PevitError(f"batch {B} exceeds the bound workspace ({self.max_batch}): call ensure_batch")
+        kh, bh, ksh, kv, bv, ksv = self._resize_tables(int(h), int(w))
+        if getattr(self, "_resize_buf", None) is None:
+            self._resize_buf = self._resize_staging(self.max_batch)
+        out = self._resize_buf[:B]
+        R = self.arch.resolution
+        _lib.check(self.lib.pevit_resize_u8(_lib.stream_ptr(), _lib.ptr(images), 3 * B, h, w, _lib.ptr(out), R, R, _lib.ptr(kh),
+                                            _lib.ptr(bh), ksh, _lib.ptr(kv), _lib.ptr(bv), ksv), "pevit_resize_u8")
+        return out
+
+    def _needs_resize(self, images) -> bool:
+        R = self.arch.resolution
+        return bool(getattr(self, "_input_resize", False)) and getattr(self, "_input_norm", None) is not None \
+            and images.dtype == torch.uint8 and images.dim() == 4 and tuple(images.shape[2:]) != (R, R)
+
+    def _input(self, images):
+        """The ONE place a native-size uint8 batch becomes (B,3,R,R): every uint8-taking method passes its images through here
+        and then through its unchanged checks and its unchanged ``_u8`` entry.  Anything else comes back as it is."""
+        return self.resize_u8(images) if self._needs_resize(images) else images
 
     def _check_batch(self, images, labels=None):
         """The C ABI takes raw pointers: reject anything that is not what it will read (f32 NCHW images -- or uint8 pixels once
@@ -378,7 +448,7 @@ class HipEngine:
     def visual_forward(self, images: torch.Tensor, save: bool = True) -> torch.Tensor:
         self.dp_flush()
         B = images.shape[0]
-        img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
+        img = self._input(images.contiguous()) if images.dtype == torch.uint8 else images.contiguous().float()
         self._check_batch(img)
         self.forward_generation += 1
         for l in range(self.arch.layers):
@@ -397,7 +467,7 @@ class HipEngine:
         forward it invalidates the activations a pending backward would read."""
         self.dp_flush()                # a pipelined DP step may still owe the parameter update
         B = images.shape[0]
-        img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
+        img = self._input(images.contiguous()) if images.dtype == torch.uint8 else images.contiguous().float()
         self._check_batch(img)
         self.forward_generation += 1
         for l in range(self.arch.layers):
@@ -416,7 +486,7 @@ class HipEngine:
         """What ``predict`` does before its engine call: flush a pipelined DP step, check the batch, bump the generations (the
         walk overwrites the activations a pending backward would read)."""
         self.dp_flush()
-        img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
+        img = self._input(images.contiguous()) if images.dtype == torch.uint8 else images.contiguous().float()
         self._check_batch(img)
         self.forward_generation += 1
         for l in range(self.arch.layers):
@@ -570,6 +640,7 @@ class HipEngine:
         caller-owned f32 destinations (an epoch buffer of the harness) instead of the engine's per-step buffers, which the
         next step overwrites."""
         B = images.shape[0]
+        images = self._input(images)
         bce = self._check_batch(images, labels)
         self.forward_generation += 1
         logits = self._logits[:B] if logits_out is None else self._out_buf(logits_out, (B, self.num_classes))
@@ -851,6 +922,9 @@ class HipEngine:
         # recorded OUTSIDE the capture (and the gated zero_grads path) into the graph
         self.dp_pipeline_off()
         B = images.shape[0]
+        if self._needs_resize(images):
+            raise _lib.PevitError("capture_train_step: the batch needs the input resize, which is not part of the captured step: "
+                                  "capture on resize_u8(images) copied to a buffer of your own")
         fn = self._train_fn(images, self._check_batch(images, labels))
         flags = 2 if nesterov else 0
         logits, loss = self._logits[:B], self._loss
@@ -957,6 +1031,7 @@ class HipEngine:
             raise ValueError(f"forward_backward_dp: unknown mode {mode!r}")
         import torch.distributed as dist
         B = images.shape[0]
+        images = self._input(images)
         self._check_batch(images, labels)
         if not getattr(self, "_dp_streamk_off", False):
             # the RCCL kernels of the overlapped all-reduce share the CUs with the second half of the backward: stream-K's

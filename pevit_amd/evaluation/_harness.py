@@ -352,6 +352,7 @@ class ClassifierBase(nn.Module):
             visual.weight_format = str(wf)
         if hasattr(config, "INPUT") and getattr(config.INPUT, "MEAN", None) is not None:
             visual.set_input_normalization(config.INPUT.MEAN, config.INPUT.STD)      # uint8 batches: ToTensor + Normalize in the engine
+            visual.set_input_resize(True)                                            # ... and Resize + CenterCrop for native-size ones
         visual._num_classes = output_dim
         visual._max_batch = max(int(config.TRAIN.BATCH_SIZE_PER_GPU), int(config.TEST.BATCH_SIZE_PER_GPU))
         if visual._engine is not None and (visual._engine.num_classes != output_dim or
@@ -497,7 +498,9 @@ class ClassifierBase(nn.Module):
             if images.device != visual.class_embedding.device:
                 return False
             if images.dtype == torch.uint8:
-                return getattr(visual, "_input_norm", None) is not None
+                R = visual.input_resolution                 # native-size pixels: resized in the engine (visual.set_input_resize)
+                sized = images.dim() == 4 and (tuple(images.shape[2:]) == (R, R) or getattr(visual, "_input_resize", False))
+                return sized and getattr(visual, "_input_norm", None) is not None
             return images.dtype == torch.float32
         return True
 

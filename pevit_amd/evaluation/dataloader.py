@@ -9,7 +9,9 @@ dataset so that ``merge_trainval_loader`` can put them back together for the fin
 
 Sources: ``<DATASET.ROOT>/<DATASET.DATASET>.npz`` holding already preprocessed tensors
 (``train_images``, ``train_labels``, ``test_images``, ``test_labels``; images float32 (N,3,R,R) or uint8, in
-which case INPUT.MEAN / INPUT.STD are applied; labels (N,) class indices, or (N, C) multi-hot with C > 1 -- bool, integer
+which case INPUT.MEAN / INPUT.STD are applied -- uint8 images may also have their native size (N,3,h,w), and are then resized
+and centre-cropped like the reference's transform, by the engine per batch or with ``DATASET.RESIZE_ON_HOST`` at load time; labels
+(N,) class indices, or (N, C) multi-hot with C > 1 -- bool, integer
 or float -- which become float32 targets for BCEWithLogitsLoss), or ``DATASET.DATASET == 'synthetic'`` (seeded random tensors,
 for smoke runs and benchmarks).
 """
@@ -165,12 +167,29 @@ def few_shot_subset(labels: np.ndarray, shots: int, seed: int):
     return np.sort(np.concatenate(keep))
 
 
+def _target_size(config):
+    return int(config.TRAIN.get("IMAGE_SIZE", [224, 224])[0])
+
+
 def _tensors(images, labels, config):
     """uint8 archives stay uint8: the Classifier hands INPUT.MEAN / INPUT.STD to the engine, which applies the reference's
     ToTensor + Normalize inside its patch gather (bit for bit the host arithmetic; a quarter of the memory and of the bytes to
-    upload).  DATASET.NORMALIZE_ON_HOST = True restores the float path."""
+    upload).  DATASET.NORMALIZE_ON_HOST = True restores the float path.
+    uint8 archives at their NATIVE size (32 x 32, 96 x 96, 37 x 53, ...: one size per archive) stay as they are too: the engine runs
+    the reference's Resize(n_px, bicubic) + CenterCrop per batch (HipEngine.set_input_resize), bit for bit Pillow's result.
+    DATASET.RESIZE_ON_HOST = True resizes at load time instead, with the same integer arithmetic on the host
+    (pevit_amd/preprocess.py); NORMALIZE_ON_HOST on such an archive resizes first when TRAIN.IMAGE_SIZE states the target."""
     x = torch.as_tensor(np.asarray(images))
     if x.dtype == torch.uint8:
+        n = _target_size(config)
+        native = x.dim() == 4 and tuple(x.shape[2:]) != (n, n)
+        # NORMALIZE_ON_HOST is older than the resize and has always normalised whatever size the archive holds: it resizes first only
+        # where the configuration states the tower's size (TRAIN.IMAGE_SIZE), RESIZE_ON_HOST always (224 without the key)
+        on_host = config.DATASET.get("RESIZE_ON_HOST", False) or \
+            (config.DATASET.get("NORMALIZE_ON_HOST", False) and config.TRAIN.get("IMAGE_SIZE", None) is not None)
+        if native and on_host:
+            from ..preprocess import resize_center_crop_u8
+            x = resize_center_crop_u8(x.contiguous(), n)
         if config.DATASET.get("NORMALIZE_ON_HOST", False):
             mean = torch.tensor(config.INPUT.MEAN).view(1, 3, 1, 1)
             std = torch.tensor(config.INPUT.STD).view(1, 3, 1, 1)
@@ -191,7 +210,12 @@ def _synthetic(config):
     out = []
     for n in sizes:
         if config.DATASET.get("SYNTHETIC_UINT8", False):      # raw pixels, as an image archive would hold them
-            out.append((torch.randint(0, 256, (n, 3, R, R), generator=g, dtype=torch.uint8), torch.arange(n) % C))
+            h, w = config.DATASET.get("SYNTHETIC_SOURCE_SIZE", None) or (R, R)      # ... at a native size: resized like an archive's
+            x = torch.randint(0, 256, (n, 3, int(h), int(w)), generator=g, dtype=torch.uint8)
+            if (int(h), int(w)) != (R, R) and config.DATASET.get("RESIZE_ON_HOST", False):
+                from ..preprocess import resize_center_crop_u8
+                x = resize_center_crop_u8(x, R)
+            out.append((x, torch.arange(n) % C))
         else:
             out.append((torch.randn((n, 3, R, R), generator=g), torch.arange(n) % C))
     return out

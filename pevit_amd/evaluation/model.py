@@ -452,6 +452,7 @@ class VisionTransformer(nn.Module):
             off += k
         if getattr(self, "_input_norm", None) is not None:
             eng.set_input_normalization(*self._input_norm)
+        eng.set_input_resize(getattr(self, "_input_resize", False))
         self._engine = eng
         return eng
 
@@ -486,6 +487,13 @@ class VisionTransformer(nn.Module):
         self._input_norm = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
         if self._engine is not None:
             self._engine.set_input_normalization(*self._input_norm)
+
+    def set_input_resize(self, on: bool = True):
+        """uint8 batches (B,3,h,w) at the dataset's native size are accepted too: the reference's Resize(R, bicubic) + CenterCrop
+        then runs in the engine, bit for bit Pillow's result (HipEngine.set_input_resize).  Needs ``set_input_normalization``."""
+        self._input_resize = bool(on)
+        if self._engine is not None:
+            self._engine.set_input_resize(self._input_resize)
 
     def forward(self, x):
         eng = self.engine()
