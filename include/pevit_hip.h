@@ -232,6 +232,38 @@ int pevit_resize_geometry(int src_h, int src_w, int n_px, int* nh, int* nw, int*
 int pevit_resize_axis(int in_size, int out_size, int first, int count, int32_t* k, int32_t* bounds);
 int pevit_resize_u8(void* stream, const uint8_t* src, int planes, int src_h, int src_w, uint8_t* dst, int out_h, int out_w,
                     const int32_t* kh, const int32_t* bh, int ksize_h, const int32_t* kv, const int32_t* bv, int ksize_v);
+/* ---- ragged sets: every image its own size (Caltech-101, Pets, Flowers-102, ...), resized in ONE launch per batch.  The set is a
+ * pool of dense (3, h_i, w_i) uint8 blocks that follow one another; one descriptor per image names its block and its tables; the
+ * tables of all images live in two pools, one pair of out rows per distinct axis (in_size, out_size, first), planned by
+ * pevit_resize_axis.  Centre crop or squash to out x out (DATASET.CENTER_CROP False) is only the choice of tables.
+ * pevit_resize_ragged_desc: offset = byte offset of the block in the pool; h, w; kh_off / kv_off = element offsets into k_pool of the
+ * axis' (out x ksize) int32 taps; bh_off / bv_off = element offsets into b_pool of its (out x 2) int32 bounds; ksize_h / ksize_v.
+ * pevit_resize_ragged_check: host only, no GPU -- validates n_images HOST descriptors before they are uploaded: offset + 3 h w inside
+ * the pool, sides in [1, 4096], ksize in [1, 33], table ranges inside the pools, out in [1, 256]; -1 with a message naming the first
+ * image and what is wrong with it.
+ * pevit_resize_ragged_u8: ONE launch; dst (batch x 3 x out x out) uint8, dense; output image b is image index[b] of the set (device
+ * int64; null: image b).  All pointers but the struct itself are device memory.  max_ksize_v: the largest ksize_v of desc (it sizes
+ * the LDS).  Every index the kernel forms is clamped -- image index, block, sides, ksize, table ranges, table contents, LDS rows --
+ * so a wrong descriptor gives wrong pixels, never an access outside a buffer.  Refused before any launch: a null pointer (index
+ * excepted), batch < 1, n_images < 1, out outside [1, 256], max_ksize_v outside [1, 33], pools smaller than one 1 x 1 image and one
+ * one-tap table.  An image's bytes do not depend on the other images of the launch, and equal pevit_resize_u8's for the same tables. */
+typedef struct pevit_resize_ragged_desc {
+    int64_t offset;
+    int32_t h, w;
+    int32_t kh_off, bh_off, ksize_h;
+    int32_t kv_off, bv_off, ksize_v;
+} pevit_resize_ragged_desc;                        /* 40 bytes */
+typedef struct pevit_resize_ragged_args {
+    const uint8_t* pool; int64_t pool_bytes;
+    const pevit_resize_ragged_desc* desc;
+    const int32_t* k_pool; int64_t k_len;          /* lengths in int32 elements */
+    const int32_t* b_pool; int64_t b_len;
+    const int64_t* index; uint8_t* dst;
+    int32_t n_images, batch, out, max_ksize_v;
+} pevit_resize_ragged_args;
+int pevit_resize_ragged_check(const pevit_resize_ragged_desc* host_desc, int n_images, int64_t pool_bytes, int64_t k_len,
+                              int64_t b_len, int out);
+int pevit_resize_ragged_u8(void* stream, const pevit_resize_ragged_args* args);
 /* ---- evaluation: images (B,3,R,R) -> logits (B x C) in one call.  stem -> blocks -> ln_post -> proj -> BatchNorm1d(affine=False) in
  * EVAL mode on the caller's running statistics -> Linear.  The tower runs its inference forms: the kernels of pevit_visual_forward
  * with every store left out that only a backward pass reads (q' / v', log-sum-exp, the MLP pre-activation, LayerNorm statistics) and

@@ -118,6 +118,18 @@ class PevitProbePredictArgs(C.Structure):
                 ("running_mean", c_void_p), ("running_var", c_void_p), ("scale", C.c_float), ("logits", c_void_p)]
 
 
+class PevitResizeRaggedDesc(C.Structure):
+    """pevit_resize_ragged_desc of include/pevit_hip.h: one image of a ragged set (40 bytes; preprocess.RAGGED_DESC is its numpy twin)"""
+    _fields_ = [("offset", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "kh_off", "bh_off", "ksize_h", "kv_off", "bv_off", "ksize_v")]
+
+
+class PevitResizeRaggedArgs(C.Structure):
+    """pevit_resize_ragged_args of include/pevit_hip.h (pevit_resize_ragged_u8); zero-initialised = nothing set"""
+    _fields_ = [("pool", c_void_p), ("pool_bytes", C.c_int64), ("desc", c_void_p), ("k_pool", c_void_p), ("k_len", C.c_int64),
+                ("b_pool", c_void_p), ("b_len", C.c_int64), ("index", c_void_p), ("dst", c_void_p)] + \
+               [(n, C.c_int32) for n in ("n_images", "batch", "out", "max_ksize_v")]
+
+
 OPTIM_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}           # enum pevit_optim_kind
 OPTIM_MAX_GROUPS = 8                                       # PEVIT_OPTIM_MAX_GROUPS
 OPTIM_NO_GRAD = 255                                        # group_of value of an element whose parameter has .grad None
@@ -178,6 +190,8 @@ SIGNATURES = {
     "pevit_resize_geometry": (c_int, [c_int, c_int, c_int] + [C.POINTER(c_int)] * 4),
     "pevit_resize_axis": (c_int, [c_int, c_int, c_int, c_int, P, P]),
     "pevit_resize_u8": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, P, c_int, P, P, c_int]),
+    "pevit_resize_ragged_check": (c_int, [P, c_int, C.c_int64, C.c_int64, C.c_int64, c_int]),
+    "pevit_resize_ragged_u8": (c_int, [P, C.POINTER(PevitResizeRaggedArgs)]),
     "pevit_head_forward_backward_bce": (c_int, [P, P, P, P, P, P, c_int, P, P, P, c_int]),
     "pevit_train_forward_backward_bce": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),
     "pevit_train_forward_backward_bce_u8": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int]),

@@ -445,3 +445,18 @@ struct ResizeArgs {
 };
 int pevit_resize_check(const ResizeArgs& a);          // 0, or -1 with the error text set; launches nothing
 int pevit_launch_resize_u8(ResizeArgs a, hipStream_t s);
+
+// ---- resize_ragged.hip (the same resize with the geometry per image: a pool of (3, h_i, w_i) blocks -> dense [batch][3][out][out]) ----
+// pool: the images' bytes, one block after the other; desc [n_images]: per image of the set its block's byte offset, h, w and, per
+// axis, the element offsets of its table rows in k_pool (int32 taps, out x ksize) and b_pool (int32 (first, taps), out x 2) and its
+// ksize (pevit_resize_ragged_desc, include/pevit_hip.h).  Output image b is image index[b] (b itself when index is null).
+// max_ksize_v: the largest ksize_v of desc, which sizes the LDS.  All pointers are device memory.  Every index is clamped on the device.
+struct pevit_resize_ragged_desc;
+struct ResizeRaggedArgs {
+    const uint8_t* pool = nullptr; const pevit_resize_ragged_desc* desc = nullptr;
+    const int32_t* k_pool = nullptr; const int32_t* b_pool = nullptr; const int64_t* index = nullptr; uint8_t* dst = nullptr;
+    long long pool_bytes = 0, k_len = 0, b_len = 0;
+    int n_images = 0, batch = 0, out = 0, max_ksize_v = 0;
+    int lds_rows = 0, ldw = 0;       // set by the launcher: rows and row pitch of the intermediate in LDS
+};
+int pevit_launch_resize_ragged_u8(ResizeRaggedArgs a, hipStream_t s);     // 0, or -1 with the error text set before any launch

@@ -352,7 +352,8 @@ class ClassifierBase(nn.Module):
             visual.weight_format = str(wf)
         if hasattr(config, "INPUT") and getattr(config.INPUT, "MEAN", None) is not None:
             visual.set_input_normalization(config.INPUT.MEAN, config.INPUT.STD)      # uint8 batches: ToTensor + Normalize in the engine
-            visual.set_input_resize(True)                                            # ... and Resize + CenterCrop for native-size ones
+            # ... and Resize + CenterCrop for native-size and ragged ones (DATASET.CENTER_CROP False: Resize((R, R)), no crop)
+            visual.set_input_resize(True, bool(config.DATASET.get("CENTER_CROP", True)))
         visual._num_classes = output_dim
         visual._max_batch = max(int(config.TRAIN.BATCH_SIZE_PER_GPU), int(config.TEST.BATCH_SIZE_PER_GPU))
         if visual._engine is not None and (visual._engine.num_classes != output_dim or

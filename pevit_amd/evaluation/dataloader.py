@@ -12,11 +12,14 @@ Sources: ``<DATASET.ROOT>/<DATASET.DATASET>.npz`` holding already preprocessed t
 which case INPUT.MEAN / INPUT.STD are applied -- uint8 images may also have their native size (N,3,h,w), and are then resized
 and centre-cropped like the reference's transform, by the engine per batch or with ``DATASET.RESIZE_ON_HOST`` at load time; labels
 (N,) class indices, or (N, C) multi-hot with C > 1 -- bool, integer
-or float -- which become float32 targets for BCEWithLogitsLoss), or ``DATASET.DATASET == 'synthetic'`` (seeded random tensors,
+or float -- which become float32 targets for BCEWithLogitsLoss; a RAGGED archive -- every image its own size -- holds
+``*_images`` as ONE 1-D uint8 pool of dense (3, h_i, w_i) blocks and ``*_shapes`` (N, 2) = (h, w), see ``_ragged_tensors``), or
+``DATASET.DATASET == 'synthetic'`` (seeded random tensors,
 for smoke runs and benchmarks).
 """
 from __future__ import annotations
 
+import logging
 import math
 import os
 
@@ -175,7 +178,8 @@ def _tensors(images, labels, config):
     """uint8 archives stay uint8: the Classifier hands INPUT.MEAN / INPUT.STD to the engine, which applies the reference's
     ToTensor + Normalize inside its patch gather (bit for bit the host arithmetic; a quarter of the memory and of the bytes to
     upload).  DATASET.NORMALIZE_ON_HOST = True restores the float path.
-    uint8 archives at their NATIVE size (32 x 32, 96 x 96, 37 x 53, ...: one size per archive) stay as they are too: the engine runs
+    uint8 archives at their NATIVE size (32 x 32, 96 x 96, 37 x 53, ...: one size per archive; ``_ragged_tensors`` takes the archives
+    with one size per image) stay as they are too: the engine runs
     the reference's Resize(n_px, bicubic) + CenterCrop per batch (HipEngine.set_input_resize), bit for bit Pillow's result.
     DATASET.RESIZE_ON_HOST = True resizes at load time instead, with the same integer arithmetic on the host
     (pevit_amd/preprocess.py); NORMALIZE_ON_HOST on such an archive resizes first when TRAIN.IMAGE_SIZE states the target."""
@@ -188,18 +192,78 @@ def _tensors(images, labels, config):
         on_host = config.DATASET.get("RESIZE_ON_HOST", False) or \
             (config.DATASET.get("NORMALIZE_ON_HOST", False) and config.TRAIN.get("IMAGE_SIZE", None) is not None)
         if native and on_host:
-            from ..preprocess import resize_center_crop_u8
-            x = resize_center_crop_u8(x.contiguous(), n)
+            if config.DATASET.get("CENTER_CROP", True):
+                from ..preprocess import resize_center_crop_u8
+                x = resize_center_crop_u8(x.contiguous(), n)
+            else:                                            # DATASET.CENTER_CROP False: Resize((n, n)), nothing cropped
+                from ..preprocess import resize_u8
+                x = resize_u8(x.contiguous(), n, center_crop=False)
         if config.DATASET.get("NORMALIZE_ON_HOST", False):
             mean = torch.tensor(config.INPUT.MEAN).view(1, 3, 1, 1)
             std = torch.tensor(config.INPUT.STD).view(1, 3, 1, 1)
             x = (x.float() / 255.0 - mean) / std
     else:
         x = x.float()
+    return x.contiguous(), _labels(labels)
+
+
+def _labels(labels):
     y = np.asarray(labels)
     if y.ndim == 2 and y.shape[1] > 1:                       # multi-hot (N, C): float32 targets of BCEWithLogitsLoss
-        return x.contiguous(), torch.as_tensor(y.astype(np.float32)).contiguous()
-    return x.contiguous(), torch.as_tensor(y).long()
+        return torch.as_tensor(y.astype(np.float32)).contiguous()
+    return torch.as_tensor(y).long()
+
+
+RAGGED_TABLE_BYTES = 256 << 20       # default of DATASET.RAGGED_TABLE_BYTES: a cap on the table pools of one split, not a tuned value
+_LOGGED = set()
+
+
+def _ragged_stays(config, dev):
+    """A ragged set stays ragged only where the engine resizes it: resident on the GPU, and neither RESIZE_ON_HOST nor
+    NORMALIZE_ON_HOST asked for.  (Host-fed ragged upload through the staging ring does not exist.)"""
+    return dev.type != "cpu" and not config.DATASET.get("RESIZE_ON_HOST", False) and not config.DATASET.get("NORMALIZE_ON_HOST", False)
+
+
+def _ragged_tensors(pool, shapes, labels, config, stays):
+    """A ragged archive split: ``pool`` 1-D uint8, image i a dense (3, h_i, w_i) block, the blocks one after the other (offsets: the
+    running sum of 3 h w, int64); ``shapes`` (N, 2) integers (h, w).  Where it ``stays`` ragged it becomes a
+    ``preprocess.RaggedImages`` -- the pool as it is, one descriptor per image, one table pair per distinct axis -- which the engine
+    resizes batch by batch in one launch (csrc/resize_ragged.hip); images outside the kernel's range (a side above 4096, an axis of
+    more than 33 taps) are resized on the host now and stored as n x n blocks.  Otherwise, and when the table pools would exceed
+    DATASET.RAGGED_TABLE_BYTES, every image is resized on the host now (``preprocess.resize_u8``: the same bytes) into the dense
+    (N, 3, n, n) tensor of the uniform route.  DATASET.CENTER_CROP False: Resize((n, n)) instead of Resize(n) + CenterCrop."""
+    from .. import preprocess as pp
+    n, crop = _target_size(config), bool(config.DATASET.get("CENTER_CROP", True))
+    pool, shapes = np.ascontiguousarray(np.asarray(pool)), np.asarray(shapes).astype(np.int64).reshape(-1, 2)
+    if pool.dtype != np.uint8 or pool.ndim != 1:
+        raise RuntimeError(f"a ragged archive holds its images as one 1-D uint8 pool; got {pool.dtype} {pool.shape}")
+    if stays:
+        cap, need = int(config.DATASET.get("RAGGED_TABLE_BYTES", RAGGED_TABLE_BYTES)), pp.ragged_table_bytes(shapes, n, crop)
+        if need > cap:
+            logging.info(f"=> ragged set: its resize tables would take {need} bytes (DATASET.RAGGED_TABLE_BYTES {cap}): resized on the host")
+            stays = False
+    if not stays:
+        return _tensors(pp.resize_ragged_u8(pool, shapes, n, crop), labels, config)
+    images = pp.RaggedImages.build(pool, shapes, n, crop)
+    if images.pre_resized and "pre_resized" not in _LOGGED:
+        _LOGGED.add("pre_resized")
+        logging.info(f"=> ragged set: {images.pre_resized} of {len(images)} images are outside the resize kernel's range (a side above "
+                     f"4096 or a downscale beyond 8x) and were resized on the host at load time")
+    return images, _labels(labels)
+
+
+def _synthetic_ragged(config, stays):
+    """DATASET.SYNTHETIC_RAGGED: seeded random pixels with a seeded size per image, both sides drawn inside
+    DATASET.SYNTHETIC_SOURCE_RANGE (inclusive); takes the route of a ragged archive."""
+    lo, hi = [int(v) for v in config.DATASET.get("SYNTHETIC_SOURCE_RANGE", (24, 72))]
+    C = config.DATASET.NUM_CLASSES
+    g = np.random.default_rng(int(config.DATASET.RANDOM_SEED_SAMPLING))
+    out = []
+    for n in config.DATASET.get("SYNTHETIC_SIZES", (256, 128)):
+        shapes = g.integers(lo, hi + 1, (int(n), 2))
+        pool = g.integers(0, 256, int((3 * shapes[:, 0] * shapes[:, 1]).sum()), dtype=np.uint8)
+        out.append(_ragged_tensors(pool, shapes, np.arange(int(n)) % C, config, stays))
+    return out
 
 
 def _synthetic(config):
@@ -213,8 +277,12 @@ def _synthetic(config):
             h, w = config.DATASET.get("SYNTHETIC_SOURCE_SIZE", None) or (R, R)      # ... at a native size: resized like an archive's
             x = torch.randint(0, 256, (n, 3, int(h), int(w)), generator=g, dtype=torch.uint8)
             if (int(h), int(w)) != (R, R) and config.DATASET.get("RESIZE_ON_HOST", False):
-                from ..preprocess import resize_center_crop_u8
-                x = resize_center_crop_u8(x, R)
+                if config.DATASET.get("CENTER_CROP", True):
+                    from ..preprocess import resize_center_crop_u8
+                    x = resize_center_crop_u8(x, R)
+                else:
+                    from ..preprocess import resize_u8
+                    x = resize_u8(x, R, center_crop=False)
             out.append((x, torch.arange(n) % C))
         else:
             out.append((torch.randn((n, 3, R, R), generator=g), torch.arange(n) % C))
@@ -225,7 +293,11 @@ def construct_dataloader(config, feature_type="image", test_split_only=False):
     if feature_type != "image":
         raise RuntimeError("only image loaders are built here")
     name = config.DATASET.DATASET
-    if name == "synthetic":
+    if name == "synthetic" and config.DATASET.get("SYNTHETIC_RAGGED", False):
+        lo, hi = [int(v) for v in config.DATASET.get("SYNTHETIC_SOURCE_RANGE", (24, 72))]
+        worst = 3 * hi * hi * sum(int(n) for n in config.DATASET.get("SYNTHETIC_SIZES", (256, 128)))
+        (trx, try_), (tex, tey) = _synthetic_ragged(config, _ragged_stays(config, _resident_device(config, worst)))
+    elif name == "synthetic":
         (trx, try_), (tex, tey) = _synthetic(config)
     else:
         path = config.DATASET.ROOT if str(config.DATASET.ROOT).endswith(".npz") else os.path.join(config.DATASET.ROOT, name + ".npz")
@@ -233,8 +305,14 @@ def construct_dataloader(config, feature_type="image", test_split_only=False):
             raise RuntimeError(f"{path} not found: this build reads preprocessed tensor archives; the reference's "
                                "vision_datasets hub / ImageFolder pipeline (feature.py:533-583) is not part of it")
         z = np.load(path)
-        trx, try_ = _tensors(z["train_images"], z["train_labels"], config)
-        tex, tey = _tensors(z["test_images"], z["test_labels"], config)
+        if "train_shapes" in z.files and "test_shapes" in z.files:           # a ragged archive: one size per image
+            train_pool, test_pool = z["train_images"], z["test_images"]
+            stays = _ragged_stays(config, _resident_device(config, train_pool.size + test_pool.size))
+            trx, try_ = _ragged_tensors(train_pool, z["train_shapes"], z["train_labels"], config, stays)
+            tex, tey = _ragged_tensors(test_pool, z["test_shapes"], z["test_labels"], config, stays)
+        else:
+            trx, try_ = _tensors(z["train_images"], z["train_labels"], config)
+            tex, tey = _tensors(z["test_images"], z["test_labels"], config)
     bs = int(config.DATASET.get("LOADER_BATCH_SIZE", 64))    # get_dataloader's batch_size_per_gpu default is 64 (feature.py:101,597)
     dev = _resident_device(config, trx.numel() * trx.element_size() + tex.numel() * tex.element_size())
     tex, tey = tex.to(dev), tey.to(dev)
@@ -245,7 +323,8 @@ def construct_dataloader(config, feature_type="image", test_split_only=False):
     shots = int(config.DATASET.NUM_SAMPLES_PER_CLASS)
     if shots > 0:
         keep = few_shot_subset(labels, shots, int(config.DATASET.RANDOM_SEED_SAMPLING))
-        trx, try_, labels = trx[keep], try_[keep], labels[keep]
+        trx = trx.subset(keep) if hasattr(trx, "subset") else trx[keep]      # (a ragged set is indexed, its pool stays as it is)
+        try_, labels = try_[keep], labels[keep]
     full = _Tensors(trx.to(dev), try_.to(dev))
     train_idx, val_idx = class_balanced_split(labels, 0.2)
     train_loader = TensorLoader(_View(full, train_idx), batch_size=bs, shuffle=True)

@@ -93,7 +93,8 @@ def _image_engine(config, model, loader):
     visual = model.visual
     if getattr(visual, "_input_norm", None) is None and hasattr(config, "INPUT") and getattr(config.INPUT, "MEAN", None) is not None:
         visual.set_input_normalization(config.INPUT.MEAN, config.INPUT.STD)
-        visual.set_input_resize(True)                  # native-size uint8 sets: Resize + CenterCrop in the engine
+        crop = bool(config.DATASET.get("CENTER_CROP", True)) if hasattr(config, "DATASET") and hasattr(config.DATASET, "get") else True
+        visual.set_input_resize(True, crop)            # native-size and ragged uint8 sets: Resize + CenterCrop (or squash) in the engine
     eng = visual.engine()
     eng.ensure_batch(int(loader.batch_size))
     return eng

@@ -452,7 +452,7 @@ class VisionTransformer(nn.Module):
             off += k
         if getattr(self, "_input_norm", None) is not None:
             eng.set_input_normalization(*self._input_norm)
-        eng.set_input_resize(getattr(self, "_input_resize", False))
+        eng.set_input_resize(getattr(self, "_input_resize", False), getattr(self, "_resize_center_crop", True))
         self._engine = eng
         return eng
 
@@ -488,12 +488,14 @@ class VisionTransformer(nn.Module):
         if self._engine is not None:
             self._engine.set_input_normalization(*self._input_norm)
 
-    def set_input_resize(self, on: bool = True):
+    def set_input_resize(self, on: bool = True, center_crop: bool = True):
         """uint8 batches (B,3,h,w) at the dataset's native size are accepted too: the reference's Resize(R, bicubic) + CenterCrop
-        then runs in the engine, bit for bit Pillow's result (HipEngine.set_input_resize).  Needs ``set_input_normalization``."""
-        self._input_resize = bool(on)
+        then runs in the engine, bit for bit Pillow's result (HipEngine.set_input_resize).  Needs ``set_input_normalization``.
+        ``center_crop`` False: Resize((R, R)) without a crop (DATASET.CENTER_CROP False).  Ragged batches
+        (``preprocess.RaggedBatch``: one size per image) are accepted on the same terms."""
+        self._input_resize, self._resize_center_crop = bool(on), bool(center_crop)
         if self._engine is not None:
-            self._engine.set_input_resize(self._input_resize)
+            self._engine.set_input_resize(self._input_resize, self._resize_center_crop)
 
     def forward(self, x):
         eng = self.engine()

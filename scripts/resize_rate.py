@@ -8,9 +8,13 @@
            it: the bytes a host-fed batch uploads and the bytes the image set occupies.
 
 Every leg runs one warm-up, then --rounds timed rounds in alternation; wall clock is taken between synchronises.
+--ragged: the ragged kernel (csrc/resize_ragged.hip: pevit_resize_ragged_u8) instead -- a uniform 32 x 32 set and a uniform 96 x 96
+set of B = 128 images, timed against pevit_resize_u8 on the same pixels in alternation (the ragged kernel adds one descriptor read per
+workgroup and nothing per pixel, so its median should lie inside the dense kernel's own min-max spread), and one mixed-size batch
+(sides drawn in [96, 448], seeded): microseconds, and its bytes against the byte floor.
 --one-pass SIZE: nothing but --iters launches of the kernel at that source size (the process to put under
 rocprofv3 --kernel-trace --stats).
-Prints one JSON object.  usage: python scripts/resize_rate.py [--rounds 3] [--iters 200] [--steps 20] [--one-pass SIZE] [--skip-harness] [--out FILE]"""
+Prints one JSON object.  usage: python scripts/resize_rate.py [--rounds 3] [--iters 200] [--steps 20] [--one-pass SIZE] [--skip-harness] [--ragged] [--out FILE]"""
 import argparse
 import ctypes as C
 import dataclasses
@@ -79,6 +83,62 @@ def kernel_rates(lib, rounds, iters):
     return out
 
 
+class RaggedCase:
+    """a ragged set of B images on the device (preprocess.RaggedImages, tables from the library's planner) and a destination"""
+
+    def __init__(self, lib, shapes, seed):
+        import numpy as np
+        from pevit_amd import _lib
+        from pevit_amd.preprocess import RaggedImages, ragged_offsets
+        self.lib = lib
+        g = np.random.default_rng(seed)
+        pool = g.integers(0, 256, int(ragged_offsets(shapes)[-1]), dtype=np.uint8)
+        self.set = RaggedImages.build(pool, shapes, N_PX, True).to("cuda")
+        self.dst = torch.empty((len(shapes), 3, N_PX, N_PX), dtype=torch.uint8, device="cuda")
+        self.bytes = self.set.pool.numel() + self.dst.numel()
+        r = self.set
+        self.args = _lib.PevitResizeRaggedArgs(
+            pool=_lib.ptr(r.pool), pool_bytes=r.pool.numel(), desc=_lib.ptr(r.desc), k_pool=_lib.ptr(r.k_pool), k_len=r.k_pool.numel(),
+            b_pool=_lib.ptr(r.b_pool), b_len=r.b_pool.numel(), index=None, dst=_lib.ptr(self.dst), n_images=len(r), batch=len(r),
+            out=N_PX, max_ksize_v=r.max_ksize_v)
+
+    def launch(self):
+        from pevit_amd import _lib
+        _lib.check(self.lib.pevit_resize_ragged_u8(_lib.stream_ptr(), C.byref(self.args)), "pevit_resize_ragged_u8")
+
+    us_per_launch = KernelCase.us_per_launch
+
+
+def _spread(us):
+    s = sorted(us)
+    return {"us": us, "median": s[len(s) // 2], "min": s[0], "max": s[-1]}
+
+
+def ragged_rates(lib, rounds, iters):
+    """uniform sets: the ragged kernel against the dense one on the same pixels, in alternation; then one mixed-size batch"""
+    import numpy as np
+    out = {}
+    for size in (32, 96):
+        dense, ragged = KernelCase(lib, size), RaggedCase(lib, [(size, size)] * B, size)
+        ragged.set.pool.copy_(dense.src.reshape(-1))                 # the same pixels
+        dense.launch(); ragged.launch(); sync()
+        assert torch.equal(dense.dst, ragged.dst), "the ragged kernel's bytes differ from the dense kernel's"
+        dense.us_per_launch(20); ragged.us_per_launch(20)            # warm-up
+        d, r = [], []
+        for _ in range(rounds):
+            d.append(round(dense.us_per_launch(iters), 3)); r.append(round(ragged.us_per_launch(iters), 3))
+        out[f"uniform_{size}->224"] = {"dense": _spread(d), "ragged": _spread(r), "bytes": dense.bytes,
+                                        "ragged_median_inside_dense_spread": bool(min(d) <= _spread(r)["median"] <= max(d))}
+    shapes = np.random.default_rng(0).integers(96, 449, (B, 2)).tolist()
+    mixed = RaggedCase(lib, [tuple(s) for s in shapes], 1)
+    mixed.us_per_launch(20)
+    us = [round(mixed.us_per_launch(iters), 3) for _ in range(rounds)]
+    out["mixed_96..448->224"] = dict(_spread(us), bytes=mixed.bytes, floor_us=mixed.bytes / HBM_PEAK * 1e6,
+                                      floor_share=round(mixed.bytes / HBM_PEAK * 1e6 / min(us), 4), max_ksize_v=mixed.set.max_ksize_v,
+                                      table_bytes=mixed.set.table_bytes)
+    return out
+
+
 def harness_rates(rounds, steps, native=32):
     from pevit_amd.config import vitb32_clip_config
     from pevit_amd.evaluation import kadaptation_clip as mod
@@ -130,6 +190,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--one-pass", type=int, default=0)
     ap.add_argument("--skip-harness", action="store_true")
+    ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     from pevit_amd import _lib
@@ -142,8 +203,8 @@ def main():
         sync()
         print(json.dumps({"one_pass": a.one_pass, "launches": a.iters}))
         return
-    res = {"kernel": kernel_rates(lib, a.rounds, a.iters)}
-    if not a.skip_harness:
+    res = {"ragged": ragged_rates(lib, a.rounds, a.iters)} if a.ragged else {"kernel": kernel_rates(lib, a.rounds, a.iters)}
+    if not a.skip_harness and not a.ragged:
         res["harness"] = harness_rates(a.rounds, a.steps)
     text = json.dumps(res, indent=1)
     print(text)
