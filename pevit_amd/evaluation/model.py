@@ -355,6 +355,8 @@ class VisionTransformer(nn.Module):
         self.weight_format = os.environ.get("PEVIT_WEIGHT_FORMAT", "bf16")
         self._engine: HipEngine | None = None
         self._train_params = None
+        self._input_norm = None                # set_input_normalization: (mean, std), handed to every engine built from here
+        self._input_resize, self._resize_center_crop = False, True      # set_input_resize, likewise
         E, L = arch.width, arch.layers
         scale = E ** -0.5
         spec = adapter_param_spec(method, E, L, lora_rank)
@@ -450,9 +452,9 @@ class VisionTransformer(nn.Module):
             k = named[n].numel()
             self._has_grad[n] = bool(mask[off:off + k].any())
             off += k
-        if getattr(self, "_input_norm", None) is not None:
+        if self._input_norm is not None:
             eng.set_input_normalization(*self._input_norm)
-        eng.set_input_resize(getattr(self, "_input_resize", False), getattr(self, "_resize_center_crop", True))
+        eng.set_input_resize(self._input_resize, self._resize_center_crop)
         self._engine = eng
         return eng
 
@@ -503,7 +505,7 @@ class VisionTransformer(nn.Module):
         params = self._trainable_params()
         save = torch.is_grad_enabled() and any(p.requires_grad for p in params)   # grad mode is off inside Function.forward
         if x.dtype == torch.uint8:
-            if getattr(self, "_input_norm", None) is None:
+            if self._input_norm is None:
                 raise _lib.PevitError("uint8 images need the preprocessing constants: call visual.set_input_normalization(mean, std)")
             return _VisualFn.apply(x.contiguous(), self, save, *params)
         return _VisualFn.apply(x.contiguous().float(), self, save, *params)

@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._context import EngineContext
 from .synth import VitArch
 
 TEXT_WEIGHT_FORMATS = ("bf16", "f32-verify")
@@ -54,60 +55,32 @@ def text_tower_parameters(model):
     yield "text_projection", model.text_projection
 
 
-class TextEngine:
+class TextEngine(EngineContext):
     def __init__(self, arch: VitArch, max_prompts: int = 256, device: str | torch.device = "cuda:0", weight_format: str = "bf16"):
-        if not torch.cuda.is_available():
-            raise _lib.PevitError("TextEngine needs a ROCm GPU (gfx950); there is no CPU fallback")
+        super().__init__(device)
         if weight_format not in TEXT_WEIGHT_FORMATS:
             raise _lib.PevitError(f"TextEngine: weight_format {weight_format!r}: the text tower takes one of {TEXT_WEIGHT_FORMATS}")
         if max_prompts < 1:
             raise _lib.PevitError(f"TextEngine: max_prompts {max_prompts} must be positive")
-        self.lib = _lib.load()
         self.arch, self.max_prompts, self.weight_format = arch, int(max_prompts), weight_format
-        self.device = torch.device(device)
-        torch.cuda.set_device(self.device)
         dims = _lib.PevitTextDims(arch.text_width, arch.text_layers, arch.context_length, arch.vocab_size, arch.embed_dim,
                                   _lib.WEIGHT_FORMATS[weight_format])
-        self._ctx = C.c_void_p()
-        _lib.check(self.lib.pevit_text_create(C.byref(dims), C.byref(self._ctx)), "pevit_text_create")
-        self.arena = torch.zeros(self.lib.pevit_arena_bytes(self._ctx), dtype=torch.uint8, device=self.device)
-        self.workspace = torch.empty(self.lib.pevit_workspace_bytes(self._ctx, self.max_prompts), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.pevit_bind(self._ctx, _lib.ptr(self.arena), self.arena.numel(), _lib.ptr(self.workspace),
-                                       self.workspace.numel(), self.max_prompts), "pevit_bind")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self.lib.pevit_ctx_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
+        self._create("pevit_text_create", dims, self.max_prompts)
 
     def load_state_dict(self, sd):
         """Frozen text tower from an OpenAI-layout state-dict (any float dtype, any device): ``transformer.resblocks.*``,
         ``token_embedding.weight``, ``positional_embedding``, ``ln_final.*`` and ``text_projection``."""
-        s = _lib.stream_ptr()
-
-        def dev(key):
-            return sd[key].detach().to(device=self.device, dtype=torch.float32).contiguous()
-
         a = self.arch
         want = {"token_embedding.weight": (a.vocab_size, a.text_width), "positional_embedding": (a.context_length, a.text_width),
                 "text_projection": (a.text_width, a.embed_dim)}
         for k, shape in want.items():
             if tuple(sd[k].shape) != shape:
                 raise _lib.PevitError(f"TextEngine.load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
-        keep = []
-        for i in range(a.text_layers):
-            b = f"transformer.resblocks.{i}."
-            ts = [dev(b + k) for k in ("attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
-                                       "attn.out_proj.bias", "ln_1.weight", "ln_1.bias", "mlp.c_fc.weight",
-                                       "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias", "ln_2.weight", "ln_2.bias")]
-            keep.append(ts)
-            _lib.check(self.lib.pevit_load_block(self._ctx, s, i, *[_lib.ptr(t) for t in ts]), "pevit_load_block")
-        ts = [dev(k) for k in ("token_embedding.weight", "positional_embedding", "ln_final.weight", "ln_final.bias", "text_projection")]
+        keep = self._load_blocks(sd, "", a.text_layers)
+        ts = [self._dev(sd[k]) for k in ("token_embedding.weight", "positional_embedding", "ln_final.weight", "ln_final.bias",
+                                         "text_projection")]
         keep.append(ts)
-        _lib.check(self.lib.pevit_load_text_stem(self._ctx, s, *[_lib.ptr(t) for t in ts]), "pevit_load_text_stem")
+        _lib.check(self.lib.pevit_load_text_stem(self._ctx, _lib.stream_ptr(), *[_lib.ptr(t) for t in ts]), "pevit_load_text_stem")
         torch.cuda.current_stream().synchronize()     # the temporaries above may now be freed
         del keep
 

@@ -598,6 +598,49 @@ def test_state_reads_right_behind_a_pipelined_step_see_the_finished_update():
             dist.destroy_process_group()
 
 
+def test_no_engine_attribute_is_born_after_init():
+    """Every attribute of the engine is declared by ``__init__``: the input path, a step, the inference walks, the exchange timing,
+    the pipelined schedule and a planned optimizer rebind declared names and introduce none."""
+    import os
+    import torch.distributed as dist
+    from pevit_amd.engine import OptimPlan
+    meta, t = load_golden("tiny_kadaptation")
+    assert (meta["arch"], meta["method"]) == ("tiny-128", "kadaptation")
+    eng, _ = make_engine(meta, t, max_batch=4)
+    born = set(vars(eng))
+    images, labels = t["images"][:4].cuda().contiguous(), t["labels"][:4].cuda().contiguous()
+    eng.set_input_normalization((0.48, 0.46, 0.41), (0.27, 0.26, 0.28))
+    eng.set_input_resize(True)
+    g = torch.Generator().manual_seed(5)
+    assert eng.resize_u8(torch.randint(0, 256, (4, 3, 20, 24), dtype=torch.uint8, generator=g).cuda()).shape == (4, 3, 48, 48)
+    eng.train_step(images, labels, lr=0.01)
+    eng.predict(images)
+    feat = eng.encode_image(images)
+    eng.zeroshot(images, torch.nn.functional.normalize(torch.randn(3, feat.shape[1], generator=g), dim=1).cuda())
+    eng.time_exchange(True)
+    own_group = not dist.is_initialized()
+    if own_group:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29537")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    try:
+        for _ in range(2):
+            eng._train_step_pipelined(images, labels, 0.01, 0.9, 1e-4, True, None, 1, False, None, None)
+        assert eng._pipe["open"]
+        eng.dp_pipeline_off()
+    finally:
+        if own_group:
+            dist.destroy_process_group()
+    assert len(eng.exchange_times_us()) == 2
+    eng.reset_optimizer()
+    group_of = torch.where(eng.grad_mask_host != 0, 0, 255).to(torch.uint8)
+    plan = OptimPlan("adam", [{"lr": 1e-3, "weight_decay": 0.0, "beta1": 0.9, "beta2": 0.999, "eps": 1e-8}], group_of)
+    eng.forward_backward(images, labels)
+    eng.optimizer_step(plan)
+    torch.cuda.synchronize()
+    assert eng._optim_kind == "adam" and eng._steps == 1 and eng._pipe is None and eng.exp_avg_sq is not None
+    assert set(vars(eng)) == born
+
+
 def test_single_sample_batches_fail_like_batchnorm():
     """BatchNorm1d in training mode rejects a 1-sample batch in PyTorch (ValueError); the engine does the same
     instead of normalising by a zero variance.  Evaluation mode (running statistics) accepts it."""
