@@ -99,6 +99,11 @@ void pevit_ctx_destroy(pevit_ctx* ctx);
 /* sizes the caller must provide */
 size_t pevit_arena_bytes(const pevit_ctx* ctx);                 /* frozen weights, engine layout */
 size_t pevit_workspace_bytes(const pevit_ctx* ctx, int batch);  /* activations + scratch          */
+/* the leading bytes of the workspace that carry state from one launch to the next: the stream-K hand-off flags, the error word and
+ * the skipped-update counter.  pevit_bind zeroes them and every launch leaves the flags zero again; the same for every batch and
+ * for both layouts.  Everything behind them is scratch that every call writes before it reads: a caller may overwrite it between
+ * two calls (not between a forward and the backward that runs on its saved activations). */
+size_t pevit_workspace_state_bytes(const pevit_ctx* ctx);
 /* number of f32 trainable parameters: tower adapters (reference named_parameters() order,
  * README.md:84-87 counts) followed by the head weight (C x D) and bias (C) */
 size_t pevit_num_tower_params(const pevit_ctx* ctx);
@@ -167,7 +172,10 @@ int pevit_visual_backward_part(pevit_ctx* ctx, void* stream, const float* dfeat_
 size_t pevit_param_layer_offset(const pevit_ctx* ctx, int layer);
 /* BatchNorm1d(D, affine=False) -> Linear(D, C) -> mean cross-entropy, forward + backward.
  * bn_training: batch statistics + running-stat update (momentum 0.1); else running stats.
- * Writes logits (B x C), loss (1), dfeat (B x D); accumulates head grads into the flat buffer. */
+ * Writes logits (B x C), loss (1), dfeat (B x D); accumulates head grads into the flat buffer.
+ * Its scratch sits in the head slots of the layout the last saving forward left, so that the backward of that forward still finds
+ * its activations; a batch LARGER than that forward's does not fit there: the workspace is laid out for it, and a backward through
+ * the smaller forward is refused from then on. */
 int pevit_head_forward_backward(pevit_ctx* ctx, void* stream, const float* feat, const int64_t* labels,
                                 float* running_mean, float* running_var, int bn_training, float* logits,
                                 float* loss, float* dfeat_or_null, int batch);

@@ -148,6 +148,7 @@ SIGNATURES = {
     "pevit_ctx_destroy": (None, [P]),
     "pevit_arena_bytes": (c_size_t, [P]),
     "pevit_workspace_bytes": (c_size_t, [P, c_int]),
+    "pevit_workspace_state_bytes": (c_size_t, [P]),
     "pevit_num_tower_params": (c_size_t, [P]),
     "pevit_num_params": (c_size_t, [P]),
     "pevit_param_grad_mask": (c_int, [P, P, c_size_t]),

@@ -56,7 +56,7 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
     const size_t T = (size_t)B * c->N, E = c->E, es = c->es;
     WsLayout w{};
     // stream-K hand-off flags (+1 error word) and partial-tile slabs: first, so that their place does not depend on the batch
-    w.w_skflag = cv.take((size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4);     // + error word + skipped-update counter
+    w.w_skflag = cv.take(WS_STATE_BYTES);
     w.w_skslab = cv.take((size_t)c->sk_slots * PEVIT_SK_SLAB_FLOATS * 4);
     w.sav.resize(c->L);
     auto carve_layer = [&]() {
@@ -360,6 +360,8 @@ extern "C" size_t pevit_workspace_bytes(const pevit_ctx* c, int batch) {
     if (!c || batch <= 0) return 0;
     return layout_workspace(c, batch, c->text).total;      // a text context is inference-only: batch counts prompts
 }
+// what a caller must leave alone between two calls: layout_workspace carves it first, whatever the batch and the layout
+extern "C" size_t pevit_workspace_state_bytes(const pevit_ctx* c) { return c ? WS_STATE_BYTES : 0; }
 extern "C" size_t pevit_num_tower_params(const pevit_ctx* c) { return c ? c->n_tower : 0; }
 extern "C" size_t pevit_num_params(const pevit_ctx* c) { return c ? c->n_total : 0; }
 extern "C" size_t pevit_param_layer_offset(const pevit_ctx* c, int layer) {
@@ -388,8 +390,10 @@ extern "C" int pevit_bind(pevit_ctx* c, void* arena, size_t arena_bytes, void* w
     if (ws_bytes < need) { pevit_set_error("bind: workspace too small (%zu < %zu)", ws_bytes, need); return -1; }
     if (((uintptr_t)arena | (uintptr_t)ws) & 255) { pevit_set_error("bind: buffers must be 256-byte aligned"); return -1; }
     c->arena = (char*)arena; c->ws = (char*)ws; c->max_batch = max_batch; c->ws_bytes_for_max = need;
+    // whatever a forward saved lived in the workspace bound before: a backward through it is refused from here on
+    c->saved = SavedForward{}; c->dfeatb_of = nullptr;
     // the stream-K flags must read 0 before the first launch (every launch leaves them 0 again)
-    HIP_OK(hipMemset(c->ws, 0, (size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4));
+    HIP_OK(hipMemset(c->ws, 0, WS_STATE_BYTES));
     return 0;
 }
 
@@ -431,7 +435,7 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
         CHECK(pevit_launch_quant_transpose_fp8(pr_w, e, 4 * e, at<float>(A, b.spr), at<u8>(A, b.wprT), e, 0, 1.0f, s));
         // QKV backward (bf16): the transposed copy holds the DE-QUANTISED weights, exactly representable in bf16
         HIP_OK(hipMemsetAsync(A + b.wqkvT, 0, E * (size_t)c->NQ * 2, s));
-        const size_t skip = align_up((size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4, 256);    // the stream-K flags stay zero
+        const size_t skip = align_up(WS_STATE_BYTES, 256);    // the stream-K flags stay zero
         // 3E*E floats of the bound workspace serve as packing scratch: whatever activations a previous forward saved there
         // are overwritten, so a backward through them is refused from here on, and the load must be
         // issued on the stream the engine trains on (include/pevit_hip.h: one stream per context)

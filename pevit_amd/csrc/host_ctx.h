@@ -18,6 +18,10 @@
 // everything the units share lives in this namespace; hidden, so that the library exports the C ABI and the launchers as before
 namespace pevit_host __attribute__((visibility("hidden"))) {
 
+// the head of every workspace layout, the only part that carries state between launches (pevit_workspace_state_bytes): the
+// stream-K hand-off flags + the error word + the skipped-update counter
+constexpr size_t WS_STATE_BYTES = (size_t)(PEVIT_SK_MAX_SLOTS + 2) * 4;
+
 struct Carver {
     size_t off = 0;
     size_t take(size_t bytes) {

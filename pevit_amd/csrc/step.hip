@@ -511,7 +511,10 @@ static int head_fb_impl(pevit_ctx* c, void* stream, const float* feat, const int
     if (bn_training && B < 2) { pevit_set_error("head: BatchNorm in training mode needs more than 1 sample per batch (got %d)", B); return -1; }
     hipStream_t s = (hipStream_t)stream;
     char* W = c->ws;
-    if (c->saved.batch == 0) c->lay = layout_workspace(c, B);
+    // the head slots of the layout a saving forward left serve every batch up to that forward's; a larger one would overrun
+    // them into each other (ybn into rstd, dlogits, dybn ...): lay the workspace out for THIS batch, which gives the saved
+    // activations up -- check_saved refuses a backward through them from here on
+    if (B > c->saved.batch) { c->saved.batch = 0; c->lay = layout_workspace(c, B); }
     if (has_loss) c->last_loss = loss;
     // only inside the fused step: the head's BatchNorm backward leaves the bf16 copy of dfeat for the tower backward
     bf16* dfb = (fused_step && dfeat && has_loss && !c->f32) ? at<bf16>(W, c->lay.w_dfeatb) : nullptr;

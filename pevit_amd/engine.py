@@ -490,7 +490,8 @@ class HipEngine(EngineContext, InputMixin, OptimMixin, DpMixin):
     def head_forward_backward(self, feat, labels, bn_training=True, need_dfeat=True, out=None):
         """BatchNorm1d -> Linear -> loss, forward and backward.  ``labels``: int64 (B,) -> cross-entropy, float32 (B, num_classes)
         -> BCEWithLogitsLoss, None -> forward only.  ``out``: caller-owned f32 (logits (B, C), loss (1,), dfeat like ``feat``)
-        instead of fresh tensors."""
+        instead of fresh tensors.  A batch larger than that of the last saving forward lays the workspace out afresh: a backward
+        through that forward is refused afterwards."""
         self.dp_flush()
         B = feat.shape[0]
         fn = self.lib.pevit_head_forward_backward if labels is None else self._head_fn(labels, B)
