@@ -366,19 +366,29 @@ def make_wcache(p):
     return get
 
 
-def visual_forward(images, p, method):
-    d = R.visual_dims(p)
-    wcache = make_wcache(p)
+def stem(images, p, d):
+    """images (B,3,R,R) -> the (N,B,E) input of block 0: patch embedding on bf16 operands, class token, positions, ln_pre (f32)."""
     x = F.conv2d(bf(images, "img"), bf(p["visual.conv1.weight"], "w"), None, stride=d["patch"])
     x = x.reshape(x.shape[0], x.shape[1], -1).permute(0, 2, 1)
     cls = p["visual.class_embedding"] + torch.zeros(x.shape[0], 1, x.shape[-1])
     x = torch.cat([cls, x], dim=1) + p["visual.positional_embedding"]
     x = F.layer_norm(x, (x.shape[-1],), p["visual.ln_pre.weight"], p["visual.ln_pre.bias"], 1e-5)
-    x = x.permute(1, 0, 2).contiguous()
-    for i in range(d["layers"]):
-        x = block(x, p, i, d["heads"], method, wcache)
+    return x.permute(1, 0, 2).contiguous()
+
+
+def features(x, p):
+    """the (N,B,E) output of the last block -> (B,D) features: ln_post of the class tokens (bf16), proj"""
     xc = _ln_b(x[0], p["visual.ln_post.weight"], p["visual.ln_post.bias"], "cls")        # class token of every image
     return LinearE.apply(xc, bf(p["visual.proj"].detach().t(), "w"), None, False, False)
+
+
+def visual_forward(images, p, method):
+    d = R.visual_dims(p)
+    wcache = make_wcache(p)
+    x = stem(images, p, d)
+    for i in range(d["layers"]):
+        x = block(x, p, i, d["heads"], method, wcache)
+    return features(x, p)
 
 
 class EmulTrainer(R.OracleTrainer):

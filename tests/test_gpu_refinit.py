@@ -43,8 +43,11 @@ cancellation at step 0, and after five steps, with the loss down from 4.6 to 0.2
 L2 statement about it means anything; such tensors are listed in the report and counted (KAdaptation, LoRA and ViT-L/14 have none at any step; at step 0 the
 up-projection and the head are never among them), and covered by the whole-step gate
 (all gradient tensors of a step as ONE vector: relative L2 <= max(stated, FLOOR_C x the reference's whole-step floor) -- 0.03-0.2
-measured -- and < 1) and by tests/test_gpu_emulation.py.  profiles/r06_parity_refinit.md has engine-vs-floor per quantity and the
-gstream_bf16 0 / 1 A/B on the ill-conditioned kinds."""
+measured -- and < 1) and, PER TENSOR, by tests/test_gpu_refinit_blocks.py: every block alone through the (N,B,E) seam at this
+initialisation (step 0 and after four steps), on the block input and upstream gradient the bf16 emulation sees there, each of y, dx
+and the block's gradient tensors gated against the emulation at max(the gate of tests/test_gpu_emulation.py, 1.5 x the distance of
+plain f32 arithmetic from the emulation on the same inputs) -- below 0.95 for every kind, these included.
+profiles/r06_parity_refinit.md has engine-vs-floor per quantity and the gstream_bf16 0 / 1 A/B on the ill-conditioned kinds."""
 import json
 import math
 import os

@@ -241,7 +241,7 @@ def test_refinit_fixtures_carry_the_reference_recorded_bf16_floor(case):
     """Round 6: every *_refinit fixture holds, next to the reference's f32 results, how far the REFERENCE ITSELF moves when its frozen
     weights (leg "weights") and all its contraction operands (leg "operands"; ViT-L/14 also "fp8") are rounded to bf16
     (tests/golden/make_golden.py --refinit --bf16-weights).  tests/test_gpu_refinit.py gates the production kernels at
-    max(stated gate, 2 x this floor); here: the floor is complete (an entry for every recorded tensor), finite, and the weights-only
+    max(stated gate, FLOOR_C x this floor) with FLOOR_C = 3; here: the floor is complete (an entry for every recorded tensor), finite, and the weights-only
     leg keeps the logits within the stated 2e-2 on every fixture -- i.e. bf16 WEIGHTS alone never cost a stated gate on the logits."""
     import math
     meta, t = load_golden(case)
