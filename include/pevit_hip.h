@@ -305,6 +305,26 @@ int pevit_zeroshot(pevit_ctx* ctx, void* stream, const float* images, const floa
                    float* probs_or_null, float* logits_or_null, float* feat_or_null, int batch);
 int pevit_zeroshot_u8(pevit_ctx* ctx, void* stream, const uint8_t* images, const float* text_cd, int num_classes, float scale,
                       float* probs_or_null, float* logits_or_null, float* feat_or_null, int batch);
+/* ---- serving: an image context that can ONLY infer, next to a frozen tower, with adapters swapped in by pointer.
+ * pevit_infer_create: the checks and errors of pevit_ctx_create for every method and weight format; dims->num_classes is the LARGEST
+ * head the context will serve (it sizes the logits slot).  Its arena holds what the inference walk reads and nothing else: no
+ * transposed copy of a frozen matrix (the dX operands of a backward), no proj as the backward reads it; one write-only [width][64]
+ * panel per layer takes the transposed adapter panels that the panel-building kernels store whoever runs them.  Its workspace
+ * (pevit_workspace_bytes) is a third layout: the state words and the stream-K slabs, ONE set of per-layer activation slots without
+ * LayerNorm statistics and without the MLP pre-activation plus the alternate block input, the final residual stream, the ln_2
+ * output, gelu(h) (and the two e4m3 copies of fp8-act), one [tokens][width] f32 scratch, and the stem / feature / eval-head slots
+ * -- nothing that only a backward, a gradient reduction or a training head touches; its size does not depend on the layer count.
+ * pevit_bind, pevit_load_block (which needs no workspace scratch here, in any format), pevit_load_stem, pevit_load_phm_rule,
+ * pevit_set_input_norm, pevit_predict[_u8], pevit_encode_image[_u8], pevit_zeroshot[_u8] and the size / status / tune / profile
+ * queries run on it, with the kernels and the bits of the same call on a pevit_ctx_create context.  Every other entry point that
+ * takes a context is refused on the host before any launch ("inference-only context" in pevit_last_error); the workspace and its
+ * flag words are left alone.
+ * pevit_set_infer_params: params = device f32 [tower adapters in the flat order of pevit_set_params | head W (num_classes x D) | head b
+ * (num_classes)], 1 <= num_classes <= dims.num_classes; only read.  The head offsets and pevit_num_params follow num_classes, and
+ * pevit_predict writes batch x num_classes logits from then on.  Calling it again swaps the adapter: the walk rebuilds the adapter
+ * panels from this buffer on every forward, so a swap costs nothing else.  The buffer must stay alive while it is set. */
+int pevit_infer_create(const pevit_dims* dims, pevit_ctx** out);
+int pevit_set_infer_params(pevit_ctx* ctx, const float* params, int num_classes);
 /* the zero-shot head alone, context-free (parity tests): feat (B x D), text_cd (C x D), outputs (B x C) */
 int pevit_op_zeroshot_head(void* stream, const float* feat, const float* text_cd, float scale, float* probs_or_null,
                            float* logits_or_null, int B, int D, int C);

@@ -174,6 +174,8 @@ SIGNATURES = {
     "pevit_encode_image_u8": (c_int, [P, P, P, P, c_int]),
     "pevit_zeroshot": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int]),
     "pevit_zeroshot_u8": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int]),
+    "pevit_infer_create": (c_int, [C.POINTER(PevitDims), C.POINTER(c_void_p)]),
+    "pevit_set_infer_params": (c_int, [P, P, c_int]),
     "pevit_op_zeroshot_head": (c_int, [P, P, P, c_float, P, P, c_int, c_int, c_int]),
     "pevit_probe_step": (c_int, [P, P, C.POINTER(PevitProbeArgs)]),
     "pevit_probe_predict": (c_int, [P, P, C.POINTER(PevitProbePredictArgs)]),

@@ -51,10 +51,13 @@ StepPlan plan_step(const pevit_ctx* c, int B, bool infer) {
 // infer: the layout of the inference walk -- no layer keeps anything, so ONE set of activation slots serves every layer and the f32
 // residual stream alternates between two input buffers (+ x_mid + w_xfinal: four [T][E] buffers whatever the layer count); the
 // pre-activation h and the LayerNorm statistics have no slot at all.  Never larger than the training layout of the same batch.
+// An inference-only context (pevit_infer_create) has the third layout whatever `infer` says: the inference layout without every
+// slot that only a backward, a gradient reduction or a training head touches.  It does not depend on the layer count.
 WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
     Carver cv;
     const size_t T = (size_t)B * c->N, E = c->E, es = c->es;
     WsLayout w{};
+    if (c->infer_only) infer = true;
     // stream-K hand-off flags (+1 error word) and partial-tile slabs: first, so that their place does not depend on the batch
     w.w_skflag = cv.take(WS_STATE_BYTES);
     w.w_skslab = cv.take((size_t)c->sk_slots * PEVIT_SK_SLAB_FLOATS * 4);
@@ -94,6 +97,19 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
         w.w_a8 = cv.take(T * E);
         w.w_attn8 = cv.take(T * E);
     }
+    const size_t Bz = (size_t)B, D = c->D;
+    if (c->infer_only) {
+        // the walk's names for its one [T][E] f32 scratch: the stem's xpre, ytmp of the unfused post-MLP path
+        w.w_dxn = cv.take(T * E * 4);
+        w.w_patches = cv.take(Bz * c->G2 * (size_t)c->Kpatch * es);
+        w.w_xpost = cv.take(Bz * E * es);
+        w.w_feat = cv.take(Bz * D * 4);
+        w.w_ybn = cv.take(Bz * D * 4);
+        w.w_bnrstd = cv.take(D * 4);
+        w.w_logits = cv.take(Bz * (size_t)c->d.num_classes * 4);     // (the largest head: pevit_set_infer_params moves c->C below it)
+        w.total = cv.off;
+        return w;
+    }
     w.w_dqkv = cv.take(T * (size_t)c->NQ * es);
     w.w_u32 = cv.take(T * 64 * 4);
     w.w_u32b = cv.take(T * 64 * 4);             // second u buffer: dP of a layer is taken one launch later (lowrank_combo)
@@ -126,7 +142,7 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
         w.w_Gd = cv.take((size_t)c->L * E * 64 * 4);
         w.w_Gu = cv.take((size_t)c->L * E * 64 * 4);
     }
-    const size_t Bz = (size_t)B, D = c->D, Cc = c->C;
+    const size_t Cc = c->C;
     w.w_patches = cv.take(Bz * c->G2 * (size_t)c->Kpatch * es);
     w.w_xpost = cv.take(Bz * E * es);
     w.w_feat = cv.take(Bz * D * 4);
@@ -145,12 +161,29 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
 }
 
 // the per-layer weight slots of the arena (c->blk must hold c->L entries): what pevit_load_block fills
+// An inference-only context (pevit_infer_create) has no slot for what only a backward reads: wqkvT, woT, wfcT, wprT, wdT, wuT.  The
+// prep kernels store the transposed adapter panels whoever runs them, so such a context gives them ONE write-only [E][64] panel per
+// layer (tsink) in place of the 64 adapter columns of wqkvT (attention-site methods) or of wdT and wuT (post-MLP methods).
 static void carve_block_arena(pevit_ctx* c, Carver& cv) {
     const size_t E = c->E;
     for (int l = 0; l < c->L; ++l) {
         BlockArena& b = c->blk[l];
-        b.wpan = b.sqkv = b.so = b.sfc = b.spr = 0;
-        if (c->fp8) {
+        b.wpan = b.sqkv = b.so = b.sfc = b.spr = b.tsink = 0;
+        if (c->infer_only) {
+            if (c->fp8) {
+                const size_t r1 = align_up(E, 256), r3 = align_up(3 * E, 256), r4 = align_up(4 * E, 256);
+                b.wqkv = cv.take(r3 * E);
+                b.wpan = cv.take(128 * E * 2);
+                b.wo = cv.take(r1 * E); b.wfc = cv.take(r4 * E); b.wpr = cv.take(r1 * 4 * E);
+                b.sqkv = cv.take(3 * E * 4); b.so = cv.take(E * 4); b.sfc = cv.take(4 * E * 4); b.spr = cv.take(E * 4);
+            } else {
+                const size_t es = c->es;
+                b.wqkv = cv.take((size_t)c->NQpad * E * es);
+                b.wo = cv.take(E * E * es); b.wfc = cv.take(4 * E * E * es); b.wpr = cv.take(4 * E * E * es);
+            }
+            b.wqkvT = b.woT = b.wfcT = b.wprT = b.wdT = b.wuT = 0;
+            if (c->d.method != PEVIT_NONE) b.tsink = cv.take(64 * E * c->es);
+        } else if (c->fp8) {
             // one byte per weight; rows padded to the largest tile (256) so that clamped tile rows stay readable
             const size_t r1 = align_up(E, 256), r3 = align_up(3 * E, 256), r4 = align_up(4 * E, 256);
             b.wqkv = cv.take(r3 * E);
@@ -171,6 +204,7 @@ static void carve_block_arena(pevit_ctx* c, Carver& cv) {
         b.bqkv = cv.take(3 * E * 4); b.bo = cv.take(E * 4); b.bfc = cv.take(4 * E * 4); b.bpr = cv.take(E * 4);
         b.ln1w = cv.take(E * 4); b.ln1b = cv.take(E * 4); b.ln2w = cv.take(E * 4); b.ln2b = cv.take(E * 4);
         b.q32 = cv.take(E * 64 * 4); b.qT = cv.take(64 * E * c->es); b.q16 = cv.take(E * 64 * 2);
+        if (c->infer_only) { b.wd = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); continue; }
         b.wd = cv.take(64 * E * c->es); b.wdT = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); b.wuT = cv.take(64 * E * c->es);
     }
 }
@@ -180,6 +214,17 @@ static void carve_block_arena(pevit_ctx* c, Carver& cv) {
 int refuse_text(const pevit_ctx* c, const char* who) {
     if (c && c->text) {
         pevit_set_error("%s: this is a text context (pevit_text_create); it runs pevit_encode_text only", who);
+        return -1;
+    }
+    return 0;
+}
+
+// everything but the inference walk, its loaders and the queries on an inference-only context, checked on the host before anything else:
+// nothing is launched, the flag words and the workspace stay as they are
+int refuse_infer(const pevit_ctx* c, const char* who) {
+    if (c && c->infer_only) {
+        pevit_set_error("%s: this is an inference-only context (pevit_infer_create); it runs pevit_predict, pevit_encode_image and "
+                        "pevit_zeroshot only", who);
         return -1;
     }
     return 0;
@@ -202,7 +247,7 @@ int check_saved(const pevit_ctx* c, Saved want, int B, int layer, const char* wh
 int check_ready(pevit_ctx* c, int B, const char* who) {
     if (!c || !c->arena || !c->ws) { pevit_set_error("%s: context not bound", who); return -1; }
     if (B <= 0 || B > c->max_batch) { pevit_set_error("%s: batch %d outside [1,%d]", who, B, c->max_batch); return -1; }
-    if (c->d.method != PEVIT_NONE && (!c->params || !c->grads)) { pevit_set_error("%s: parameters not set", who); return -1; }
+    if (c->d.method != PEVIT_NONE && (!c->params || (!c->grads && !c->infer_only))) { pevit_set_error("%s: parameters not set", who); return -1; }
     return 0;
 }
 
@@ -211,32 +256,35 @@ int check_ready(pevit_ctx* c, int B, const char* who) {
 using namespace pevit_host;
 
 // ------------------------------------------------------------------------------------
-extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
-    if (!dims || !out) { pevit_set_error("ctx_create: null argument"); return -1; }
+// what pevit_ctx_create and pevit_infer_create share: the checks of the dims (errors under the caller's name `who`), the arena and the
+// flat parameter layout.  No HIP call: sizes only.
+static int create_image_ctx(const pevit_dims* dims, pevit_ctx** out, bool infer_only, const char* who) {
+    if (!dims || !out) { pevit_set_error("%s: null argument", who); return -1; }
     const pevit_dims d = *dims;
     if (d.width <= 0 || d.width % 128 != 0 || d.width > 1024) {
-        pevit_set_error("ctx_create: width %d must be a multiple of 128 in (0,1024]", d.width); return -1;
+        pevit_set_error("%s: width %d must be a multiple of 128 in (0,1024]", who, d.width); return -1;
     }
     if (d.layers <= 0 || d.patch <= 0 || d.resolution <= 0 || d.resolution % d.patch != 0) {
-        pevit_set_error("ctx_create: bad layers/patch/resolution %d/%d/%d", d.layers, d.patch, d.resolution); return -1;
+        pevit_set_error("%s: bad layers/patch/resolution %d/%d/%d", who, d.layers, d.patch, d.resolution); return -1;
     }
-    if (d.method < 0 || d.method > PEVIT_NONE) { pevit_set_error("ctx_create: unknown method %d", d.method); return -1; }
+    if (d.method < 0 || d.method > PEVIT_NONE) { pevit_set_error("%s: unknown method %d", who, d.method); return -1; }
     if (d.method == PEVIT_LORA && (d.lora_rank < 1 || d.lora_rank > 32)) {
-        pevit_set_error("ctx_create: LoRA rank %d outside [1,32]", d.lora_rank); return -1;
+        pevit_set_error("%s: LoRA rank %d outside [1,32]", who, d.lora_rank); return -1;
     }
     if (d.weight_format != PEVIT_W_BF16 && d.weight_format != PEVIT_W_FP8_E4M3 && d.weight_format != PEVIT_W_F32_VERIFY &&
         d.weight_format != PEVIT_W_FP8_ACT) {
-        pevit_set_error("ctx_create: unknown weight_format %d", d.weight_format); return -1;
+        pevit_set_error("%s: unknown weight_format %d", who, d.weight_format); return -1;
     }
     if ((d.weight_format == PEVIT_W_FP8_E4M3 || d.weight_format == PEVIT_W_FP8_ACT) && (d.method == PEVIT_ADAPTER || d.method == PEVIT_COMPACTER)) {
-        pevit_set_error("ctx_create: fp8 weights are built for the attention-site methods (KAdaptation, LoRA) and the frozen tower"); return -1;
+        pevit_set_error("%s: fp8 weights are built for the attention-site methods (KAdaptation, LoRA) and the frozen tower", who); return -1;
     }
     if (d.out_dim <= 0 || d.out_dim % 8 != 0 || d.num_classes <= 0) {
-        pevit_set_error("ctx_create: bad out_dim/num_classes %d/%d", d.out_dim, d.num_classes); return -1;
+        pevit_set_error("%s: bad out_dim/num_classes %d/%d", who, d.out_dim, d.num_classes); return -1;
     }
     pevit_ctx* c = new (std::nothrow) pevit_ctx();
-    if (!c) { pevit_set_error("ctx_create: out of host memory"); return -1; }
+    if (!c) { pevit_set_error("%s: out of host memory", who); return -1; }
     c->d = d;
+    c->infer_only = infer_only;
     c->E = d.width; c->L = d.layers; c->H = d.width / 64; c->P = d.patch; c->R = d.resolution;
     const int grid = d.resolution / d.patch;
     c->G2 = grid * grid; c->N = c->G2 + 1; c->D = d.out_dim; c->C = d.num_classes;
@@ -248,11 +296,11 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
     c->f32 = d.weight_format == PEVIT_W_F32_VERIFY;
     c->es = c->f32 ? 4 : 2;
     c->sk_slots = c->f32 ? 0 : pevit_gemm_sk_slots();
-    if (c->N > 288) { pevit_set_error("ctx_create: %d tokens per image exceeds 288", c->N); delete c; return -1; }
+    if (c->N > 288) { pevit_set_error("%s: %d tokens per image exceeds 288", who, c->N); delete c; return -1; }
 
     // ---- weight arena -------------------------------------------------------------
     c->blk = new (std::nothrow) BlockArena[c->L];
-    if (!c->blk) { pevit_set_error("ctx_create: out of host memory"); pevit_ctx_destroy(c); return -1; }
+    if (!c->blk) { pevit_set_error("%s: out of host memory", who); pevit_ctx_destroy(c); return -1; }
     Carver cv;
     const size_t E = c->E;
     carve_block_arena(c, cv);
@@ -262,7 +310,7 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
     c->a_lnpre_w = cv.take(E * 4); c->a_lnpre_b = cv.take(E * 4);
     c->a_lnpost_w = cv.take(E * 4); c->a_lnpost_b = cv.take(E * 4);
     c->a_proj = cv.take(align_up((size_t)c->D, 128) * E * c->es);      // [D][E]  (proj^T)
-    c->a_projT = cv.take(E * (size_t)c->D * c->es);                   // [E][D]
+    c->a_projT = infer_only ? 0 : cv.take(E * (size_t)c->D * c->es);  // [E][D]: the backward's operand
     c->a_phm = cv.take(64 * 4);
     c->arena_bytes = cv.off;
 
@@ -292,6 +340,12 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) {
     *out = c;
     return 0;
 }
+
+extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) { return create_image_ctx(dims, out, false, "ctx_create"); }
+
+// An image context that can only infer (include/pevit_hip.h): the arena without the transposed copies, the third workspace layout
+// (layout_workspace), parameters through pevit_set_infer_params.  dims->num_classes is the largest head it will serve.
+extern "C" int pevit_infer_create(const pevit_dims* dims, pevit_ctx** out) { return create_image_ctx(dims, out, true, "infer_create"); }
 
 // The CLIP text tower as a context: the block arena of pevit_ctx_create (method PEVIT_NONE) and, in place of the image stem, the f32
 // token-embedding table, the positional embedding, ln_final and text_projection^T.  No HIP call: sizes only.
@@ -358,7 +412,7 @@ extern "C" void pevit_ctx_destroy(pevit_ctx* c) {
 extern "C" size_t pevit_arena_bytes(const pevit_ctx* c) { return c ? c->arena_bytes : 0; }
 extern "C" size_t pevit_workspace_bytes(const pevit_ctx* c, int batch) {
     if (!c || batch <= 0) return 0;
-    return layout_workspace(c, batch, c->text).total;      // a text context is inference-only: batch counts prompts
+    return layout_workspace(c, batch, c->text).total;      // a text context is inference-only: batch counts prompts (pevit_infer_create: its own layout)
 }
 // what a caller must leave alone between two calls: layout_workspace carves it first, whatever the batch and the layout
 extern "C" size_t pevit_workspace_state_bytes(const pevit_ctx* c) { return c ? WS_STATE_BYTES : 0; }
@@ -398,8 +452,26 @@ extern "C" int pevit_bind(pevit_ctx* c, void* arena, size_t arena_bytes, void* w
 }
 
 extern "C" int pevit_set_params(pevit_ctx* c, float* params, float* grads, float* mom, const unsigned char* mask) {
+    CHECK(refuse_infer(c, "set_params"));
     if (!c || !params || !grads) { pevit_set_error("set_params: null argument"); return -1; }
     c->params = params; c->grads = grads; c->mom = mom; c->grad_mask = mask;
+    return 0;
+}
+
+// The parameters of an inference-only context: params = [tower adapters in adapter_param_spec order | head W (C x D) | head b (C)],
+// device f32, for 1 <= C <= dims.num_classes; the head offsets follow C.  Only read, by pointer: calling again swaps the adapter (the
+// walk rebuilds the adapter panels from the flat buffer on every forward).
+extern "C" int pevit_set_infer_params(pevit_ctx* c, const float* params, int num_classes) {
+    if (!c || !params) { pevit_set_error("set_infer_params: null argument"); return -1; }
+    if (!c->infer_only) { pevit_set_error("set_infer_params: not an inference-only context (pevit_infer_create); a training context takes pevit_set_params"); return -1; }
+    if (num_classes < 1 || num_classes > c->d.num_classes) {
+        pevit_set_error("set_infer_params: num_classes %d outside [1,%d] of the context", num_classes, c->d.num_classes); return -1;
+    }
+    c->params = const_cast<float*>(params);
+    c->C = num_classes;
+    c->p_head_w = c->n_tower;
+    c->p_head_b = c->p_head_w + (size_t)c->C * c->D;
+    c->n_total = c->p_head_b + c->C;
     return 0;
 }
 
@@ -421,42 +493,47 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
         HIP_OK(hipMemsetAsync(A + b.wqkv, 0, align_up(3 * E, 256) * E, s));
         HIP_OK(hipMemsetAsync(A + b.wpan, 0, 128 * E * 2, s));
         HIP_OK(hipMemsetAsync(A + b.wo, 0, align_up(E, 256) * E, s));
-        HIP_OK(hipMemsetAsync(A + b.woT, 0, align_up(E, 256) * E, s));
         HIP_OK(hipMemsetAsync(A + b.wfc, 0, align_up(4 * E, 256) * E, s));
-        HIP_OK(hipMemsetAsync(A + b.wfcT, 0, align_up(E, 256) * 4 * E, s));
         HIP_OK(hipMemsetAsync(A + b.wpr, 0, align_up(E, 256) * 4 * E, s));
-        HIP_OK(hipMemsetAsync(A + b.wprT, 0, align_up(4 * E, 256) * E, s));
         CHECK(pevit_launch_quant_rows_fp8(in_w, 3 * e, e, at<u8>(A, b.wqkv), e, at<float>(A, b.sqkv), e, 0.125f, s));
         CHECK(pevit_launch_quant_rows_fp8(out_w, e, e, at<u8>(A, b.wo), e, at<float>(A, b.so), 0, 1.0f, s));
-        CHECK(pevit_launch_quant_transpose_fp8(out_w, e, e, at<float>(A, b.so), at<u8>(A, b.woT), e, 0, 1.0f, s));
         CHECK(pevit_launch_quant_rows_fp8(fc_w, 4 * e, e, at<u8>(A, b.wfc), e, at<float>(A, b.sfc), 0, 1.0f, s));
-        CHECK(pevit_launch_quant_transpose_fp8(fc_w, 4 * e, e, at<float>(A, b.sfc), at<u8>(A, b.wfcT), 4 * e, 0, 1.0f, s));
         CHECK(pevit_launch_quant_rows_fp8(pr_w, e, 4 * e, at<u8>(A, b.wpr), 4 * e, at<float>(A, b.spr), 0, 1.0f, s));
-        CHECK(pevit_launch_quant_transpose_fp8(pr_w, e, 4 * e, at<float>(A, b.spr), at<u8>(A, b.wprT), e, 0, 1.0f, s));
-        // QKV backward (bf16): the transposed copy holds the DE-QUANTISED weights, exactly representable in bf16
-        HIP_OK(hipMemsetAsync(A + b.wqkvT, 0, E * (size_t)c->NQ * 2, s));
-        const size_t skip = align_up(WS_STATE_BYTES, 256);    // the stream-K flags stay zero
-        // 3E*E floats of the bound workspace serve as packing scratch: whatever activations a previous forward saved there
-        // are overwritten, so a backward through them is refused from here on, and the load must be
-        // issued on the stream the engine trains on (include/pevit_hip.h: one stream per context)
-        float* tmp = at<float>(c->ws, skip);
-        c->saved = SavedForward{};
-        if (skip + (size_t)3 * E * E * 4 > c->ws_bytes_for_max) { pevit_set_error("load_block: workspace too small for the fp8 packing scratch"); return -1; }
-        CHECK(pevit_launch_dequant_rows_fp8(at<u8>(A, b.wqkv), e, at<float>(A, b.sqkv), 3 * e, e, tmp, s));
-        CHECK(pevit_launch_transpose_bf16(tmp, 3 * e, e, at<bf16>(A, b.wqkvT), c->NQ, 0, 1.0f, s));
+        // an inference-only context keeps no transposed copy, so its load needs no workspace scratch either
+        if (!c->infer_only) {
+            HIP_OK(hipMemsetAsync(A + b.woT, 0, align_up(E, 256) * E, s));
+            HIP_OK(hipMemsetAsync(A + b.wfcT, 0, align_up(E, 256) * 4 * E, s));
+            HIP_OK(hipMemsetAsync(A + b.wprT, 0, align_up(4 * E, 256) * E, s));
+            CHECK(pevit_launch_quant_transpose_fp8(out_w, e, e, at<float>(A, b.so), at<u8>(A, b.woT), e, 0, 1.0f, s));
+            CHECK(pevit_launch_quant_transpose_fp8(fc_w, 4 * e, e, at<float>(A, b.sfc), at<u8>(A, b.wfcT), 4 * e, 0, 1.0f, s));
+            CHECK(pevit_launch_quant_transpose_fp8(pr_w, e, 4 * e, at<float>(A, b.spr), at<u8>(A, b.wprT), e, 0, 1.0f, s));
+            // QKV backward (bf16): the transposed copy holds the DE-QUANTISED weights, exactly representable in bf16
+            HIP_OK(hipMemsetAsync(A + b.wqkvT, 0, E * (size_t)c->NQ * 2, s));
+            const size_t skip = align_up(WS_STATE_BYTES, 256);    // the stream-K flags stay zero
+            // 3E*E floats of the bound workspace serve as packing scratch: whatever activations a previous forward saved there
+            // are overwritten, so a backward through them is refused from here on, and the load must be
+            // issued on the stream the engine trains on (include/pevit_hip.h: one stream per context)
+            float* tmp = at<float>(c->ws, skip);
+            c->saved = SavedForward{};
+            if (skip + (size_t)3 * E * E * 4 > c->ws_bytes_for_max) { pevit_set_error("load_block: workspace too small for the fp8 packing scratch"); return -1; }
+            CHECK(pevit_launch_dequant_rows_fp8(at<u8>(A, b.wqkv), e, at<float>(A, b.sqkv), 3 * e, e, tmp, s));
+            CHECK(pevit_launch_transpose_bf16(tmp, 3 * e, e, at<bf16>(A, b.wqkvT), c->NQ, 0, 1.0f, s));
+        }
     } else {
         const int f = c->f32;
         HIP_OK(hipMemsetAsync(A + b.wqkv, 0, (size_t)c->NQpad * E * c->es, s));
         CHECK(pevit_launch_cast_bf16(in_w, at<bf16>(A, b.wqkv), E * E, 0.125f, s, f));
         CHECK(pevit_launch_cast_bf16(in_w + E * E, eadv(c, at<bf16>(A, b.wqkv), E * E), 2 * E * E, 1.0f, s, f));
-        HIP_OK(hipMemsetAsync(A + b.wqkvT, 0, E * (size_t)c->NQ * c->es, s));
-        CHECK(pevit_launch_transpose_bf16(in_w, 3 * (int)E, (int)E, at<bf16>(A, b.wqkvT), c->NQ, (int)E, 0.125f, s, f));
         CHECK(pevit_launch_cast_bf16(out_w, at<bf16>(A, b.wo), E * E, 1.0f, s, f));
-        CHECK(pevit_launch_transpose_bf16(out_w, (int)E, (int)E, at<bf16>(A, b.woT), (int)E, 0, 1.0f, s, f));
         CHECK(pevit_launch_cast_bf16(fc_w, at<bf16>(A, b.wfc), 4 * E * E, 1.0f, s, f));
-        CHECK(pevit_launch_transpose_bf16(fc_w, 4 * (int)E, (int)E, at<bf16>(A, b.wfcT), 4 * (int)E, 0, 1.0f, s, f));
         CHECK(pevit_launch_cast_bf16(pr_w, at<bf16>(A, b.wpr), 4 * E * E, 1.0f, s, f));
-        CHECK(pevit_launch_transpose_bf16(pr_w, (int)E, 4 * (int)E, at<bf16>(A, b.wprT), (int)E, 0, 1.0f, s, f));
+        if (!c->infer_only) {           // the transposed copies: operands of the dX products
+            HIP_OK(hipMemsetAsync(A + b.wqkvT, 0, E * (size_t)c->NQ * c->es, s));
+            CHECK(pevit_launch_transpose_bf16(in_w, 3 * (int)E, (int)E, at<bf16>(A, b.wqkvT), c->NQ, (int)E, 0.125f, s, f));
+            CHECK(pevit_launch_transpose_bf16(out_w, (int)E, (int)E, at<bf16>(A, b.woT), (int)E, 0, 1.0f, s, f));
+            CHECK(pevit_launch_transpose_bf16(fc_w, 4 * (int)E, (int)E, at<bf16>(A, b.wfcT), 4 * (int)E, 0, 1.0f, s, f));
+            CHECK(pevit_launch_transpose_bf16(pr_w, (int)E, 4 * (int)E, at<bf16>(A, b.wprT), (int)E, 0, 1.0f, s, f));
+        }
     }
     // biases and LN affines stay f32; the q third of in_proj_bias carries the same 1/8
     HIP_OK(hipMemcpyAsync(A + b.bqkv, in_b, 3 * E * 4, hipMemcpyDeviceToDevice, s));
@@ -475,6 +552,7 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
 }
 
 extern "C" int pevit_set_optim_state(pevit_ctx* c, float* exp_avg_sq, const unsigned char* group_of) {
+    CHECK(refuse_infer(c, "set_optim_state"));
     if (!c || !group_of) { pevit_set_error("set_optim_state: null argument"); return -1; }
     c->exp_avg_sq = exp_avg_sq; c->group_of = group_of;
     return 0;
@@ -483,6 +561,7 @@ extern "C" int pevit_set_optim_state(pevit_ctx* c, float* exp_avg_sq, const unsi
 // a device word owned by the caller (e.g. pevit_ar_error_word) that, while non-zero, makes pevit_sgd_step withhold the update --
 // the same treatment a stream-K hand-off error gets.  nullptr detaches it.  The word must outlive the context's use of it.
 extern "C" int pevit_set_external_poison(pevit_ctx* c, const unsigned* device_word) {
+    CHECK(refuse_infer(c, "set_external_poison"));
     if (!c) { pevit_set_error("set_external_poison: null context"); return -1; }
     c->ext_poison = device_word;
     return 0;
@@ -494,6 +573,7 @@ extern "C" int pevit_set_external_poison(pevit_ctx* c, const unsigned* device_wo
 // previous step's gradient exchange + optimizer update, which it may then run on another stream: the exchange's latency and its
 // cross-stream hand-overs run under ~70 us of the next step's stem instead of between two steps.  nullptr detaches it.
 extern "C" int pevit_set_step_gate(pevit_ctx* c, void* event) {
+    CHECK(refuse_infer(c, "set_step_gate"));
     if (!c) { pevit_set_error("set_step_gate: null context"); return -1; }
     c->step_gate = (hipEvent_t)event;
     return 0;
@@ -517,7 +597,7 @@ extern "C" int pevit_load_stem(pevit_ctx* c, void* stream, const float* conv_w, 
     HIP_OK(hipMemcpyAsync(A + c->a_lnpost_b, lnpost_b, E * 4, hipMemcpyDeviceToDevice, s));
     // proj is (E, D): feat = x @ proj  ->  B operand [D][E] = proj^T ; backward uses proj itself [E][D]
     CHECK(pevit_launch_transpose_bf16(proj, c->E, c->D, at<bf16>(A, c->a_proj), c->E, 0, 1.0f, s, c->f32));
-    CHECK(pevit_launch_cast_bf16(proj, at<bf16>(A, c->a_projT), E * (size_t)c->D, 1.0f, s, c->f32));
+    if (!c->infer_only) CHECK(pevit_launch_cast_bf16(proj, at<bf16>(A, c->a_projT), E * (size_t)c->D, 1.0f, s, c->f32));
     return 0;
 }
 

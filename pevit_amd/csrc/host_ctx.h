@@ -38,6 +38,7 @@ struct BlockArena {        // byte offsets inside the weight arena, one per laye
     size_t wd, wdT, wu, wuT;      // post-MLP adapter panels (bf16), rewritten every step
     size_t wpan;                  // fp8 weights only: the 64 adapter rows P_q^T | P_v^T (bf16) of the separate t = xn P product
     size_t sqkv, so, sfc, spr;    // fp8 weights only: per-output-channel scales (f32, powers of two)
+    size_t tsink;                 // inference-only contexts: [E][64] write-only panel that takes the transposed stores of the prep kernels
 };
 
 struct LayerSaved {        // byte offsets inside the workspace, one per layer (kept for backward)
@@ -101,6 +102,7 @@ struct pevit_ctx {
     bool f32 = false;         // f32-class verification mode: every bf16-declared buffer holds f32 (verify.hip)
     bool text = false;        // CLIP text tower (pevit_text_create): N = context_length, inference only, pevit_encode_text is its one forward
     bool causal = false;      // ... its attention is causal (attn_core_fwd passes this to the attention launch)
+    bool infer_only = false;  // pevit_infer_create: no transposed weight copies, the third workspace layout, no gradients; runs the inference walk only
     int V = 0;                // ... vocabulary size (rows of the token-embedding table)
     size_t a_tok = 0;         // ... arena offset of the f32 token-embedding table [V][E]
     size_t es = 2;            // bytes per element of those buffers
@@ -175,6 +177,7 @@ inline bf16* eadv(const pevit_ctx* c, const bf16* p, size_t elems) {
 StepPlan plan_step(const pevit_ctx* c, int B, bool infer = false);
 WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer = false);
 int refuse_text(const pevit_ctx* c, const char* who);
+int refuse_infer(const pevit_ctx* c, const char* who);
 int check_saved(const pevit_ctx* c, Saved want, int B, int layer, const char* who);
 int check_ready(pevit_ctx* c, int B, const char* who);
 

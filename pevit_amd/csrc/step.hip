@@ -28,6 +28,7 @@ static int check_layer(const pevit_ctx* c, int layer, const char* who) {
 extern "C" int pevit_blocks_forward(pevit_ctx* c, void* stream, const float* x_nbe, float* y_nbe, int B, int save_for_backward,
                                     int l_lo, int l_hi) {
     CHECK(refuse_text(c, "blocks_forward"));
+    CHECK(refuse_infer(c, "blocks_forward"));
     CHECK(check_ready(c, B, "blocks_forward"));
     CHECK(check_range(c, l_lo, l_hi, "blocks_forward", "block"));
     hipStream_t s = (hipStream_t)stream;
@@ -50,6 +51,7 @@ extern "C" int pevit_transformer_forward(pevit_ctx* c, void* stream, const float
 // exactly these blocks are accumulated into the flat gradient buffer
 extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy_nbe, float* dx_nbe, int B, int l_lo, int l_hi) {
     CHECK(refuse_text(c, "blocks_backward"));
+    CHECK(refuse_infer(c, "blocks_backward"));
     CHECK(check_ready(c, B, "blocks_backward"));
     CHECK(check_range(c, l_lo, l_hi, "blocks_backward", "block"));
     CHECK(check_saved(c, Saved::blocks, B, -1, "blocks_backward"));
@@ -73,6 +75,7 @@ extern "C" int pevit_blocks_backward(pevit_ctx* c, void* stream, const float* dy
 extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, const float* x_nbe, float* y_nbe, int B,
                                        int save_for_backward, float* weights, int average_weights) {
     CHECK(refuse_text(c, "attention_forward"));
+    CHECK(refuse_infer(c, "attention_forward"));
     CHECK(check_ready(c, B, "attention_forward"));
     CHECK(check_layer(c, layer, "attention_forward"));
     if (c->fp8act) {
@@ -113,6 +116,7 @@ extern "C" int pevit_attention_forward(pevit_ctx* c, void* stream, int layer, co
 // shared phm_rule factors).  Adapter / Compacter / the frozen tower: stock attention with frozen weights, dx only.
 extern "C" int pevit_attention_backward(pevit_ctx* c, void* stream, int layer, const float* dy_nbe, float* dx_nbe, int B) {
     CHECK(refuse_text(c, "attention_backward"));
+    CHECK(refuse_infer(c, "attention_backward"));
     CHECK(check_ready(c, B, "attention_backward"));
     CHECK(check_layer(c, layer, "attention_backward"));
     CHECK(check_saved(c, Saved::attention, B, layer, "attention_backward"));
@@ -142,6 +146,7 @@ extern "C" int pevit_transformer_backward(pevit_ctx* c, void* stream, const floa
 }
 
 extern "C" int pevit_zero_grads(pevit_ctx* c, void* stream) {
+    CHECK(refuse_infer(c, "zero_grads"));
     if (!c || !c->grads) { pevit_set_error("zero_grads: parameters not set"); return -1; }
     CHECK(pevit_launch_zero(c->grads, c->n_total * sizeof(float), (hipStream_t)stream));
     return 0;
@@ -149,6 +154,7 @@ extern "C" int pevit_zero_grads(pevit_ctx* c, void* stream) {
 
 extern "C" int pevit_sgd_step(pevit_ctx* c, void* stream, float lr, float momentum, float wd, float grad_scale,
                               int flags) {
+    CHECK(refuse_infer(c, "sgd_step"));
     if (!c || !c->params || !c->grads || !c->mom) { pevit_set_error("sgd_step: parameters/momentum not set"); return -1; }
     // the error word of the workspace bound NOW (a re-bind moves it; without stream-K slots -- f32 verification mode -- there is
     // no hand-off that could fail and nothing to guard)
@@ -170,6 +176,7 @@ static_assert((int)PEVIT_OPTIM_SGD == (int)OPTIM_SGD && (int)PEVIT_OPTIM_ADAM ==
 // and the step alone is computed here in double and rounded to f32 once.
 extern "C" int pevit_optim_step(pevit_ctx* c, void* stream, int kind, const pevit_optim_group* groups, int n_groups, int step,
                                 float grad_scale, int flags) {
+    CHECK(refuse_infer(c, "optim_step"));
     if (!c || !c->params || !c->grads || !c->mom) { pevit_set_error("optim_step: parameters/momentum not set"); return -1; }
     if (kind != PEVIT_OPTIM_SGD && kind != PEVIT_OPTIM_ADAM && kind != PEVIT_OPTIM_ADAMW) {
         pevit_set_error("optim_step: unknown optimizer kind %d", kind); return -1;
@@ -261,11 +268,13 @@ static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_an
 }
 extern "C" int pevit_visual_forward(pevit_ctx* c, void* stream, const float* images, float* feat, int B,
                                     int save_for_backward) {
+    CHECK(refuse_infer(c, "visual_forward"));
     return visual_forward_impl(c, stream, images, 0, feat, B, save_for_backward, false, false);
 }
 // the same from uint8 pixels (B,3,R,R): the reference's ToTensor + Normalize run inside the patch gather (pevit_set_input_norm)
 extern "C" int pevit_visual_forward_u8(pevit_ctx* c, void* stream, const uint8_t* images, float* feat, int B,
                                        int save_for_backward) {
+    CHECK(refuse_infer(c, "visual_forward_u8"));
     CHECK(check_u8_input(c, "visual_forward_u8"));
     return visual_forward_impl(c, stream, images, 1, feat, B, save_for_backward, false, false);
 }
@@ -286,8 +295,9 @@ static int predict_impl(pevit_ctx* c, void* stream, const void* images, int u8, 
     a.feat = feat_or_null ? feat_or_null : at<float>(W, c->lay.w_feat); a.W = c->params + c->p_head_w; a.bias = c->params + c->p_head_b;
     // (training = 0: bn_fwd_kernel only reads the running statistics)
     a.running_mean = const_cast<float*>(running_mean); a.running_var = const_cast<float*>(running_var); a.training = 0;
-    a.ybn = at<float>(W, c->lay.w_ybn); a.rstd = at<float>(W, c->lay.w_bnrstd); a.logits = logits; a.dlogits = at<float>(W, c->lay.w_dlogits);
-    a.dybn = at<float>(W, c->lay.w_dybn); a.B = B; a.D = c->D; a.Cc = c->C;
+    a.ybn = at<float>(W, c->lay.w_ybn); a.rstd = at<float>(W, c->lay.w_bnrstd); a.logits = logits; a.B = B; a.D = c->D; a.Cc = c->C;
+    // (the forward-only launch touches neither; an inference-only context has no slot for them)
+    if (!c->infer_only) { a.dlogits = at<float>(W, c->lay.w_dlogits); a.dybn = at<float>(W, c->lay.w_dybn); }
     return pevit_launch_head(a, (hipStream_t)stream);
 }
 extern "C" int pevit_predict(pevit_ctx* c, void* stream, const float* images, const float* running_mean, const float* running_var,
@@ -346,6 +356,7 @@ extern "C" int pevit_zeroshot_u8(pevit_ctx* c, void* stream, const uint8_t* imag
 static int probe_check_ctx(const pevit_ctx* c, const char* who) {
     if (!c) { pevit_set_error("%s: null context", who); return -1; }
     CHECK(refuse_text(c, who));
+    CHECK(refuse_infer(c, who));
     if (c->d.method != PEVIT_NONE) {
         pevit_set_error("%s: the context's method is not PEVIT_NONE (the probe trains the head over a frozen tower; the adapter "
                         "methods train through pevit_train_forward_backward)", who);
@@ -410,6 +421,7 @@ extern "C" int pevit_probe_predict(pevit_ctx* c, void* stream, const pevit_probe
 
 // tokens (S,N) int64 -> features (S,D) f32                              model.py:1153-1168
 extern "C" int pevit_encode_text(pevit_ctx* c, void* stream, const int64_t* tokens, float* features, int S) {
+    CHECK(refuse_infer(c, "encode_text"));
     if (c && !c->text) { pevit_set_error("encode_text: this is an image context (pevit_ctx_create); text contexts come from pevit_text_create"); return -1; }
     CHECK(check_ready(c, S, "encode_text"));
     if (!tokens || !features) { pevit_set_error("encode_text: null argument"); return -1; }
@@ -449,6 +461,7 @@ extern "C" int pevit_encode_text(pevit_ctx* c, void* stream, const int64_t* toke
 // parallelism calls (L, L/2) then (L/2, 0) and all-reduces the first part's gradients while the second runs.
 extern "C" int pevit_visual_backward_part(pevit_ctx* c, void* stream, const float* dfeat, int B, int l_hi, int l_lo) {
     CHECK(refuse_text(c, "visual_backward"));
+    CHECK(refuse_infer(c, "visual_backward"));
     CHECK(check_ready(c, B, "visual_backward"));
     CHECK(check_saved(c, Saved::visual, B, -1, "visual_backward"));
     CHECK(check_range(c, l_lo, l_hi, "visual_backward", "layer"));
@@ -500,6 +513,7 @@ static int head_fb_impl(pevit_ctx* c, void* stream, const float* feat, const int
                         float* running_mean, float* running_var, int bn_training, float* logits, float* loss, float* dfeat, int B,
                         bool fused_step) {
     CHECK(refuse_text(c, "head_forward_backward"));
+    CHECK(refuse_infer(c, "head_forward_backward"));
     if (!c || !c->ws || !c->params || !c->grads) { pevit_set_error("head: context not ready"); return -1; }
     if (B <= 0 || B > c->max_batch) { pevit_set_error("head: batch %d outside [1,%d]", B, c->max_batch); return -1; }
     if (!feat || !running_mean || !running_var || !logits) { pevit_set_error("head: null argument"); return -1; }
@@ -536,6 +550,7 @@ extern "C" int pevit_head_forward_backward_bce(pevit_ctx* c, void* stream, const
                                                float* running_mean, float* running_var, int bn_training, float* logits,
                                                float* loss, float* dfeat, int B) {
     CHECK(refuse_text(c, "head_forward_backward_bce"));
+    CHECK(refuse_infer(c, "head_forward_backward_bce"));
     if (!targets) { pevit_set_error("head_bce: targets is null (the forward alone is pevit_head_forward_backward with no labels)"); return -1; }
     return head_fb_impl(c, stream, feat, nullptr, targets, running_mean, running_var, bn_training, logits, loss, dfeat, B, false);
 }
@@ -543,6 +558,7 @@ extern "C" int pevit_head_forward_backward_bce(pevit_ctx* c, void* stream, const
 static int train_fb_impl(pevit_ctx* c, void* stream, const void* images, int u8, const int64_t* labels, const float* targets,
                          float* running_mean, float* running_var, int bn_training, float* logits, float* loss, int B) {
     CHECK(refuse_text(c, "train_forward_backward"));
+    CHECK(refuse_infer(c, "train_forward_backward"));
     CHECK(check_ready(c, B, "train_forward_backward"));
     if (!labels == !targets) { pevit_set_error("train_forward_backward: exactly one of labels and targets must be given"); return -1; }
     const bool gate = c->step_gate != nullptr;          // with a gate the gradients are cleared behind it, inside the forward pass
@@ -563,6 +579,7 @@ extern "C" int pevit_train_forward_backward(pevit_ctx* c, void* stream, const fl
 extern "C" int pevit_train_forward_backward_u8(pevit_ctx* c, void* stream, const uint8_t* images, const int64_t* labels,
                                                float* running_mean, float* running_var, int bn_training, float* logits,
                                                float* loss, int B) {
+    CHECK(refuse_infer(c, "train_forward_backward_u8"));
     CHECK(check_u8_input(c, "train_forward_backward_u8"));
     return train_fb_impl(c, stream, images, 1, labels, nullptr, running_mean, running_var, bn_training, logits, loss, B);
 }
@@ -574,6 +591,7 @@ extern "C" int pevit_train_forward_backward_bce(pevit_ctx* c, void* stream, cons
 extern "C" int pevit_train_forward_backward_bce_u8(pevit_ctx* c, void* stream, const uint8_t* images, const float* targets,
                                                    float* running_mean, float* running_var, int bn_training, float* logits,
                                                    float* loss, int B) {
+    CHECK(refuse_infer(c, "train_forward_backward_bce_u8"));
     CHECK(check_u8_input(c, "train_forward_backward_bce_u8"));
     return train_fb_impl(c, stream, images, 1, nullptr, targets, running_mean, running_var, bn_training, logits, loss, B);
 }

@@ -9,8 +9,9 @@ static AdapterPanels panels(pevit_ctx* c, int l) {
     AdapterPanels p;
     p.w_aug_rows = c->fp8 ? at<bf16>(c->arena, b.wpan) : eadv(c, at<bf16>(c->arena, b.wqkv), (size_t)3 * c->E * c->E);
     p.ldw = c->E;
-    p.wT_aug_cols = eadv(c, at<bf16>(c->arena, b.wqkvT), 3 * (size_t)c->E);
-    p.ldwT = c->NQ;
+    // (an inference-only context has no wqkvT: the 64 columns go to its write-only panel, nobody reads them)
+    p.wT_aug_cols = c->infer_only ? at<bf16>(c->arena, b.tsink) : eadv(c, at<bf16>(c->arena, b.wqkvT), 3 * (size_t)c->E);
+    p.ldwT = c->infer_only ? 64 : c->NQ;
     p.q32 = at<float>(c->arena, b.q32);
     p.qT = at<bf16>(c->arena, b.qT);
     p.q16 = at<bf16>(c->arena, b.q16);
@@ -38,8 +39,9 @@ int prep_adapters(pevit_ctx* c, hipStream_t s) {
         CHECK(pevit_launch_prep_lora(a, s));
     } else if (post_mlp(c)) {
         const BlockArena& b0 = c->blk[0];
-        BottleneckPanels bp{at<bf16>(c->arena, b0.wd), at<bf16>(c->arena, b0.wdT), at<bf16>(c->arena, b0.wu),
-                            at<bf16>(c->arena, b0.wuT)};
+        // (an inference-only context has neither wdT nor wuT: both transposed stores go to its write-only panel, nobody reads them)
+        BottleneckPanels bp{at<bf16>(c->arena, b0.wd), at<bf16>(c->arena, c->infer_only ? b0.tsink : b0.wdT), at<bf16>(c->arena, b0.wu),
+                            at<bf16>(c->arena, c->infer_only ? b0.tsink : b0.wuT)};
         if (c->d.method == PEVIT_ADAPTER) {
             CHECK(pevit_launch_prep_adapter(lp + c->o_dw, lp + c->o_uw, bp, c->E, c->L, st, s, c->f32));
         } else {

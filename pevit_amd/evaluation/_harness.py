@@ -33,7 +33,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import _lib
+from .. import _lib, adapter_io
 from ..engine import OptimPlan, _group_hypers
 from ..optim import build_optimizer
 from . import clip_load
@@ -825,6 +825,13 @@ def train_task(classifier_cls, train_dataloader, test_dataloader, config, sweep_
     module's signatures; by default the loops above."""
     train_one_fn, validate_fn = train_one_fn or train_one, validate_fn or validate
     best_acc1 = 0
+    # TRAIN.SAVE_ADAPTER "best" | "last" (not a reference key; "" = off, and always off in sweep runs): keep the run's product, the
+    # adapter + head + BatchNorm statistics, as <OUTPUT_DIR>/adapter_<dataset>_<method>.pt (adapter_io)
+    save_adapter = "" if sweep_run else str((config.TRAIN.get("SAVE_ADAPTER", "") if hasattr(config.TRAIN, "get") else
+                                             getattr(config.TRAIN, "SAVE_ADAPTER", "")) or "")
+    if save_adapter not in ("", "best", "last"):
+        raise ValueError(f"TRAIN.SAVE_ADAPTER {save_adapter!r}: expected '', 'best' or 'last'")
+    snapshot = None
     with ordered_section():                                   # adapter / head initialisation draws from the process-wide generator
         model = classifier_cls(config, 0)
     n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
@@ -848,6 +855,8 @@ def train_task(classifier_cls, train_dataloader, test_dataloader, config, sweep_
     model_info["n_backbone_params"] = sum(p.numel() for p in model.backbone.parameters())
     model_info["n_params"] = sum(p.numel() for p in model.parameters())
 
+    if save_adapter:
+        adapter_io.refuse_merged(model, "TRAIN.SAVE_ADAPTER on")      # before the first epoch, not after it
     acc1 = 0.0
     for epoch in range(config.TRAIN.BEGIN_EPOCH, config.TRAIN.END_EPOCH):
         adjust_learning_rate(optimizer, epoch, config)
@@ -856,7 +865,15 @@ def train_task(classifier_cls, train_dataloader, test_dataloader, config, sweep_
         acc1, logits = validate_fn(test_dataloader, model, criterion, epoch, config, return_logits=True)
         if acc1 > best_acc1:
             model_info["best_logits"] = logits
+            if save_adapter == "best":                        # a CPU copy of a few MB at most
+                snapshot = adapter_io.adapter_state(model, **adapter_io.config_meta(config), epoch=int(epoch), score=float(acc1))
         best_acc1 = max(acc1, best_acc1)
+    if save_adapter == "last" and config.TRAIN.END_EPOCH > config.TRAIN.BEGIN_EPOCH:
+        snapshot = adapter_io.adapter_state(model, **adapter_io.config_meta(config), epoch=int(config.TRAIN.END_EPOCH) - 1, score=float(acc1))
+    if snapshot is not None:
+        name = f"adapter_{config.DATASET.DATASET}_{snapshot['meta']['method']}.pt"
+        model_info["adapter_file"] = adapter_io.write_adapter(snapshot, os.path.join(config.OUTPUT_DIR, name))
+        logging.info(f"=> adapter of epoch {snapshot['meta']['epoch']} written to {model_info['adapter_file']}")
 
     logging.info(f"=> Learning rate {config.TRAIN.LR}, L2 lambda {config.TRAIN.WD}: Best score: Acc@1 {best_acc1:.3f}")
     if sweep_run and config.TRAIN.SEARCH_RESULT_ON_LAST_EPOCH:

@@ -12,7 +12,12 @@ of the two routes are compared once per configuration (the tower bits are the sa
 --profile: additionally one batch per route under the engine's own per-launch events (HipEngine.profile_gemms(all_kernels=True)):
 per kernel kind / GEMM shape the launches, milliseconds and ALGORITHMIC bytes (profile.hip prof_close) of a whole forward.
 --one-pass ROUTE: nothing but a warm-up and one pass of ROUTE at batch 128 (the process to put under rocprofv3 --kernel-trace --stats).
-Prints one JSON object.  usage: python scripts/predict_rate.py [--steps 20] [--reps 3] [--profile] [--out FILE]"""
+--serving [--serving-route both|train|serving]: instead of the above, the serving leg (profiles/serving.md): ``HipEngine.predict``
+on a training context ("train") against ``serving.InferenceEngine.predict`` on an inference-only one ("serving") -- ViT-B/32, KAdaptation,
+100 classes, batches 128 and 32, REPS rounds each in alternation -- the arena / workspace bytes of both contexts as the library
+reports them for ViT-B/32, ViT-B/16 and ViT-L/14 at batches 32 and 128, and microseconds per ``use()``.  With one route only, that
+route alone is built and timed (a process per round, to alternate two builds of the library).
+Prints one JSON object.  usage: python scripts/predict_rate.py [--steps 20] [--reps 3] [--profile] [--serving] [--out FILE]"""
 import argparse
 import dataclasses
 import json
@@ -119,6 +124,88 @@ def profile(model, bs):
     return out
 
 
+def serving_sizes(lib):
+    """arena / workspace bytes of the training and the inference-only context, from the size queries (no allocation)"""
+    import ctypes as C
+    from pevit_amd import _lib
+    from pevit_amd.synth import ARCHS
+    out = {}
+    for name in ("ViT-B/32", "ViT-B/16", "ViT-L/14"):
+        a = ARCHS[name]
+        d = _lib.PevitDims(a.width, a.layers, a.patch, a.resolution, a.embed_dim, _lib.METHOD_IDS["kadaptation"], 4, 100, _lib.WEIGHT_FORMATS["bf16"])
+        row = {}
+        for kind, creator in (("train", "pevit_ctx_create"), ("serving", "pevit_infer_create")):
+            if not hasattr(lib, creator):
+                continue
+            ctx = C.c_void_p()
+            _lib.check(getattr(lib, creator)(C.byref(d), C.byref(ctx)), creator)
+            row[kind] = {"arena_bytes": lib.pevit_arena_bytes(ctx), "workspace_bytes_bs32": lib.pevit_workspace_bytes(ctx, 32),
+                         "workspace_bytes_bs128": lib.pevit_workspace_bytes(ctx, 128)}
+            lib.pevit_ctx_destroy(ctx)
+        out[name] = row
+    return out
+
+
+def serving_leg(steps, reps, route):
+    from pevit_amd import _lib
+    from pevit_amd.engine import HipEngine, adapter_param_spec
+    from pevit_amd.synth import ARCHS, randomize_adapters, synth_state_dict
+    dev = torch.device("cuda", 0)
+    arch, method, classes = ARCHS["ViT-B/32"], "kadaptation", 100
+    sd = {k: v for k, v in synth_state_dict(arch, seed=2, text_tower=False).items() if k.startswith("visual.")}
+    ad = [(n, torch.zeros(s)) for n, s, _ in adapter_param_spec(method, arch.width, arch.layers)]
+    randomize_adapters(ad, seed=3)
+    sd.update(dict(ad))
+    eng = HipEngine(arch, method, classes, 128)
+    eng.load_state_dict(sd)
+    g = torch.Generator().manual_seed(5)
+    v = eng.param_views()
+    with torch.no_grad():
+        v["layers.0.weight"].copy_(((torch.rand((classes, 512), generator=g) * 2 - 1) / 512 ** 0.5).cuda())
+        eng.running_var.copy_((0.5 + torch.rand(512, generator=g)).cuda())
+    routes, out = {}, {"sizes": serving_sizes(eng.lib)}
+    if route in ("both", "serving"):
+        from pevit_amd import adapter_io
+        from pevit_amd.serving import InferenceEngine
+        ckpt = adapter_io.engine_adapter_state(eng, sd)
+        inf = InferenceEngine(arch, method, classes, 128)
+        inf.load_backbone(sd)
+        for name in ("a", "b"):
+            inf.add_adapter(name, ckpt)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i in range(2000):
+            inf.use("ab"[i & 1])
+        out["use_us"] = round((time.perf_counter() - t0) / 2000 * 1e6, 3)
+        routes["serving"] = inf.predict
+        out["bound"] = {"train": {"arena_bytes": eng.arena.numel(), "workspace_bytes": eng.workspace.numel()},
+                        "serving": {"arena_bytes": inf.arena_bytes, "workspace_bytes": inf.workspace_bytes}}
+    if route in ("both", "train"):
+        routes["train"] = eng.predict
+    else:
+        del eng
+        torch.cuda.empty_cache()
+    for bs in (128, 32):
+        x = torch.randn((steps * bs, 3, 224, 224), generator=torch.Generator().manual_seed(0)).to(dev)
+        batches = [x[i * bs:(i + 1) * bs] for i in range(steps)]
+        if len(routes) == 2:
+            out[f"bs{bs}_bit_identical"] = bool(torch.equal(routes["train"](batches[0]), routes["serving"](batches[0])))
+        for r in routes.values():
+            run_pass(r, batches)                                  # warm-up pass
+        wall = {r: [] for r in routes}
+        order = list(routes)
+        for rep in range(reps):
+            for r in (order if rep % 2 == 0 else order[::-1]):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                run_pass(routes[r], batches)
+                torch.cuda.synchronize(dev)
+                wall[r].append(round(steps * bs / (time.perf_counter() - t0), 1))
+        out[f"bs{bs}_images_per_s_rounds"] = wall
+        del x, batches
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -126,7 +213,16 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--one-pass", choices=["module", "predict"], default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--serving", action="store_true")
+    ap.add_argument("--serving-route", choices=["both", "train", "serving"], default="both")
     args = ap.parse_args()
+    if args.serving:
+        s = json.dumps(serving_leg(args.steps, args.reps, args.serving_route), indent=1)
+        print(s)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(s + "\n")
+        return
     from pevit_amd.config import default_config
     from pevit_amd.evaluation import _harness
     from pevit_amd.synth import ARCHS, synth_state_dict
