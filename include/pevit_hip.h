@@ -477,6 +477,23 @@ int pevit_op_delta_add(void* stream, void* qbuf, void* vbuf, const float* t, con
 int pevit_op_attn_fwd_delta(void* stream, void* q, const void* k, void* v, const float* t, const void* q16_bf16, const float* bias,
                             float ascale, void* out, int ldo, float* lse, int B, int H, int N);
 int pevit_op_attn_delta_hpw(int B, int H, int N);
+/* The segmented forms of the two kernels above (pevit_segments.h: pevit_predict_segments), inference only.  The B images are split
+ * into nseg <= 16 contiguous segments that tile [0, B) in order; the raw reshape of the delta works INSIDE a segment (local reference
+ * row rr: token rr / count of image first + rr % count) with that segment's bf16 Q panel, bias (or NULL) and its 64 columns
+ * [tcol, tcol + 64) of t, whose rows are tpitch floats apart (tpitch and tcol multiples of 64).  Each segment of the output is, bit
+ * for bit, what the unsegmented entry gives on that segment's slices alone.
+ *   delta_add_seg:      q and v (B*H, N, 64) are rewritten in place; pevit_op_attn_fwd follows unchanged
+ *   attn_fwd_delta_seg: one launch where pevit_op_attn_delta_hpw(B, H, N) > 0; q and v are only read; one workgroup per run of heads
+ *                       inside a segment, so the grid is sum_s ceil(count_s * H / 6) */
+typedef struct pevit_op_segment {
+    int32_t first, count, tcol;
+    const void* q16_bf16;
+    const float* bias;
+} pevit_op_segment;
+int pevit_op_delta_add_seg(void* stream, void* qbuf, void* vbuf, const float* t, int tpitch, float ascale, int B, int H, int N,
+                           int nseg, const pevit_op_segment* segs);
+int pevit_op_attn_fwd_delta_seg(void* stream, const void* q, const void* k, const void* v, const float* t, int tpitch, float ascale,
+                                void* out, int ldo, int B, int H, int N, int nseg, const pevit_op_segment* segs);
 /* softmax probabilities P = exp(q k^T - lse) (attn_probs.hip): q, k (B*H, N, 64) bf16 as pevit_op_attn_fwd takes them, lse as it
  * wrote it; average = 1: out (B, N, N) f32, the mean over the H heads; 0: out (B, H, N, N) f32.  N <= 384. */
 int pevit_op_attn_probs(void* stream, const void* q, const void* k, const float* lse, float* out, int B, int H, int N, int average);
@@ -656,7 +673,8 @@ int pevit_op_scale_f32(void* stream, float* p, size_t n, float scale);
 int pevit_op_text_embed(void* stream, const int64_t* tokens, const float* table, const float* pos, float* x, int S, int N, int E, int V);
 int pevit_op_text_eot_gather(void* stream, const int64_t* tokens, const float* x, float* rows_out, int S, int N, int E);
 /* measurement only: device buffer of 8 uint64 per workgroup that the next pevit_op_attn_fwd_delta launches fill with s_memtime
- * stamps at their phase boundaries (NULL switches it off) */
+ * stamps at their phase boundaries (NULL switches it off).  The segmented launches (pevit_op_attn_fwd_delta_seg, every call on a
+ * multi-slot context) take no stamps: they may have more workgroups than ceil(B H / 6). */
 int pevit_debug_timeline(void* buf);
 /* measurement only: `workgroups` 256-thread workgroups with `lds_bytes` of LDS each that keep their CU slots for `microseconds`
  * on `stream` -- what the kernels of an overlapped RCCL all-reduce do to the one-tile-per-CU GEMMs (scripts/r4_coresidency.py) */
@@ -760,6 +778,9 @@ int pevit_set_external_poison(pevit_ctx* ctx, const unsigned* device_word);
  * cleared.  Recorded by the caller behind the previous step's gradient exchange + pevit_sgd_step, which may then run on another
  * stream, under the next step's stem (engine.HipEngine dp_exchange_mode = "pipelined").  NULL detaches it. */
 int pevit_set_step_gate(pevit_ctx* ctx, void* hip_event);
+
+/* segmented predict on a multi-slot inference context: its four entry points */
+#include "pevit_segments.h"
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,16 @@ class PevitAdapterBwdArgs(C.Structure):
                 [(n, C.c_int32) for n in ("act_kind", "T", "E", "tn_blocks")])
 
 
+class PevitSegment(C.Structure):
+    """pevit_segment of include/pevit_segments.h: one segment of pevit_predict_segments"""
+    _fields_ = [(n, C.c_int32) for n in ("first", "count", "slot")] + [(n, c_void_p) for n in ("running_mean", "running_var", "logits", "features")]
+
+
+class PevitOpSegment(C.Structure):
+    """pevit_op_segment of include/pevit_hip.h (the test-only pevit_op_delta_add_seg / pevit_op_attn_fwd_delta_seg)"""
+    _fields_ = [(n, C.c_int32) for n in ("first", "count", "tcol")] + [(n, c_void_p) for n in ("q16", "bias")]
+
+
 LOWRANK_FORMS = {"u": 0, "grad": 1, "combo": 2, "u_f32": 3, "grad_f32": 4}       # enum pevit_lowrank_form
 
 
@@ -222,6 +232,8 @@ SIGNATURES = {
     "pevit_op_delta_add": (c_int, [P, P, P, P, P, P, c_float, c_int, c_int, c_int]),
     "pevit_op_attn_fwd_delta": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int, P, c_int, c_int, c_int]),
     "pevit_op_attn_delta_hpw": (c_int, [c_int, c_int, c_int]),
+    "pevit_op_delta_add_seg": (c_int, [P, P, P, P, c_int, c_float, c_int, c_int, c_int, c_int, C.POINTER(PevitOpSegment)]),
+    "pevit_op_attn_fwd_delta_seg": (c_int, [P, P, P, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, c_int, C.POINTER(PevitOpSegment)]),
     "pevit_op_attn_probs": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int]),
     # test-only forms (csrc/verify.hip; the GEMM ones csrc/ops.hip): the step-only members of the launchers' parameter structs
     "pevit_op_ln_fwd_ex": (c_int, [P, P, P, P, c_int, c_int, c_size_t, P, P, P, P, P]),
@@ -283,6 +295,15 @@ SIGNATURES = {
     "pevit_streamk_status": (c_int, [P, P, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
 }
 
+# include/pevit_segments.h (which pevit_hip.h includes): the entry points of a multi-slot inference context, a table of their own
+SEGMENT_SIGNATURES = {
+    "pevit_infer_create_slots": (c_int, [C.POINTER(PevitDims), c_int, C.POINTER(c_void_p)]),
+    "pevit_load_adapter_slot": (c_int, [P, P, c_int, P, c_int]),
+    "pevit_predict_segments": (c_int, [P, P, P, c_int, c_int, C.POINTER(PevitSegment)]),
+    "pevit_predict_segments_u8": (c_int, [P, P, P, c_int, c_int, C.POINTER(PevitSegment)]),
+}
+MAX_SLOTS, MAX_SEGMENTS = 8, 16          # PEVIT_MAX_SLOTS, PEVIT_MAX_SEGMENTS_PER_CALL
+
 _lib = None
 
 
@@ -307,7 +328,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

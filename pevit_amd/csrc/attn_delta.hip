@@ -14,6 +14,8 @@
 //
 // Results are bit-identical to the two-kernel path (tests/test_gpu_ops2.py): same roundings (q' = bf16(q + delta)), same
 // MFMA order per 16-query tile.
+#include <string.h>
+
 #include "common.h"
 #include "kernels.h"
 #include "mfma_frag.h"
@@ -30,20 +32,35 @@ namespace {
 // HC, NC: heads and tokens per image as compile-time constants (0 = the runtime arguments).  Round 5: 20.5 -> 19.7 us at H = 12,
 // N = 50 (scripts/experiments/gpu_r5_fixn.sh) -- bounds, row strides and the head / row arithmetic fold.
 // SAVE = false: the inference form -- q' and v' stay in LDS and lse is not stored (q and v are only read); the same `out`.
-template <int HPW, int NW, int PER, int HC, int NC, bool SAVE = true>
+// SEG = SegTable: the segmented inference form (kernels.h).  The grid is sum_s ceil(count_s * H / HPW): a workgroup looks up its
+// segment and its run INSIDE it, then moves every operand to the segment's first image and takes the segment's image count for B,
+// so that everything below -- the raw reshape included -- is the unsegmented kernel on that segment alone.  A run never crosses a
+// segment (with H = 2 a run of six heads is three images: numbered globally it would put reference rows of two segments, with two
+// Q panels, into one MFMA); the last run of a segment is partial, as the last run of a batch is.
+template <int HPW, int NW, int PER, int HC, int NC, bool SAVE = true, class SEG = NoSegments>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restrict__ q, const bf16* __restrict__ k, bf16* __restrict__ v,
                                                                  const float* __restrict__ t, const bf16* __restrict__ q16,
                                                                  const float* __restrict__ bias, float ascale,
                                                                  bf16* __restrict__ out, int ldo, float* __restrict__ lse,
-                                                                 int B, int H_rt, int N_rt, unsigned long long* __restrict__ tl) {
+                                                                 int B, int H_rt, int N_rt, unsigned long long* __restrict__ tl, SEG sg) {
     const int N = NC ? NC : N_rt, H = HC ? HC : H_rt;
+    int blk = blockIdx.x;                                 // the run of heads, counted inside the segment
+    int tp = 64;                                          // row pitch of t (floats)
+    if constexpr (SEG::on) {
+        static_assert(!SAVE, "the segmented form is inference only");
+        const SegPick sp = seg_pick(sg, blockIdx.x);
+        const size_t img = (size_t)sp.first * N;          // rows in front of the segment, in every [T][.] buffer
+        blk = sp.wg; B = sp.count; tp = sg.tpitch;
+        q += img * H * 64; k += img * H * 64; v += img * H * 64; out += img * ldo;
+        t += img * tp + sp.tcol; q16 = sp.q16; bias = sp.bias;
+    }
     constexpr int NT = 64 * NW, LDR = AFD_LDR;
     // measurement only (pevit_debug_timeline): s_memtime of wave 0 of every workgroup at the phase boundaries
     auto stamp = [&](int i) { if (tl && threadIdx.x == 0) tl[(size_t)blockIdx.x * 8 + i] = __builtin_amdgcn_s_memtime(); };
     stamp(0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int E = H * 64, T = B * N, BH = B * H;
-    const int bh0 = blockIdx.x * HPW;
+    const int bh0 = blk * HPW;
     const int nh = min(HPW, BH - bh0);
     const int rows = nh * N;                              // head rows of this run
     const int prow = (HPW - 1) * N + (N + 16 > 64 ? N + 16 : 64);   // LDS rows per tensor: the last head's 64-row tile stays inside
@@ -82,7 +99,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
     for (int kq = 0; kq < 2; ++kq) {
         const int rr = min(rr0 + 16 * kq + c16, T - 1);
         const int n = rr / B, b = rr - n * B;                   // row_of_ref (mfma_frag.h) in 64-bit: the address arithmetic this kernel was tuned with
-        const float* src = t + ((size_t)b * N + n) * 64 + which * 32 + 8 * g;
+        const float* src = t + ((size_t)b * N + n) * tp + which * 32 + 8 * g;
         ta[kq][0] = *reinterpret_cast<const float4*>(src); ta[kq][1] = *reinterpret_cast<const float4*>(src + 4);
     }
 #pragma unroll
@@ -251,12 +268,22 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_delta_kernel(bf16* __restric
 
 unsigned long long* g_timeline = nullptr;
 
+template <int HPW, int NW, int PER, int HC, int NC>
+int launch_fwd_delta_seg(const AttnSiteSegArgs& a, const SegTable& tab, int runs, int bytes, hipStream_t s) {
+    constexpr auto kern = attn_fwd_delta_kernel<HPW, NW, PER, HC, NC, false, SegTable>;
+    if (reserve_lds<kern, 160 * 1024>("attn_fwd_delta_seg")) return -1;
+    hipLaunchKernelGGL(kern, dim3(runs), dim3(64 * NW), bytes, s, a.q, a.k, a.v, a.t, (const bf16*)nullptr, (const float*)nullptr, a.ascale,
+                       a.out, a.ldo, (float*)nullptr, a.B, a.H, a.N, (unsigned long long*)nullptr, tab);     // no timeline: its buffer is sized for ceil(B H / HPW) workgroups, a segmented launch may have more
+    LAUNCH_OK("attn_fwd_delta_kernel (segmented)");
+    return 0;
+}
+
 template <int HPW, int NW, int PER, int HC, int NC, bool SAVE = true>
 int launch_fwd_delta(const AttnFwdDeltaArgs& a, int bytes, hipStream_t s) {
     constexpr auto kern = attn_fwd_delta_kernel<HPW, NW, PER, HC, NC, SAVE>;
     if (reserve_lds<kern, 160 * 1024>("attn_fwd_delta")) return -1;
     hipLaunchKernelGGL(kern, dim3(ceil_div(a.B * a.H, HPW)), dim3(64 * NW), bytes, s, a.q, a.k, a.v, a.t, a.q16, a.bias, a.ascale, a.out, a.ldo,
-                       a.lse, a.B, a.H, a.N, g_timeline);
+                       a.lse, a.B, a.H, a.N, g_timeline, NoSegments{});
     LAUNCH_OK("attn_fwd_delta_kernel");
     return 0;
 }
@@ -284,4 +311,42 @@ int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s) {
     if (!a.nosave && !a.lse) { pevit_set_error("attn_fwd_delta: lse is null (only the nosave form takes that)"); return -1; }
     if (H == 12 && N == 50) return a.nosave ? launch_fwd_delta<HPW, NW, PER, 12, 50, false>(a, bytes, s) : launch_fwd_delta<HPW, NW, PER, 12, 50>(a, bytes, s);
     return a.nosave ? launch_fwd_delta<HPW, NW, PER, 0, 0, false>(a, bytes, s) : launch_fwd_delta<HPW, NW, PER, 0, 0>(a, bytes, s);
+}
+
+// what the two segmented launchers check alike, before anything is launched
+int pevit_seg_table(const AttnSiteSegArgs& a, const char* who, SegTable& tab) {
+    if (a.nseg < 1 || a.nseg > PEVIT_MAX_SEGMENTS) { pevit_set_error("%s: %d segments outside [1,%d]", who, a.nseg, PEVIT_MAX_SEGMENTS); return -1; }
+    if (a.tpitch < 64 || a.tpitch % 64) { pevit_set_error("%s: the row pitch %d of t must be a positive multiple of 64", who, a.tpitch); return -1; }
+    memset(&tab, 0, sizeof(tab));
+    tab.nseg = a.nseg; tab.tpitch = a.tpitch;
+    int next = 0;
+    for (int i = 0; i < a.nseg; ++i) {
+        const AttnSegment& g = a.seg[i];
+        if (g.first != next || g.count < 1) {
+            pevit_set_error("%s: segment %d is images [%d, %d): the segments must tile [0, %d) in order, one image at least each", who, i,
+                            g.first, g.first + g.count, a.B);
+            return -1;
+        }
+        if (g.tcol < 0 || g.tcol % 64 || g.tcol + 64 > a.tpitch) { pevit_set_error("%s: segment %d: t columns [%d, %d) outside the pitch %d", who, i, g.tcol, g.tcol + 64, a.tpitch); return -1; }
+        if (!g.q16) { pevit_set_error("%s: segment %d has no Q panel", who, i); return -1; }
+        next += g.count;
+        tab.first[i] = g.first; tab.count[i] = g.count; tab.tcol[i] = g.tcol; tab.q16[i] = g.q16; tab.bias[i] = g.bias;
+    }
+    if (next != a.B) { pevit_set_error("%s: the segments cover %d of %d images", who, next, a.B); return -1; }
+    return 0;
+}
+
+int pevit_launch_attn_fwd_delta_seg(const AttnSiteSegArgs& a, hipStream_t s) {
+    constexpr int HPW = 6, NW = 12, PER = 4;
+    const int H = a.H, N = a.N;
+    if (pevit_attn_delta_hpw(a.B, H, N) != HPW) { pevit_set_error("attn_fwd_delta_seg: no fused form for H=%d N=%d", H, N); return -1; }
+    if (a.ldo % 8) { pevit_set_error("attn_fwd_delta_seg: ldo must be a multiple of 8"); return -1; }
+    const int bytes = 3 * ((HPW - 1) * N + (N + 16 > 64 ? N + 16 : 64)) * AFD_LDR * 2;
+    if (bytes > 160 * 1024) { pevit_set_error("attn_fwd_delta_seg: %d bytes of LDS", bytes); return -1; }
+    SegTable tab;
+    if (pevit_seg_table(a, "attn_fwd_delta_seg", tab)) return -1;
+    int runs = 0;
+    for (int i = 0; i < a.nseg; ++i) { tab.wg0[i] = runs; runs += ceil_div(a.seg[i].count * H, HPW); }
+    if (H == 12 && N == 50) return launch_fwd_delta_seg<HPW, NW, PER, 12, 50>(a, tab, runs, bytes, s);
+    return launch_fwd_delta_seg<HPW, NW, PER, 0, 0>(a, tab, runs, bytes, s);
 }

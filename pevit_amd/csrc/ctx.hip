@@ -72,7 +72,7 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
         }
         s.xn1 = cv.take(T * E * es);
         s.qkv = cv.take(3 * T * E * es);
-        s.t = cv.take(T * 64 * 4);
+        s.t = cv.take(T * 64 * 4 * (c->slots ? c->slots + 1 : 1));      // (multi-slot context: the columns of every slot + the single-adapter calls')
         s.lse = cv.take((size_t)B * c->H * c->N * 4);
         s.attn_out = cv.take(T * E * es);
         if (!infer) s.h = cv.take(T * 4 * E * es);
@@ -204,6 +204,7 @@ static void carve_block_arena(pevit_ctx* c, Carver& cv) {
         b.bqkv = cv.take(3 * E * 4); b.bo = cv.take(E * 4); b.bfc = cv.take(4 * E * 4); b.bpr = cv.take(E * 4);
         b.ln1w = cv.take(E * 4); b.ln1b = cv.take(E * 4); b.ln2w = cv.take(E * 4); b.ln2b = cv.take(E * 4);
         b.q32 = cv.take(E * 64 * 4); b.qT = cv.take(64 * E * c->es); b.q16 = cv.take(E * 64 * 2);
+        b.q16s = c->slots ? cv.take(c->slots * q16_slot_bytes(c)) : 0;
         if (c->infer_only) { b.wd = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); continue; }
         b.wd = cv.take(64 * E * c->es); b.wdT = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); b.wuT = cv.take(64 * E * c->es);
     }
@@ -258,9 +259,10 @@ using namespace pevit_host;
 // ------------------------------------------------------------------------------------
 // what pevit_ctx_create and pevit_infer_create share: the checks of the dims (errors under the caller's name `who`), the arena and the
 // flat parameter layout.  No HIP call: sizes only.
-static int create_image_ctx(const pevit_dims* dims, pevit_ctx** out, bool infer_only, const char* who) {
+static int create_image_ctx(const pevit_dims* dims, pevit_ctx** out, bool infer_only, const char* who, int slots = 0) {
     if (!dims || !out) { pevit_set_error("%s: null argument", who); return -1; }
     const pevit_dims d = *dims;
+    if (slots < 0 || slots > PEVIT_MAX_SLOTS) { pevit_set_error("%s: %d slots outside [1,%d]", who, slots, PEVIT_MAX_SLOTS); return -1; }
     if (d.width <= 0 || d.width % 128 != 0 || d.width > 1024) {
         pevit_set_error("%s: width %d must be a multiple of 128 in (0,1024]", who, d.width); return -1;
     }
@@ -289,7 +291,8 @@ static int create_image_ctx(const pevit_dims* dims, pevit_ctx** out, bool infer_
     const int grid = d.resolution / d.patch;
     c->G2 = grid * grid; c->N = c->G2 + 1; c->D = d.out_dim; c->C = d.num_classes;
     c->Kpatch = (int)align_up((size_t)3 * d.patch * d.patch, 64);
-    c->NQ = 3 * c->E + 64; c->NQpad = (int)align_up((size_t)c->NQ, 128);
+    c->slots = slots;
+    c->NQ = 3 * c->E + 64 * (slots + 1); c->NQpad = (int)align_up((size_t)c->NQ, 128);
     c->ascale = d.method == PEVIT_LORA ? 128.0f / (float)d.lora_rank : 160.0f;
     c->fp8act = d.weight_format == PEVIT_W_FP8_ACT;
     c->fp8 = d.weight_format == PEVIT_W_FP8_E4M3 || c->fp8act;
@@ -346,6 +349,40 @@ extern "C" int pevit_ctx_create(const pevit_dims* dims, pevit_ctx** out) { retur
 // An image context that can only infer (include/pevit_hip.h): the arena without the transposed copies, the third workspace layout
 // (layout_workspace), parameters through pevit_set_infer_params.  dims->num_classes is the largest head it will serve.
 extern "C" int pevit_infer_create(const pevit_dims* dims, pevit_ctx** out) { return create_image_ctx(dims, out, true, "infer_create"); }
+
+// The same with `slots` resident adapters for pevit_predict_segments (include/pevit_segments.h): per layer 64 more rows of wqkv and
+// one more Q panel per slot, 64 more f32 columns of t per slot and token.  What the segmented attention site was not built for is
+// refused by name; with one slot such dims give the context of pevit_infer_create.
+extern "C" int pevit_infer_create_slots(const pevit_dims* dims, int slots, pevit_ctx** out) {
+    const char* who = "infer_create_slots";
+    if (!dims || !out) { pevit_set_error("%s: null argument", who); return -1; }
+    if (slots < 1 || slots > PEVIT_MAX_SLOTS) { pevit_set_error("%s: %d slots outside [1,%d]", who, slots, PEVIT_MAX_SLOTS); return -1; }
+    const char* why = nullptr;
+    if (dims->method == PEVIT_ADAPTER || dims->method == PEVIT_COMPACTER)
+        why = "the post-MLP methods (Adapter, Compacter) are not served by segments: the 32-row blocks of their kernels straddle segments";
+    else if (dims->method == PEVIT_NONE) why = "method none has no adapter to keep in a slot";
+    else if (dims->weight_format == PEVIT_W_FP8_E4M3 || dims->weight_format == PEVIT_W_FP8_ACT)
+        why = "the fp8 weight formats keep the adapter rows outside the QKV product; segments are built for bf16";
+    else if (dims->weight_format == PEVIT_W_F32_VERIFY) why = "the f32 verification mode has no segmented kernels";
+    if (why && slots > 1) { pevit_set_error("%s: %d slots: %s", who, slots, why); return -1; }
+    return create_image_ctx(dims, out, true, who, why ? 0 : slots);
+}
+
+// Make `params` (the flat buffer of pevit_set_infer_params) resident in a slot: its bf16 panels are built here, once, by the kernel
+// the walk launches per call for the selected adapter; the pointer is kept for the delta bias and the head.
+extern "C" int pevit_load_adapter_slot(pevit_ctx* c, void* stream, int slot, const float* params, int num_classes) {
+    if (!c || !params) { pevit_set_error("load_adapter_slot: null argument"); return -1; }
+    if (!c->slots) { pevit_set_error("load_adapter_slot: this context has no adapter slots (pevit_infer_create_slots)"); return -1; }
+    if (!c->arena) { pevit_set_error("load_adapter_slot: context not bound"); return -1; }
+    if (slot < 0 || slot >= c->slots) { pevit_set_error("load_adapter_slot: slot %d outside [0,%d)", slot, c->slots); return -1; }
+    if (num_classes < 1 || num_classes > c->d.num_classes) {
+        pevit_set_error("load_adapter_slot: num_classes %d outside [1,%d] of the context", num_classes, c->d.num_classes); return -1;
+    }
+    c->slot_params[slot] = nullptr;
+    CHECK(prep_adapters(c, (hipStream_t)stream, slot, params));
+    c->slot_params[slot] = params; c->slot_classes[slot] = num_classes;
+    return 0;
+}
 
 // The CLIP text tower as a context: the block arena of pevit_ctx_create (method PEVIT_NONE) and, in place of the image stem, the f32
 // token-embedding table, the positional embedding, ln_final and text_projection^T.  No HIP call: sizes only.
@@ -548,6 +585,7 @@ extern "C" int pevit_load_block(pevit_ctx* c, void* stream, int l, const float* 
     HIP_OK(hipMemsetAsync(A + b.q32, 0, E * 64 * 4, s));
     HIP_OK(hipMemsetAsync(A + b.qT, 0, 64 * E * c->es, s));
     HIP_OK(hipMemsetAsync(A + b.q16, 0, E * 64 * 2, s));
+    for (int i = 0; i < c->slots; ++i) c->slot_params[i] = nullptr;       // (the rows of every slot went with the wqkv memset)
     return 0;
 }
 

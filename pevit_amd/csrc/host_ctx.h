@@ -39,6 +39,7 @@ struct BlockArena {        // byte offsets inside the weight arena, one per laye
     size_t wpan;                  // fp8 weights only: the 64 adapter rows P_q^T | P_v^T (bf16) of the separate t = xn P product
     size_t sqkv, so, sfc, spr;    // fp8 weights only: per-output-channel scales (f32, powers of two)
     size_t tsink;                 // inference-only contexts: [E][64] write-only panel that takes the transposed stores of the prep kernels
+    size_t q16s;                  // multi-slot contexts: the [E][64] bf16 Q panels of the slots, q16_slot_bytes apart (q16: the single-adapter calls')
 };
 
 struct LayerSaved {        // byte offsets inside the workspace, one per layer (kept for backward)
@@ -72,6 +73,7 @@ struct StepPlan {
     bool dx_stored = false;      // dX GEMMs hand the LN-input gradient to LayerNorm backward in the storage type
     bool lowrank_combo = false;  // u + dQ + d bias of a layer and the dP of the layer before it as one launch
     bool lowrank_xcd = false;    // lowrank_grad: XCD-contiguous workgroup order
+    bool segments = false;       // segmented call (pevit_predict_segments): the attention site per segment on the slots' panels, no prep launch
     bool infer = false;          // inference walk (pevit_predict): the kernel forms that store nothing for a backward pass, one set of activation slots for all layers
 };
 
@@ -96,13 +98,21 @@ struct AttnGradWalk {
 struct pevit_ctx {
     pevit_dims d;
     int E, L, H, N, P, R, D, C, G2, Kpatch;
-    int NQ, NQpad;            // 3E+64 and its multiple-of-128 padding
+    int NQ, NQpad;            // 3E+64 (multi-slot context: 3E + 64 (slots + 1)) and its multiple-of-128 padding
     bool fp8 = false;         // frozen block weights as e4m3 codes + per-channel scales (fp8.hip)
     bool fp8act = false;      // ... and fp8 A operands in the forward frozen products (PEVIT_W_FP8_ACT)
     bool f32 = false;         // f32-class verification mode: every bf16-declared buffer holds f32 (verify.hip)
     bool text = false;        // CLIP text tower (pevit_text_create): N = context_length, inference only, pevit_encode_text is its one forward
     bool causal = false;      // ... its attention is causal (attn_core_fwd passes this to the attention launch)
     bool infer_only = false;  // pevit_infer_create: no transposed weight copies, the third workspace layout, no gradients; runs the inference walk only
+    // multi-slot context (pevit_infer_create_slots; 0: none).  Rows [3E + 64 s, + 64) of wqkv hold slot s's P rows, the rows behind
+    // the last slot those of the single-adapter calls, which prep_adapters rebuilds per call: NQ = 3E + 64 (slots + 1) covers them,
+    // a segmented call's product stops at 3E + 64 slots
+    int slots = 0;
+    const float* slot_params[PEVIT_MAX_SLOTS] = {};     // pevit_load_adapter_slot: the flat buffer of each slot (null: not loaded) ...
+    int slot_classes[PEVIT_MAX_SLOTS] = {};             // ... and its class count
+    int nseg = 0;                                       // the segments of the segmented call in flight
+    pevit_segment segs[PEVIT_MAX_SEGMENTS_PER_CALL] = {};
     int V = 0;                // ... vocabulary size (rows of the token-embedding table)
     size_t a_tok = 0;         // ... arena offset of the f32 token-embedding table [V][E]
     size_t es = 2;            // bytes per element of those buffers
@@ -162,6 +172,8 @@ namespace pevit_host __attribute__((visibility("hidden"))) {
 inline bool attention_site(const pevit_ctx* c) {
     return c->d.method == PEVIT_KADAPTATION || c->d.method == PEVIT_LORA;
 }
+// bytes between the Q panels of two slots of a layer
+inline size_t q16_slot_bytes(const pevit_ctx* c) { return align_up((size_t)c->E * 64 * 2, 256); }
 inline bool post_mlp(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER || c->d.method == PEVIT_COMPACTER; }
 // activation of the post-MLP bottleneck as the fused kernels take it: 0 = ReLU (Adapter), 1 = gelu_new (Compacter)
 inline int act_kind(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER ? 0 : 1; }
@@ -187,7 +199,7 @@ void prof_close(pevit_ctx* c, hipStream_t s, int slot, double flops, double byte
 int gemm(pevit_ctx* c, int epi, const GemmParams& p_in, hipStream_t s);
 
 // ---- walk.hip ----
-int prep_adapters(pevit_ctx* c, hipStream_t s);
+int prep_adapters(pevit_ctx* c, hipStream_t s, int slot = -1, const float* params = nullptr);
 int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, unsigned char* a8, unsigned char* attn8);
 int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool cls_only, int l_lo = 0, int l_hi = -1);
 int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, bool cls, AttnGradWalk& w);

@@ -148,7 +148,42 @@ struct AttnFwdDeltaArgs {
 };
 int pevit_launch_attn_fwd_delta(const AttnFwdDeltaArgs& a, hipStream_t s);
 
-void pevit_attn_delta_set_timeline(void* buf);      // measurement only: 8 s_memtime stamps per workgroup of the next fused launches (null = off)
+// ---- segmented forms of the attention site (pevit_predict_segments): the batch is split into contiguous segments of images, and
+// the raw reshape of the delta works INSIDE each segment (local reference row rr: token rr / count of image first + rr % count), with
+// that segment's Q panel, bias and 64 columns of t.  Inference only: q and v are only read by the fused form.
+constexpr int PEVIT_MAX_SEGMENTS = 16;
+struct AttnSegment {
+    int first = 0, count = 0;           // images [first, first + count) of the batch
+    int tcol = 0;                       // first of this segment's 64 columns of t
+    const bf16* q16 = nullptr;          // its [E][64] bf16 panel of Q
+    const float* bias = nullptr;        // its delta bias [E], or null
+};
+struct AttnSiteSegArgs {
+    bf16* q = nullptr; const bf16* k = nullptr; bf16* v = nullptr;     // head layout, all B images
+    const float* t = nullptr; int tpitch = 64;                         // [B*N][tpitch] f32
+    float ascale = 0.f;
+    bf16* out = nullptr; int ldo = 0;                                  // (the fused form only)
+    int B = 0, H = 0, N = 0;
+    int nseg = 0; AttnSegment seg[PEVIT_MAX_SEGMENTS];
+};
+// the kernels' view, passed by value: wg0[s] = first workgroup of segment s (a run of heads, or a group of reference rows, never
+// crosses a segment).  Entries behind nseg are zero.  NoSegments is the empty table of the unsegmented instances: every use of the
+// table sits under `if constexpr (SEG::on)`, so those instances keep their code.
+struct NoSegments { static constexpr bool on = false; };
+struct SegTable {
+    static constexpr bool on = true;
+    int nseg, tpitch;
+    int first[PEVIT_MAX_SEGMENTS], count[PEVIT_MAX_SEGMENTS], tcol[PEVIT_MAX_SEGMENTS], wg0[PEVIT_MAX_SEGMENTS];
+    const bf16* q16[PEVIT_MAX_SEGMENTS]; const float* bias[PEVIT_MAX_SEGMENTS];
+};
+// the host checks both launchers share (segments tile [0, B), t columns inside the pitch); fills everything of `tab` but wg0
+int pevit_seg_table(const AttnSiteSegArgs& a, const char* who, SegTable& tab);
+// q / v of every segment rewritten in place with q + delta, v + delta (bf16 storage); the unchanged attn_fwd follows
+int pevit_launch_delta_add_seg(const AttnSiteSegArgs& a, hipStream_t s);
+// delta + attention in one launch, where pevit_attn_delta_hpw allows: one workgroup per run of heads INSIDE a segment
+int pevit_launch_attn_fwd_delta_seg(const AttnSiteSegArgs& a, hipStream_t s);
+
+void pevit_attn_delta_set_timeline(void* buf);     // measurement only: 8 s_memtime stamps per workgroup of the next fused launches (null = off)
 
 // ---- lowrank.hip -----------------------------------------------------------------
 struct AdapterPanels {      // per layer, rewritten every step from the f32 master parameters

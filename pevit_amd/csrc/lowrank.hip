@@ -108,13 +108,25 @@ __global__ void prep_lora_kernel(const float* __restrict__ a1q, const float* __r
 #define DA_RG_V 4
 #endif
 constexpr int DA_RG = DA_RG_V, DA_COLS = 64;
-template <typename ST>
+// SEG = SegTable: the segmented form (kernels.h; bf16 storage).  blockIdx.x counts the workgroups of all segments, segment after
+// segment; a workgroup looks up its segment, moves q, v and t to the segment's first image and takes the segment's image count for
+// B: below that it is the unsegmented kernel on the segment alone, with the segment's Q panel, bias and columns of t.
+template <typename ST, class SEG = NoSegments>
 __global__ __launch_bounds__(256) void delta_add_kernel(bf16* qbuf, bf16* vbuf, const float* __restrict__ t,
                                                         const float* __restrict__ q32, const bf16* __restrict__ q16,
-                                                        const float* __restrict__ bias, float ascale, int B, int N, int E) {
+                                                        const float* __restrict__ bias, float ascale, int B, int N, int E, SEG sg) {
     constexpr bool Q16 = sizeof(ST) == 2;
     const int lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
-    const int wg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    int blk = blockIdx.x;
+    int tp = 64;                                   // row pitch of t (floats)
+    if constexpr (SEG::on) {
+        static_assert(Q16, "the segmented form is built for bf16 storage");
+        const SegPick sp = seg_pick(sg, blockIdx.x);
+        const size_t img = (size_t)sp.first * N;   // rows in front of the segment
+        blk = sp.wg; B = sp.count; tp = sg.tpitch;
+        qbuf += img * E; vbuf += img * E; t += img * tp + sp.tcol; q16 = sp.q16; bias = sp.bias;
+    }
+    const int wg = blk * 4 + (threadIdx.x >> 6);
     const int which = blockIdx.y;                  // 0: q, 1: v
     const int T = B * N;
     const int parts = E / DA_COLS;
@@ -148,7 +160,7 @@ __global__ __launch_bounds__(256) void delta_add_kernel(bf16* qbuf, bf16* vbuf, 
     bf16x8 qb16[NST][2];
 #pragma unroll
     for (int k = 0; k < DA_RG; ++k) {
-        const float* src = t + (size_t)row_of_ref(rrk[k], B, N) * 64 + which * 32 + 8 * g;
+        const float* src = t + (size_t)row_of_ref(rrk[k], B, N) * tp + which * 32 + 8 * g;
         traw[k][0] = *reinterpret_cast<const float4*>(src); traw[k][1] = *reinterpret_cast<const float4*>(src + 4);
     }
     const int m = c16;
@@ -688,10 +700,27 @@ int pevit_launch_delta_add(const DeltaAddArgs& a, hipStream_t s) {
     const int T = B * N;
     const int waves = ceil_div(T, 16 * DA_RG) * (E / DA_COLS);
     if (a.f32) hipLaunchKernelGGL(delta_add_kernel<float>, dim3(ceil_div(waves, 4), 2), dim3(256), 0, s, a.qbuf, a.vbuf, a.t, a.q32, a.q16, a.bias,
-                                  a.ascale, B, N, E);
+                                  a.ascale, B, N, E, NoSegments{});
     else hipLaunchKernelGGL(delta_add_kernel<bf16>, dim3(ceil_div(waves, 4), 2), dim3(256), 0, s, a.qbuf, a.vbuf, a.t, a.q32, a.q16, a.bias,
-                            a.ascale, B, N, E);
+                            a.ascale, B, N, E, NoSegments{});
     LAUNCH_OK("delta_add_kernel");
+    return 0;
+}
+
+// every segment gets whole workgroups: ceil(waves of the segment / 4), the waves behind its last group of reference rows leave at once
+int pevit_launch_delta_add_seg(const AttnSiteSegArgs& a, hipStream_t s) {
+    const int N = a.N, E = a.H * 64;
+    if (a.H < 1 || N < 1) { pevit_set_error("delta_add_seg: bad geometry H=%d N=%d", a.H, N); return -1; }
+    SegTable tab;
+    if (pevit_seg_table(a, "delta_add_seg", tab)) return -1;
+    int wgs = 0;
+    for (int i = 0; i < a.nseg; ++i) {
+        tab.wg0[i] = wgs;
+        wgs += ceil_div(ceil_div(a.seg[i].count * N, 16 * DA_RG) * (E / DA_COLS), 4);
+    }
+    hipLaunchKernelGGL((delta_add_kernel<bf16, SegTable>), dim3(wgs, 2), dim3(256), 0, s, a.q, a.v, a.t, (const float*)nullptr,
+                       (const bf16*)nullptr, (const float*)nullptr, a.ascale, a.B, N, E, tab);
+    LAUNCH_OK("delta_add_kernel (segmented)");
     return 0;
 }
 

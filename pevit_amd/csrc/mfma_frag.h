@@ -5,6 +5,7 @@
 // production and the f32-verify kernels) agree because they call the SAME functions here.
 #pragma once
 #include "common.h"
+#include "kernels.h"
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -100,6 +101,29 @@ __device__ __forceinline__ const T* ddelta_slab(const T* dqkv, int ld, int col0,
     const int bh = c / N, n = c - bh * N;
     const int b = bh / H, h = bh - b * H;
     return dqkv + ((size_t)b * N + n) * ld + col0 + h * 64;
+}
+
+// The segment that owns workgroup `wg` of a segmented attention-site launch (kernels.h: SegTable), and the workgroup's index inside
+// it.  Static indices and selects only (a dynamic index would copy the table to scratch), and everything here is uniform over the
+// workgroup.  What the gfx950 build gives: no scratch in any instance; delta_add_kernel keeps the picked values in SGPRs, the two
+// attn_fwd_delta_kernel instances spill 68 / 98 SGPRs into VGPR lanes (160 VGPRs against 154, still 3 waves per SIMD).
+struct SegPick {
+    int first, count, tcol, wg;
+    const bf16* q16; const float* bias;
+};
+__device__ __forceinline__ SegPick seg_pick(const SegTable& sg, int wg) {
+    SegPick p{sg.first[0], sg.count[0], sg.tcol[0], wg, sg.q16[0], sg.bias[0]};
+#pragma unroll
+    for (int s = 1; s < PEVIT_MAX_SEGMENTS; ++s) {
+        const bool in = s < sg.nseg && wg >= sg.wg0[s];
+        p.first = in ? sg.first[s] : p.first;
+        p.count = in ? sg.count[s] : p.count;
+        p.tcol = in ? sg.tcol[s] : p.tcol;
+        p.wg = in ? wg - sg.wg0[s] : p.wg;
+        p.q16 = in ? sg.q16[s] : p.q16;
+        p.bias = in ? sg.bias[s] : p.bias;
+    }
+    return p;
 }
 
 // sum over the 8 row-lanes of a wave that hold the same 16-byte column piece (thread = (row tid >> 3, piece tid & 7))

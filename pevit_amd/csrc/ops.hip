@@ -135,6 +135,30 @@ extern "C" int pevit_op_attn_fwd_delta(void* stream, void* q, const void* k, voi
     a.nosave = lse == nullptr;      // no lse buffer: the inference form (q, v are left as they are)
     return pevit_launch_attn_fwd_delta(a, (hipStream_t)stream);
 }
+static int seg_args(AttnSiteSegArgs& a, const char* who, int nseg, const pevit_op_segment* segs) {
+    if (!segs || nseg < 1 || nseg > PEVIT_MAX_SEGMENTS) { pevit_set_error("%s: %d segments outside [1,%d]", who, nseg, PEVIT_MAX_SEGMENTS); return -1; }
+    a.nseg = nseg;
+    for (int i = 0; i < nseg; ++i) {
+        a.seg[i].first = segs[i].first; a.seg[i].count = segs[i].count; a.seg[i].tcol = segs[i].tcol;
+        a.seg[i].q16 = (const bf16*)segs[i].q16_bf16; a.seg[i].bias = segs[i].bias;
+    }
+    return 0;
+}
+extern "C" int pevit_op_delta_add_seg(void* stream, void* qbuf, void* vbuf, const float* t, int tpitch, float ascale, int B, int H, int N,
+                                      int nseg, const pevit_op_segment* segs) {
+    AttnSiteSegArgs a;
+    a.q = (bf16*)qbuf; a.v = (bf16*)vbuf; a.t = t; a.tpitch = tpitch; a.ascale = ascale; a.B = B; a.H = H; a.N = N;
+    if (seg_args(a, "delta_add_seg", nseg, segs)) return -1;
+    return pevit_launch_delta_add_seg(a, (hipStream_t)stream);
+}
+extern "C" int pevit_op_attn_fwd_delta_seg(void* stream, const void* q, const void* k, const void* v, const float* t, int tpitch,
+                                           float ascale, void* out, int ldo, int B, int H, int N, int nseg, const pevit_op_segment* segs) {
+    AttnSiteSegArgs a;      // (q and v are only read by the fused inference form)
+    a.q = (bf16*)const_cast<void*>(q); a.k = (const bf16*)k; a.v = (bf16*)const_cast<void*>(v); a.t = t; a.tpitch = tpitch; a.ascale = ascale;
+    a.out = (bf16*)out; a.ldo = ldo; a.B = B; a.H = H; a.N = N;
+    if (seg_args(a, "attn_fwd_delta_seg", nseg, segs)) return -1;
+    return pevit_launch_attn_fwd_delta_seg(a, (hipStream_t)stream);
+}
 extern "C" int pevit_debug_occupy(void* stream, int workgroups, int lds_bytes, double microseconds) {
     return pevit_launch_occupy(workgroups, lds_bytes, microseconds, (hipStream_t)stream);
 }

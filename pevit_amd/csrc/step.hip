@@ -211,16 +211,18 @@ extern "C" int pevit_optim_step(pevit_ctx* c, void* stream, int kind, const pevi
 // images (B,3,R,R) f32 -> feat (B,D) f32                               model.py:1034-1051
 // infer (pevit_predict): the inference layout and kernel forms; what a previous forward saved is overwritten, so no backward may follow
 // gate (the fused step, where pevit_set_step_gate gave it an event): wait for the step gate behind the stem and clear the gradients there
+// segments (pevit_predict_segments, which has made its own checks: no adapter need be selected there): c->segs holds the call's segments
 static int visual_forward_impl(pevit_ctx* c, void* stream, const void* images_any, int u8, float* feat, int B, int save_for_backward,
-                               bool infer, bool gate) {
+                               bool infer, bool gate, bool segments = false) {
     const float* images = (const float*)images_any;
     CHECK(refuse_text(c, infer ? "predict" : "visual_forward"));
-    CHECK(check_ready(c, B, infer ? "predict" : "visual_forward"));
+    if (!segments) CHECK(check_ready(c, B, infer ? "predict" : "visual_forward"));
     hipStream_t s = (hipStream_t)stream;
     if (infer) c->saved = SavedForward{};
     c->lay = layout_workspace(c, B, infer);
     if (infer && c->lay.total > c->ws_bytes_for_max) { pevit_set_error("predict: workspace too small (%zu < %zu)", c->ws_bytes_for_max, c->lay.total); return -1; }
-    const StepPlan pl = plan_step(c, B, infer);
+    StepPlan pl = plan_step(c, B, infer);
+    pl.segments = segments;
     char* W = c->ws; char* A = c->arena;
     const int E = c->E, N = c->N, T = B * N;
     float* xpre = at<float>(W, c->lay.w_dxn);               // scratch, free during the forward pass
@@ -308,6 +310,58 @@ extern "C" int pevit_predict_u8(pevit_ctx* c, void* stream, const uint8_t* image
                                 float* logits, float* feat_or_null, int B) {
     CHECK(check_u8_input(c, "predict_u8"));
     return predict_impl(c, stream, images, 1, running_mean, running_var, logits, feat_or_null, B);
+}
+
+// Requests for several resident adapters in ONE walk (include/pevit_segments.h): everything but the attention site runs once on all B
+// images, the attention site per segment on its slot's panels (walk.hip attn_core_fwd_slots), and the head once per segment on the
+// segment's feature rows with the slot's Linear layer and the segment's running statistics.  Every refusal comes before any launch.
+static int predict_segments_impl(pevit_ctx* c, void* stream, const void* images, int u8, int B, int nseg, const pevit_segment* segs) {
+    const char* who = "predict_segments";
+    CHECK(refuse_text(c, who));
+    if (!c || !c->arena || !c->ws) { pevit_set_error("%s: context not bound", who); return -1; }
+    if (!c->slots) { pevit_set_error("%s: this context has no adapter slots (pevit_infer_create_slots)", who); return -1; }
+    if (!images || !segs) { pevit_set_error("%s: null argument", who); return -1; }
+    if (B <= 0 || B > c->max_batch) { pevit_set_error("%s: batch %d outside [1,%d]", who, B, c->max_batch); return -1; }
+    if (nseg < 1 || nseg > PEVIT_MAX_SEGMENTS_PER_CALL) { pevit_set_error("%s: %d segments outside [1,%d]", who, nseg, PEVIT_MAX_SEGMENTS_PER_CALL); return -1; }
+    int next = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const pevit_segment& g = segs[i];
+        if (g.first != next || g.count < 1 || g.count > B - next) {
+            pevit_set_error("%s: segment %d is images [%d, %d): the segments must tile [0, %d) in order, one image at least each", who, i,
+                            g.first, g.first + g.count, B);
+            return -1;
+        }
+        if (g.slot < 0 || g.slot >= c->slots) { pevit_set_error("%s: segment %d names slot %d outside [0,%d)", who, i, g.slot, c->slots); return -1; }
+        if (!c->slot_params[g.slot]) { pevit_set_error("%s: segment %d names slot %d, which is not loaded (pevit_load_adapter_slot)", who, i, g.slot); return -1; }
+        if (!g.running_mean || !g.running_var || !g.logits) { pevit_set_error("%s: segment %d: null argument", who, i); return -1; }
+        next += g.count;
+    }
+    if (next != B) { pevit_set_error("%s: the segments cover %d of %d images: they must tile [0, %d)", who, next, B, B); return -1; }
+    c->nseg = nseg;
+    for (int i = 0; i < nseg; ++i) c->segs[i] = segs[i];
+    hipStream_t s = (hipStream_t)stream;
+    CHECK(visual_forward_impl(c, stream, images, u8, nullptr, B, 0, true, false, true));
+    char* W = c->ws;
+    const float* feat = at<float>(W, c->lay.w_feat);
+    for (int i = 0; i < nseg; ++i) {
+        const pevit_segment& g = segs[i];
+        const float* p = c->slot_params[g.slot];
+        const int Cs = c->slot_classes[g.slot];
+        HeadArgs a;
+        a.feat = feat + (size_t)g.first * c->D; a.W = p + c->n_tower; a.bias = a.W + (size_t)Cs * c->D;
+        a.running_mean = const_cast<float*>(g.running_mean); a.running_var = const_cast<float*>(g.running_var); a.training = 0;
+        a.ybn = at<float>(W, c->lay.w_ybn); a.rstd = at<float>(W, c->lay.w_bnrstd); a.logits = g.logits; a.B = g.count; a.D = c->D; a.Cc = Cs;
+        CHECK(pevit_launch_head(a, s));
+        if (g.features) HIP_OK(hipMemcpyAsync(g.features, a.feat, (size_t)g.count * c->D * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+extern "C" int pevit_predict_segments(pevit_ctx* c, void* stream, const float* images, int B, int nseg, const pevit_segment* segs) {
+    return predict_segments_impl(c, stream, images, 0, B, nseg, segs);
+}
+extern "C" int pevit_predict_segments_u8(pevit_ctx* c, void* stream, const uint8_t* images, int B, int nseg, const pevit_segment* segs) {
+    CHECK(check_u8_input(c, "predict_segments_u8"));
+    return predict_segments_impl(c, stream, images, 1, B, nseg, segs);
 }
 
 // images (B,3,R,R) -> features (B,D) through the inference forms, without a head (CLIP.encode_image for evaluation).  Like

@@ -4,38 +4,43 @@
 
 namespace pevit_host {
 
-static AdapterPanels panels(pevit_ctx* c, int l) {
+// slot: a slot of a multi-slot context; -1: the panels of the single-adapter calls (on such a context: the rows behind the last slot
+// and b.q16).  The f32 and the transposed panels are write-only on an inference-only context: every slot stores them to the same place.
+static AdapterPanels panels(pevit_ctx* c, int l, int slot = -1) {
     const BlockArena& b = c->blk[l];
     AdapterPanels p;
-    p.w_aug_rows = c->fp8 ? at<bf16>(c->arena, b.wpan) : eadv(c, at<bf16>(c->arena, b.wqkv), (size_t)3 * c->E * c->E);
+    const size_t prow = 3 * (size_t)c->E + 64 * (size_t)(slot < 0 ? c->slots : slot);
+    p.w_aug_rows = c->fp8 ? at<bf16>(c->arena, b.wpan) : eadv(c, at<bf16>(c->arena, b.wqkv), prow * c->E);
     p.ldw = c->E;
     // (an inference-only context has no wqkvT: the 64 columns go to its write-only panel, nobody reads them)
     p.wT_aug_cols = c->infer_only ? at<bf16>(c->arena, b.tsink) : eadv(c, at<bf16>(c->arena, b.wqkvT), 3 * (size_t)c->E);
     p.ldwT = c->infer_only ? 64 : c->NQ;
     p.q32 = at<float>(c->arena, b.q32);
     p.qT = at<bf16>(c->arena, b.qT);
-    p.q16 = at<bf16>(c->arena, b.q16);
+    p.q16 = slot < 0 ? at<bf16>(c->arena, b.q16) : at<bf16>(c->arena, b.q16s + (size_t)slot * q16_slot_bytes(c));
     return p;
 }
 
-// rebuild the bf16 adapter panels of every layer from the f32 master parameters (one launch)
-int prep_adapters(pevit_ctx* c, hipStream_t s) {
+// rebuild the bf16 adapter panels of every layer from the f32 master parameters (one launch).  slot >= 0 (pevit_load_adapter_slot):
+// the panels of that slot of a multi-slot context from `params`; otherwise those of the single-adapter calls from c->params
+int prep_adapters(pevit_ctx* c, hipStream_t s, int slot, const float* params) {
     const size_t E = c->E;
     LayerStrides st;
     st.arena_bytes = c->L > 1 ? c->blk[1].wqkv - c->blk[0].wqkv : 0;
     st.param_floats = c->p_layer_stride;
-    const float* lp = c->params + c->p_layer0;
+    if (slot < 0) params = c->params;
+    const float* lp = params + c->p_layer0;
     if (c->d.method == PEVIT_KADAPTATION) {
-        const float* r = c->params;
+        const float* r = params;
         PrepKadaptArgs a;
         a.rule1_l = r; a.rule1_r = r + 1024; a.rule2_l = r + 2048; a.rule2_r = r + 3072; a.q_left = lp; a.q_right = lp + E;
-        a.pan = panels(c, 0); a.E = c->E; a.ascale = c->ascale; a.layers = c->L; a.st = st; a.f32 = c->f32;
+        a.pan = panels(c, 0, slot); a.E = c->E; a.ascale = c->ascale; a.layers = c->L; a.st = st; a.f32 = c->f32;
         CHECK(pevit_launch_prep_kadapt(a, s));
     } else if (c->d.method == PEVIT_LORA) {
         const size_t rE = (size_t)c->d.lora_rank * E;
         PrepLoraArgs a;
         a.a1q = lp; a.a2q = lp + rE; a.a1v = lp + 2 * rE; a.a2v = lp + 3 * rE; a.r = c->d.lora_rank;
-        a.pan = panels(c, 0); a.E = c->E; a.ascale = c->ascale; a.layers = c->L; a.st = st; a.f32 = c->f32;
+        a.pan = panels(c, 0, slot); a.E = c->E; a.ascale = c->ascale; a.layers = c->L; a.st = st; a.f32 = c->f32;
         CHECK(pevit_launch_prep_lora(a, s));
     } else if (post_mlp(c)) {
         const BlockArena& b0 = c->blk[0];
@@ -59,6 +64,53 @@ int prep_adapters(pevit_ctx* c, hipStream_t s) {
 // leaves q / k / v in the head layout, lse and attn_out in the layer's saved slots.  Shared by the block walk and the attention seam.
 // Inference walk (pl.infer): the forms without the q' / v' write-back and without lse (f32 verification mode: the saving kernels, on
 // the shared slots).
+// A multi-slot context (pevit_infer_create_slots: attention-site method, bf16, inference walk) runs the segmented forms throughout.
+// Segmented call: the QKV product carries the 64 t columns of EVERY slot, and each segment takes its slot's columns, Q panel and bias.
+// Single-adapter call: one segment over the whole batch on the panels behind the last slot -- the product is 64 columns wider still,
+// and q, k, v and t keep their bits (the tile families QKV runs on are bit-identical whatever N).
+static int attn_core_fwd_slots(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l) {
+    const int E = c->E, T = B * c->N, H = c->H, N = c->N;
+    char* W = c->ws; char* A = c->arena;
+    const BlockArena& b = c->blk[l];
+    const LayerSaved& v = c->lay.sav[l];
+    bf16* qkv = at<bf16>(W, v.qkv);
+    const size_t plane = (size_t)T * E;
+    const int tcols = 64 * (pl.segments ? c->slots : c->slots + 1);
+    {
+        GemmParams p = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wqkv), E, c->NQpad, T, 3 * E + tcols, E);
+        p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.outf = at<float>(W, v.t); p.ldo = tcols;
+        p.E = E; p.H = H; p.Ntok = N;
+        CHECK(gemm(c, EPI_QKV_HEADS, p, s));
+    }
+    const bool kad = c->d.method == PEVIT_KADAPTATION;
+    const size_t boff = c->p_layer0 + c->p_layer_stride * l + 4 * (size_t)E;      // the delta bias of layer l in a flat buffer
+    AttnSiteSegArgs a;
+    a.q = qkv; a.k = qkv + plane; a.v = qkv + 2 * plane; a.t = at<float>(W, v.t); a.tpitch = tcols; a.ascale = c->ascale;
+    a.out = at<bf16>(W, v.attn_out); a.ldo = E; a.B = B; a.H = H; a.N = N;
+    if (pl.segments) {
+        a.nseg = c->nseg;
+        for (int i = 0; i < c->nseg; ++i) {
+            const pevit_segment& g = c->segs[i];
+            a.seg[i].first = g.first; a.seg[i].count = g.count; a.seg[i].tcol = 64 * g.slot;
+            a.seg[i].q16 = at<bf16>(A, b.q16s + (size_t)g.slot * q16_slot_bytes(c));
+            a.seg[i].bias = kad ? c->slot_params[g.slot] + boff : nullptr;
+        }
+    } else {
+        a.nseg = 1;
+        a.seg[0].first = 0; a.seg[0].count = B; a.seg[0].tcol = 64 * c->slots; a.seg[0].q16 = at<bf16>(A, b.q16);
+        a.seg[0].bias = kad ? c->params + boff : nullptr;
+    }
+    if (pl.attn_delta) {
+        PROF(c, s, PEVIT_PROF_ATTN_FWD_DELTA, T, (double)T * E * 4 * 2 + (double)T * 64 * 4, pevit_launch_attn_fwd_delta_seg(a, s));
+        return 0;
+    }
+    PROF(c, s, PEVIT_PROF_DELTA_ADD, T, (double)T * E * 4 * c->es + (double)T * 64 * 4, pevit_launch_delta_add_seg(a, s));
+    AttnArgs aa = attn_args(c, B, l);
+    aa.lse = nullptr;
+    PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2, pevit_launch_attn_fwd(aa, s));
+    return 0;
+}
+
 int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, unsigned char* a8, unsigned char* attn8) {
     const int E = c->E, T = B * c->N, H = c->H, N = c->N;
     char* W = c->ws; char* A = c->arena;
@@ -67,6 +119,7 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
     const LayerSaved& v = c->lay.sav[l];
     bf16* qkv = at<bf16>(W, v.qkv);
     const size_t plane = (size_t)T * E;
+    if (c->slots) return attn_core_fwd_slots(c, s, B, pl, l);
     if (!c->fp8) {
         GemmParams p = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wqkv), E, c->NQpad, T, site ? c->NQ : 3 * E, E);
         p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.outf = at<float>(W, v.t); p.ldo = 64;
@@ -138,7 +191,7 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
     if (l_hi < 0) l_hi = c->L;
     const int E = c->E, T = B * c->N, N = c->N;
     char* W = c->ws; char* A = c->arena;
-    if (pl.site || pl.post_mlp) CHECK(prep_adapters(c, s));
+    if ((pl.site || pl.post_mlp) && !pl.segments) CHECK(prep_adapters(c, s));     // (a segmented call reads the panels its slots were loaded with)
     for (int l = l_lo; l < l_hi; ++l) {
         const BlockArena& b = c->blk[l];
         const LayerSaved& v = c->lay.sav[l];

@@ -17,6 +17,9 @@ on a training context ("train") against ``serving.InferenceEngine.predict`` on a
 100 classes, batches 128 and 32, REPS rounds each in alternation -- the arena / workspace bytes of both contexts as the library
 reports them for ViT-B/32, ViT-B/16 and ViT-L/14 at batches 32 and 128, and microseconds per ``use()``.  With one route only, that
 route alone is built and timed (a process per round, to alternate two builds of the library).
+--segments: instead of the above, the segmented leg (profiles/serving.md; ``segments_leg`` below): eight requests of 16 images for
+eight resident adapters as a loop of ``use`` + ``predict`` against ONE ``predict_segments`` call, and the cost of a ``slots = 8``
+context.  --segments-one-pass ROUTE: nothing but STEPS calls of that route (the process to put under rocprofv3).
 Prints one JSON object.  usage: python scripts/predict_rate.py [--steps 20] [--reps 3] [--profile] [--serving] [--out FILE]"""
 import argparse
 import dataclasses
@@ -206,6 +209,111 @@ def serving_leg(steps, reps, route):
     return out
 
 
+def segments_leg(steps, reps, one_pass=None):
+    """ViT-B/32 + KAdaptation, 8 resident adapters, 8 requests of 16 images for 8 different adapters: the loop ``use(name);
+    predict(images)`` per request on a plain context ("loop": the route before segments, unchanged code) against one
+    ``predict_segments`` call on a ``slots = 8`` context ("segments"), same images, passes in alternation as the other legs.  Next
+    to it what a ``slots = 8`` context costs: ``predict`` at batch 128 on it against the plain context (its QKV product is 512
+    columns wider than 3 E + 64 for the single-adapter calls), and the arena / workspace bytes of both."""
+    from pevit_amd import adapter_io
+    from pevit_amd.engine import HipEngine, adapter_param_spec
+    from pevit_amd.serving import InferenceEngine
+    from pevit_amd.synth import ARCHS, randomize_adapters, synth_state_dict
+    dev = torch.device("cuda", 0)
+    arch, method, classes, n_req, req = ARCHS["ViT-B/32"], "kadaptation", 100, 8, 16
+    sd = {k: v for k, v in synth_state_dict(arch, seed=2, text_tower=False).items() if k.startswith("visual.")}
+    ckpts = []
+    for i in range(n_req):                                # eight different adapters and heads
+        ad = [(n, torch.zeros(s)) for n, s, _ in adapter_param_spec(method, arch.width, arch.layers)]
+        randomize_adapters(ad, seed=3 + i)
+        eng = HipEngine(arch, method, classes, 16)
+        eng.load_state_dict(dict(sd, **dict(ad)))
+        g = torch.Generator().manual_seed(5 + i)
+        with torch.no_grad():
+            eng.param_views()["layers.0.weight"].copy_(((torch.rand((classes, 512), generator=g) * 2 - 1) / 512 ** 0.5).cuda())
+            eng.running_var.copy_((0.5 + torch.rand(512, generator=g)).cuda())
+        ckpts.append(adapter_io.engine_adapter_state(eng, sd))
+        del eng
+    torch.cuda.empty_cache()
+    names = [f"task{i}" for i in range(n_req)]
+    engines = {}
+    for kind, slots in (("plain", 1), ("slots8", 8)):
+        e = InferenceEngine(arch, method, classes, 128, slots=slots)
+        e.load_backbone(sd)
+        for n, ck in zip(names, ckpts):
+            e.add_adapter(n, ck)
+        engines[kind] = e
+    plain, multi = engines["plain"], engines["slots8"]
+    out = {"sizes": {k: {"arena_bytes": e.arena_bytes, "workspace_bytes_max_batch_128": e.workspace_bytes} for k, e in engines.items()}}
+    x = torch.randn((steps, n_req * req, 3, 224, 224), generator=torch.Generator().manual_seed(0)).to(dev)
+
+    def loop(batch):
+        res = []
+        for i, n in enumerate(names):
+            plain.use(n)
+            res.append(plain.predict(batch[i * req:(i + 1) * req]))
+        return res
+
+    def segments(batch):
+        return multi.predict_segments([(n, batch[i * req:(i + 1) * req]) for i, n in enumerate(names)])
+
+    def single128(e):
+        def fn(batch):
+            e.use(names[0])
+            return e.predict(batch)
+        return fn
+    if one_pass:
+        fn = {"loop": loop, "segments": segments}[one_pass]
+        for i in range(steps):
+            fn(x[i])
+        torch.cuda.synchronize(dev)
+        return {"one_pass": one_pass, "calls": steps}
+    a, b = loop(x[0]), segments(x[0])
+    torch.cuda.synchronize(dev)
+    out["requests_bit_identical"] = [bool(torch.equal(p, q)) for p, q in zip(a, b)]
+    # A request runs on 16 x 50 rows in the loop and among 128 x 50 in the segmented call: the row-wise GEMMs may be planned
+    # differently.  The floor of that (tests/test_gpu_segments.py, test 4): the frozen tower alone, whole batch against its slices
+    rel = lambda p, q: float((p.double() - q.double()).abs().max() / (q.double().abs().max() + 1e-30))
+    out["requests_max_rel_distance"] = [rel(q, p) for p, q in zip(a, b)]
+    # ... and that the plan is ALL they differ by: at the same row count a lone segment is predict bit for bit, and at the full
+    # row count a request's answer does not depend on which adapters serve the other seven
+    lone = multi.predict_segments([(names[0], x[0][:req])])[0]
+    uniform = multi.predict_segments([(names[0], x[0][i * req:(i + 1) * req]) for i in range(n_req)])[0]
+    torch.cuda.synchronize(dev)
+    out["lone_segment_is_predict_bit_identical"] = bool(torch.equal(lone, a[0]))
+    out["request_0_same_bits_whoever_shares_the_call"] = bool(torch.equal(uniform, b[0]))
+    out["lone_segment_against_shared_call_max_rel"] = rel(b[0], lone)
+    eng = HipEngine(arch, "none", classes, 16)
+    eng.load_state_dict(sd)
+    with torch.no_grad():
+        eng.param_views()["layers.0.weight"].copy_(((torch.rand((classes, 512), generator=torch.Generator().manual_seed(4)) * 2 - 1) / 512 ** 0.5).cuda())
+    none = InferenceEngine(arch, "none", classes, 128)
+    none.load_backbone(sd)
+    none.add_adapter("head", adapter_io.engine_adapter_state(eng, sd))
+    none.use("head")
+    whole = none.predict(x[0]).clone()
+    out["plan_floor_method_none"] = max(rel(whole[i * req:(i + 1) * req], none.predict(x[0][i * req:(i + 1) * req])) for i in range(n_req))
+    del eng, none
+    for label, routes in (("requests_8x16", {"loop": loop, "segments": segments}),
+                          ("predict_bs128", {"plain": single128(plain), "slots8": single128(multi)})):
+        for r in routes.values():
+            run_pass(r, x)                                        # warm-up pass
+        wall = {r: [] for r in routes}
+        order = list(routes)
+        for rep in range(reps):
+            for r in (order if rep % 2 == 0 else order[::-1]):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                run_pass(routes[r], x)
+                torch.cuda.synchronize(dev)
+                wall[r].append(round(steps * n_req * req / (time.perf_counter() - t0), 1))
+        out[f"{label}_images_per_s_rounds"] = wall
+        med = {r: statistics.median(v) for r, v in wall.items()}
+        first, second = order
+        out[f"{label}_{second}_over_{first}"] = round(med[second] / med[first], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -215,7 +323,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--serving", action="store_true")
     ap.add_argument("--serving-route", choices=["both", "train", "serving"], default="both")
+    ap.add_argument("--segments", action="store_true")
+    ap.add_argument("--segments-one-pass", choices=["loop", "segments"], default=None)
     args = ap.parse_args()
+    if args.segments or args.segments_one_pass:
+        s = json.dumps(segments_leg(args.steps, args.reps, args.segments_one_pass), indent=1)
+        print(s)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(s + "\n")
+        return
     if args.serving:
         s = json.dumps(serving_leg(args.steps, args.reps, args.serving_route), indent=1)
         print(s)
