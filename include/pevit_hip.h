@@ -413,7 +413,8 @@ int pevit_train_forward_backward_bce_u8(pevit_ctx* ctx, void* stream, const uint
 enum pevit_prof_kind {
     PEVIT_PROF_LN_FWD = 0, PEVIT_PROF_LN_BWD = 1, PEVIT_PROF_ATTN_FWD = 2, PEVIT_PROF_ATTN_BWD = 3, PEVIT_PROF_DELTA_ADD = 4,
     PEVIT_PROF_LOWRANK_U = 5, PEVIT_PROF_LOWRANK_GRAD = 6, PEVIT_PROF_IM2COL = 7, PEVIT_PROF_LOWRANK_BWD = 8,
-    PEVIT_PROF_ATTN_FWD_DELTA = 9, PEVIT_PROF_ADAPTER_FWD = 10, PEVIT_PROF_ADAPTER_BWD = 11
+    PEVIT_PROF_ATTN_FWD_DELTA = 9, PEVIT_PROF_ADAPTER_FWD = 10, PEVIT_PROF_ADAPTER_BWD = 11,
+    PEVIT_PROF_GRAD_SUMSQ = 12, PEVIT_PROF_GRAD_SCALE = 13
 };
 int pevit_profile_begin(pevit_ctx* ctx, int max_launches);
 int pevit_profile_end(pevit_ctx* ctx, double* total_ms, double* total_flops, double* total_bytes, int* launches);
@@ -781,6 +782,8 @@ int pevit_set_step_gate(pevit_ctx* ctx, void* hip_event);
 
 /* segmented predict on a multi-slot inference context: its four entry points */
 #include "pevit_segments.h"
+/* gradient-norm clipping over the flat gradient buffer, between the backward and the update: its three entry points */
+#include "pevit_clip.h"
 
 #ifdef __cplusplus
 }

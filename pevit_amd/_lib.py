@@ -304,6 +304,13 @@ SEGMENT_SIGNATURES = {
 }
 MAX_SLOTS, MAX_SEGMENTS = 8, 16          # PEVIT_MAX_SLOTS, PEVIT_MAX_SEGMENTS_PER_CALL
 
+# include/pevit_clip.h (which pevit_hip.h includes): gradient-norm clipping over the flat gradient buffer, a table of their own
+CLIP_SIGNATURES = {
+    "pevit_clip_scratch_floats": (c_size_t, [c_size_t]),
+    "pevit_clip_grad_norm": (c_int, [P, P, c_float, c_float, P]),
+    "pevit_op_clip_grad_norm": (c_int, [P, P, P, c_size_t, c_float, c_float, P]),
+}
+
 _lib = None
 
 
@@ -328,7 +335,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -110,6 +110,7 @@ def default_config() -> CfgNode:
                    FUSED_OPTIMIZER=True,     # Adam / AdamW / SGD with several groups as one fused launch (not a reference key; False: torch's own step())
                    CACHE_FEATURES=True,      # linear probe: encode every image once per checkpoint and train the head on the cached rows (not a reference key; False: every step runs the tower)
                    TEXT_TOWER_ENGINE=False,  # INIT_HEAD_WITH_TEXT_ENCODER: all prompts through the engine's text tower in chunks instead of one torch call per class (not a reference key)
+                   CLIP_GRAD_NORM=0.0,       # > 0: clip_grad_norm_ to this L2 norm between backward and step (full_model_finetune.py:327 of the reference; here the PEFT loops honour it too)
                    WITHOUT_WD_LIST=[], NESTEROV=True, BEGIN_EPOCH=0, END_EPOCH=100, EXTRA_FINAL_TRAIN_EPOCH=0,
                    EMULATE_ZERO_SHOT=False, BATCH_SIZE_PER_GPU=32, SHUFFLE=True, RMSPROP_ALPHA=0.99, RMSPROP_CENTERED=False),
         TEST=dict(BATCH_SIZE_PER_GPU=32, METRIC="accuracy", MODEL_FILE=""),

@@ -309,6 +309,20 @@ struct OptimArgs {
 };
 int pevit_launch_optim(const OptimArgs& a, hipStream_t s);
 
+// ---- clip.hip (gradient-norm clipping over the flat gradient buffer: clip_grad_norm_, norm_type 2) ----
+constexpr int CLIP_CHUNK = 8192;          // elements of the slice one workgroup of grad_sumsq_kernel / grad_scale_kernel owns
+struct ClipArgs {
+    float* g = nullptr;                   // the flat buffer, 16-byte aligned; scaled in place
+    const unsigned char* mask = nullptr;  // optional, 4-byte aligned: elements whose byte is 0 are neither counted nor scaled
+    size_t n = 0;
+    float max_norm = 0.f, grad_scale = 1.f;      // grad_scale multiplies the NORM only (1 / world under data parallelism)
+    float* scratch = nullptr;             // pevit_clip_scratch_floats(n) words: {total, coef, ticket, -, one partial per workgroup}
+};
+size_t pevit_clip_blocks(size_t n);       // workgroups (= partials) of both launches
+int pevit_clip_check(float max_norm, float grad_scale, const char* who);     // both finite and > 0, or -1 with the error text set
+int pevit_launch_grad_sumsq(const ClipArgs& a, hipStream_t s);               // scratch[0] = total, scratch[1] = coef
+int pevit_launch_grad_scale(const ClipArgs& a, hipStream_t s);               // g *= scratch[1]
+
 int pevit_launch_occupy(int blocks, int lds_bytes, double micros, hipStream_t s);   // measurement only (pevit_debug_occupy)
 
 // ---- fp8.hip (e4m3 codes + power-of-two channel scales of the frozen weights) -----------------

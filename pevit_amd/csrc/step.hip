@@ -169,6 +169,24 @@ extern "C" int pevit_sgd_step(pevit_ctx* c, void* stream, float lr, float moment
     return pevit_launch_sgd(a, (hipStream_t)stream);
 }
 
+// clip_grad_norm_ over the gradient buffer, between the backward (and the exchange) and the update: two launches of clip.hip.
+// Neither error word gates it -- they withhold the update behind it, and a clipped buffer nobody applies harms nothing.
+extern "C" int pevit_clip_grad_norm(pevit_ctx* c, void* stream, float max_norm, float grad_scale, float* scratch) {
+    if (!c) { pevit_set_error("clip_grad_norm: null context"); return -1; }
+    CHECK(refuse_text(c, "clip_grad_norm"));
+    CHECK(refuse_infer(c, "clip_grad_norm"));
+    CHECK(pevit_clip_check(max_norm, grad_scale, "clip_grad_norm"));
+    if (!scratch) { pevit_set_error("clip_grad_norm: null scratch buffer (pevit_clip_scratch_floats)"); return -1; }
+    if (!c->params || !c->grads || !c->n_total) { pevit_set_error("clip_grad_norm: parameters not set (pevit_set_params)"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    ClipArgs a;
+    a.g = c->grads; a.mask = c->grad_mask; a.n = c->n_total; a.max_norm = max_norm; a.grad_scale = grad_scale; a.scratch = scratch;
+    const double bytes = 4.0 * (double)a.n + (a.mask ? (double)a.n : 0.0);
+    PROF(c, s, PEVIT_PROF_GRAD_SUMSQ, 1, bytes, pevit_launch_grad_sumsq(a, s));
+    PROF(c, s, PEVIT_PROF_GRAD_SCALE, 1, bytes + 4.0 * (double)a.n, pevit_launch_grad_scale(a, s));
+    return 0;
+}
+
 static_assert((int)PEVIT_OPTIM_SGD == (int)OPTIM_SGD && (int)PEVIT_OPTIM_ADAM == (int)OPTIM_ADAM &&
               (int)PEVIT_OPTIM_ADAMW == (int)OPTIM_ADAMW && PEVIT_OPTIM_MAX_GROUPS == OPTIM_MAX_GROUPS, "optimizer kinds: header vs kernels.h");
 

@@ -158,6 +158,10 @@ class HipEngine(EngineContext, InputMixin, OptimMixin, DpMixin):
         # it: an in-place edit of a plan is seen
         self._group_of = self._group_of_host = self._group_of_seen = None
         self._optim_kind = None          # which optimizer the momentum / exp_avg_sq buffers belong to (None: fresh, or plain sgd_step)
+        # clip_grad_norm: {norm before clipping, clip coefficient, arrival count, -, one partial per workgroup}; zeroed once, here
+        self._clip_scratch = torch.zeros(self.lib.pevit_clip_scratch_floats(self.n_params), dtype=torch.float32, device=self.device)
+        self.last_grad_norm = self._clip_scratch[0]      # 0-dim device view: the norm the last clip found, never synchronised here
+        self.max_grad_norm = None        # a bound: every update of train_step / a captured step clips the gradients to it first (None: off)
         # ---- engine_dp.py
         self._pipe = None                # the pipelined schedule's second stream, its two events and "open": an update is owed
         self._xt = None                  # time_exchange: the event pairs around every exchange (None: off)
@@ -531,7 +535,9 @@ class HipEngine(EngineContext, InputMixin, OptimMixin, DpMixin):
         is the only thing that crosses xGMI (the frozen backbone never does); how it is exchanged is ``dp_exchange_mode``
         (default: one in-stream all-reduce behind the fused forward/backward call, 1/world folded into the SGD kernel).
         ``optimizer``: an ``OptimPlan`` (Adam, AdamW, SGD with several groups) -- the update is then ``optimizer_step(plan)``
-        wherever it is ``sgd_step`` otherwise, and ``lr`` / ``momentum`` / ``weight_decay`` / ``nesterov`` are not read."""
+        wherever it is ``sgd_step`` otherwise, and ``lr`` / ``momentum`` / ``weight_decay`` / ``nesterov`` are not read.
+        With ``self.max_grad_norm`` set the gradients are clipped to that L2 norm right in front of the update (two more launches,
+        no host read; under DP behind the exchange, on the norm of the averaged gradient); None, the default: the launches of before."""
         if optimizer is None and lr is None:
             raise TypeError("train_step: lr (plain SGD) or optimizer (an OptimPlan) is required")
         if world_size > 1:

@@ -1,6 +1,8 @@
 """The parameter updates of ``HipEngine`` and the error words that can withhold them: the fused SGD kernel, the planned optimizers
 (csrc/optim.hip), the whole step captured into a HIP graph, and the stream-K / all-reduce error-word check behind every update.
-A mixin: its state (``_steps``, ``_optim_kind``, ``exp_avg_sq``, ``_group_of*``) is declared in ``HipEngine.__init__``."""
+Gradient-norm clipping (csrc/clip.hip) sits in front of every update.
+A mixin: its state (``_steps``, ``_optim_kind``, ``exp_avg_sq``, ``_group_of*``, ``_clip_scratch``, ``last_grad_norm``, ``max_grad_norm``) is declared in
+``HipEngine.__init__``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,6 +10,14 @@ import ctypes as C
 import torch
 
 from . import _lib
+
+
+def clip_grad_norm(engine, max_norm, grad_scale=1.0):
+    """``torch.nn.utils.clip_grad_norm_`` on ``engine.grads``, on the device: two launches on the current stream, no host read
+    (``OptimMixin._clip_grad_norm``).  Returns ``engine.last_grad_norm``, the 0-dim device view of the norm before clipping.  For a
+    caller that takes the step apart (gradients, clip, update as separate calls); ``engine.max_grad_norm = bound`` makes every
+    ``train_step`` do the same in front of its update."""
+    return engine._clip_grad_norm(max_norm, grad_scale)
 
 
 class OptimMixin:
@@ -84,8 +94,25 @@ class OptimMixin:
         self._optim_kind = plan.kind
         self._after_update()
 
+    def _clip_grad_norm(self, max_norm, grad_scale=1.0, _pipelined=False):
+        """(Public as ``engine_optim.clip_grad_norm(engine, ...)``: the class surface of ``HipEngine`` is a recorded one.)
+        ``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (norm_type 2, f32) on ``self.grads`` as two launches on the
+        current stream, no host read (``pevit_clip_grad_norm``): the tensors whose ``.grad`` is None in torch (``grad_mask``) are
+        neither counted nor touched.  ``grad_scale``: the update's factor (1 / world where the buffer holds the sum over the
+        ranks); it scales the norm only, the buffer is multiplied by the clip coefficient alone.  Returns ``last_grad_norm``: the
+        0-dim device view of the norm BEFORE clipping, not synchronised (the next clip overwrites it)."""
+        if not _pipelined:
+            self.dp_flush()
+        _lib.check(self.lib.pevit_clip_grad_norm(self._ctx, _lib.stream_ptr(), float(max_norm), float(grad_scale),
+                                                 _lib.ptr(self._clip_scratch)), "pevit_clip_grad_norm")
+        return self.last_grad_norm
+
     def _update(self, optimizer, lr, momentum, weight_decay, grad_scale, nesterov, _pipelined=False):
-        """The step's one dispatch point between the plain-SGD kernel and a planned optimizer."""
+        """The step's one dispatch point between the plain-SGD kernel and a planned optimizer; with ``self.max_grad_norm`` set the
+        gradients are clipped right in front of it, on the stream the update runs on (under data parallelism: behind the exchange,
+        on the norm of the averaged gradient).  Every caller -- plain ``train_step`` and the three DP schedules -- comes through here."""
+        if self.max_grad_norm is not None:
+            self._clip_grad_norm(self.max_grad_norm, grad_scale, _pipelined=_pipelined)
         if optimizer is not None:
             return self.optimizer_step(optimizer, grad_scale, _pipelined=_pipelined)
         self.sgd_step(lr, momentum, weight_decay, grad_scale, nesterov, _pipelined=_pipelined)
@@ -137,7 +164,10 @@ class OptimMixin:
         library's one-time attribute calls are not stream operations).  Same kernels, same order: bit-identical to eager
         (tests/test_gpu_mirror.py::test_graph_replay_equals_eager).  Measured: profiles/r05_graph_capture.md.
         Plain SGD only: the Adam step count ``t`` is kept by the host and reaches the kernel by value, so a captured launch would
-        replay one fixed ``t``; an ``optimizer`` plan (``optimizer_step``) raises here until a device-side counter exists."""
+        replay one fixed ``t``; an ``optimizer`` plan (``optimizer_step``) raises here until a device-side counter exists.
+        With ``self.max_grad_norm`` set at capture time the two launches of the clip are captured between the backward and the
+        update, the bound baked in like the other hyper-parameters (the clip coefficient lives on the device, so a replay clips by
+        the norm of ITS gradients)."""
         if optimizer is not None:
             raise _lib.PevitError("capture_train_step captures the plain-SGD step only: the planned optimizers (Adam, AdamW, "
                                   "per-group SGD) take their step count and hyper-parameters by value on every launch")
@@ -166,6 +196,9 @@ class OptimMixin:
                 _lib.check(fn(self._ctx, _lib.stream_ptr(), _lib.ptr(images), _lib.ptr(labels), _lib.ptr(self.running_mean),
                               _lib.ptr(self.running_var), int(bn_training), _lib.ptr(logits), _lib.ptr(loss), B),
                            "pevit_train_forward_backward (capture)")
+                if self.max_grad_norm is not None:
+                    _lib.check(self.lib.pevit_clip_grad_norm(self._ctx, _lib.stream_ptr(), float(self.max_grad_norm), 1.0,
+                                                             _lib.ptr(self._clip_scratch)), "pevit_clip_grad_norm (capture)")
                 _lib.check(self.lib.pevit_sgd_step(self._ctx, _lib.stream_ptr(), lr, momentum, weight_decay, 1.0, flags),
                            "pevit_sgd_step (capture)")
         torch.cuda.current_stream(self.device).wait_stream(side)

@@ -458,15 +458,18 @@ class ClassifierBase(nn.Module):
             return None                               # a trainable tensor the engine's flat buffer does not hold
         return plan_fused_optimizer(optimizer, layout, mask)
 
-    def fused_train_step(self, images, target, optimizer, logits_out=None, loss_out=None, plan=None):
+    def fused_train_step(self, images, target, optimizer, logits_out=None, loss_out=None, plan=None, max_grad_norm=None):
         """One reference train_one iteration as one engine call.  ``logits_out`` (B, C) / ``loss_out`` (1,): rows of the caller's
         epoch buffers the engine writes straight into; without them the results are copies of the engine's per-step buffers.
         ``plan`` (``fused_optimizer_plan``): the update is the planned optimizer's instead of plain SGD's; either way the
-        hyper-parameters are read from ``optimizer.param_groups`` on every step."""
+        hyper-parameters are read from ``optimizer.param_groups`` on every step.  ``max_grad_norm``: the gradients are clipped to
+        this L2 norm in front of the update, inside the engine call (``HipEngine.max_grad_norm``; None switches it off again)."""
         eng = self.engine()
         eng.ensure_batch(images.shape[0])
         g = next(g for g in optimizer.param_groups if len(g["params"]) > 0)
         img = images.contiguous() if images.dtype == torch.uint8 else images.contiguous().float()
+        if eng.max_grad_norm != max_grad_norm:
+            eng.max_grad_norm = max_grad_norm
         if plan is not None:
             logits, loss = eng.train_step(img, target.contiguous(), bn_training=self.channel_bn.training, logits_out=logits_out,
                                           loss_out=loss_out, optimizer=plan.refresh(optimizer))
@@ -731,6 +734,10 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
     # the optimizers can_fuse leaves out (Adam, AdamW, SGD with several lr / weight decays) keep the same one-call step through a plan
     plan = None if fused else model.fused_optimizer_plan(criterion, optimizer)
     fused = fused or plan is not None
+    # TRAIN.CLIP_GRAD_NORM > 0: clip_grad_norm_ between backward and step.  The reference's PEFT loops never read the key (only its
+    # full_model_finetune.py does): honouring it here is an extension; at its default of 0 nothing changes
+    clip = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)
+    clip = {"max_grad_norm": clip} if clip > 0 else {}
     dev = config.GPUS[0]
     single = len(config.GPUS) == 1
     # epoch buffers the fused step writes its logits / loss straight into (no per-step copies of the engine's buffers)
@@ -767,7 +774,7 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
                 direct = out_buf is not None and row + n <= out_buf.shape[0] and step < loss_buf.shape[0]
                 output, loss = model.fused_train_step(images, target, optimizer,
                                                       out_buf[row:row + n] if direct else None,
-                                                      loss_buf[step:step + 1] if direct else None, plan=plan)
+                                                      loss_buf[step:step + 1] if direct else None, plan=plan, **clip)
                 row += n if direct else 0
                 step += 1 if direct else 0
             else:
@@ -775,6 +782,8 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
                 output = model.forward(images)
                 loss = criterion(output, target)
                 loss.backward()
+                if clip:
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), clip["max_grad_norm"])
                 optimizer.step()
             step_losses.append(loss.detach().reshape(1)); step_sizes.append(images.size(0))
             outputs.append(output.detach())

@@ -32,6 +32,7 @@ from .clip_load import *  # noqa: F401,F403
 from .dataloader import TensorLoader, _Tensors, _View
 from .feature import _engine_feature_chunks, _image_engine
 from .metric import get_metric
+from ..engine_optim import clip_grad_norm
 from ..optim import build_optimizer  # noqa: F401
 
 METHOD = "none"
@@ -263,6 +264,10 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
     picked, sizes = [], []
     row = step = 0
     scale = model.scale()
+    # TRAIN.CLIP_GRAD_NORM > 0 (reference :327-328): clip_grad_norm_ between the backward and the step.  On the engine routes the
+    # step is then taken apart -- gradients only, the clip (two launches, no host read), the update as its own call
+    clip = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)
+    clip = clip if clip > 0 else None
     try:
         for sel in epoch_index_batches(train_loader):
             n = sel.shape[0]
@@ -276,17 +281,24 @@ def train_one(train_loader, model, criterion, optimizer, epoch, config):
                 output = model.head(cache.feats[sel])
                 loss = criterion(output, target)
                 loss.backward()
+                if clip is not None:
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
                 optimizer.step()
                 logits_out.copy_(output.detach()); loss_out.copy_(loss.detach().reshape(1))
             else:
                 eng.ensure_batch(n)
                 g = next(g for g in optimizer.param_groups if len(g["params"]) > 0)
-                eng.probe_step(cache.feats, sel, cache.labels, lr=g["lr"], momentum=g.get("momentum", 0.0),
-                               weight_decay=g["weight_decay"], nesterov=bool(g.get("nesterov", False)),
-                               bn_training=model.channel_bn.training, scale=scale, update=route == "fused",
+                hyper = dict(lr=g["lr"], momentum=g.get("momentum", 0.0), weight_decay=g["weight_decay"],
+                             nesterov=bool(g.get("nesterov", False)))
+                eng.probe_step(cache.feats, sel, cache.labels, **hyper,
+                               bn_training=model.channel_bn.training, scale=scale, update=route == "fused" and clip is None,
                                logits_out=logits_out, loss_out=loss_out)
+                if clip is not None:
+                    clip_grad_norm(eng, clip)
                 if route == "plan":
                     eng.optimizer_step(plan.refresh(optimizer))
+                elif clip is not None:
+                    eng.sgd_step(**hyper)
                 if model.channel_bn.training:
                     model._bn_steps = getattr(model, "_bn_steps", 0) + 1
             picked.append(sel); sizes.append(n)
