@@ -590,6 +590,20 @@ int pevit_op_adapter_fwd_ex(void* stream, const pevit_adapter_fwd_args* args);
 int pevit_op_adapter_bwd_ex(void* stream, const pevit_adapter_bwd_args* args);
 int pevit_op_adapter_blocks(int T);         /* workgroups (= blocks of `partial`) of the fused backward */
 int pevit_op_adapter_fused_ok(int E);       /* 1: the fused launches take this width */
+/* Test-only form of the segmented inference launch of the fused forward (adapter_fused.hip adapter_fwd_seg_kernel;
+ * tests/test_gpu_segments_postmlp.py).  hraw, bpr, x_mid, x_out as above, over all rows; segs: a HOST array of nseg in [1,16]
+ * segments, rows [first, end) each with its own gamma, beta [E], wd [64][E] and wu [E][64] bf16, b_down [64], b_up [E].  One launch of
+ * sum_s ceil((end_s - first_s) / 32) workgroups, none of which crosses a segment end; x_out of a segment has the bits of
+ * pevit_op_adapter_fwd_ex on that segment's rows alone.  Nothing else is written (no z, act, apre, mean_a, rstd_a). */
+typedef struct pevit_adapter_seg {
+    int32_t first, end;
+    const float* gamma; const float* beta; const void* wd; const float* b_down; const void* wu; const float* b_up;
+} pevit_adapter_seg;
+typedef struct pevit_adapter_fwd_seg_args {
+    const float* hraw; const float* bpr; const float* x_mid; float* x_out; const pevit_adapter_seg* segs;
+    int32_t act_kind, E, nseg;
+} pevit_adapter_fwd_seg_args;
+int pevit_op_adapter_fwd_seg(void* stream, const pevit_adapter_fwd_seg_args* args);
 /* Test-only forms of the attention-site low-rank adapter launches (lowrank.hip; tests/test_gpu_lowrank.py): the members of the
  * launchers' parameter structs, by name, from one flat argument struct each (zero-initialised = nothing set).  They add no kernel.
  *   pevit_op_lowrank_ex:    form = enum pevit_lowrank_form.  LOWRANK_U: dqkv [T][ld] bf16 (q | k | v gradients in row layout), qT
@@ -782,6 +796,8 @@ int pevit_set_step_gate(pevit_ctx* ctx, void* hip_event);
 
 /* segmented predict on a multi-slot inference context: its four entry points */
 #include "pevit_segments.h"
+/* ... and the slot contexts of all four methods (Adapter and Compacter included): their two entry points */
+#include "pevit_segments_all.h"
 /* gradient-norm clipping over the flat gradient buffer, between the backward and the update: its three entry points */
 #include "pevit_clip.h"
 

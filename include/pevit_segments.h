@@ -13,8 +13,13 @@
  * answer therefore does not depend on who shares the launch with it.  Everything outside the attention site is row-wise and runs
  * once on all rows.
  *
+ * All four methods are served by segments.  This header holds the entries of the attention-site methods and the two calls;
+ * Adapter and Compacter, whose adapters are row-wise, get their slot contexts from pevit_infer_create_slots_all and their slots from
+ * pevit_load_adapter_slot_rule (pevit_segments_all.h, included behind this file), and are answered by the same two calls below.
+ *
  * pevit_infer_create_slots: pevit_infer_create with 1 <= slots <= 8 slots.  KAdaptation and LoRA in the bf16 weight format only: the
- * other methods (the 32-row blocks of the post-MLP adapter kernels straddle segments), the fp8 formats and the f32 verification mode
+ * post-MLP methods (this entry keeps refusing them: their slots are another arena, see pevit_infer_create_slots_all), method none,
+ * the fp8 formats and the f32 verification mode
  * are refused with slots > 1 (with slots == 1 they give the context of pevit_infer_create, which refuses the segmented calls).
  * pevit_infer_create itself is unchanged: same arena, same workspace.  The arena grows by 64 slots rows of in_proj and `slots` Q
  * panels per layer, the workspace by 64 slots f32 columns of t per token.

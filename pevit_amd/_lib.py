@@ -67,6 +67,18 @@ class PevitAdapterBwdArgs(C.Structure):
                 [(n, C.c_int32) for n in ("act_kind", "T", "E", "tn_blocks")])
 
 
+class PevitAdapterSeg(C.Structure):
+    """pevit_adapter_seg of include/pevit_hip.h: one segment (rows [first, end) and its operands) of pevit_op_adapter_fwd_seg"""
+    _fields_ = ([(n, C.c_int32) for n in ("first", "end")] +
+                [(n, c_void_p) for n in ("gamma", "beta", "wd", "b_down", "wu", "b_up")])
+
+
+class PevitAdapterFwdSegArgs(C.Structure):
+    """pevit_adapter_fwd_seg_args of include/pevit_hip.h (the test-only pevit_op_adapter_fwd_seg); zero-initialised = nothing set"""
+    _fields_ = ([(n, c_void_p) for n in ("hraw", "bpr", "x_mid", "x_out")] + [("segs", C.POINTER(PevitAdapterSeg))] +
+                [(n, C.c_int32) for n in ("act_kind", "E", "nseg")])
+
+
 class PevitSegment(C.Structure):
     """pevit_segment of include/pevit_segments.h: one segment of pevit_predict_segments"""
     _fields_ = [(n, C.c_int32) for n in ("first", "count", "slot")] + [(n, c_void_p) for n in ("running_mean", "running_var", "logits", "features")]
@@ -248,6 +260,7 @@ SIGNATURES = {
     "pevit_op_adapter_bwd_ex": (c_int, [P, C.POINTER(PevitAdapterBwdArgs)]),
     "pevit_op_adapter_blocks": (c_int, [c_int]),
     "pevit_op_adapter_fused_ok": (c_int, [c_int]),
+    "pevit_op_adapter_fwd_seg": (c_int, [P, C.POINTER(PevitAdapterFwdSegArgs)]),
     "pevit_op_lowrank_ex": (c_int, [P, C.POINTER(PevitLowrankArgs)]),
     "pevit_op_prep_lowrank": (c_int, [P, C.POINTER(PevitPrepLowrankArgs)]),
     "pevit_op_chain_lowrank": (c_int, [P, C.POINTER(PevitChainLowrankArgs)]),
@@ -304,6 +317,12 @@ SEGMENT_SIGNATURES = {
 }
 MAX_SLOTS, MAX_SEGMENTS = 8, 16          # PEVIT_MAX_SLOTS, PEVIT_MAX_SEGMENTS_PER_CALL
 
+# include/pevit_segments_all.h (which pevit_hip.h includes): slot contexts for all four methods, a table of their own
+SEGMENT_ALL_SIGNATURES = {
+    "pevit_infer_create_slots_all": (c_int, [C.POINTER(PevitDims), c_int, C.POINTER(c_void_p)]),
+    "pevit_load_adapter_slot_rule": (c_int, [P, P, c_int, P, c_int, P]),
+}
+
 # include/pevit_clip.h (which pevit_hip.h includes): gradient-norm clipping over the flat gradient buffer, a table of their own
 CLIP_SIGNATURES = {
     "pevit_clip_scratch_floats": (c_size_t, [c_size_t]),
@@ -335,7 +354,8 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(SEGMENT_ALL_SIGNATURES.items()) + \
+            list(CLIP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -351,6 +351,153 @@ __global__ __launch_bounds__(64 * AF_WAVES, AF_MINW) void adapter_fwd_kernel(con
     }
 }
 
+// ---- the segmented inference form (pevit_predict_segments on a post-MLP slot context) ---------------------------------------------
+// The rows of one launch belong to up to 16 segments, each with its own LayerNorm affine, panels and biases (the adapter its slot
+// holds).  The table travels by value; the grid is sum_s ceil(rows_s / AF_ROWS) and wg0[s] is the first workgroup of segment s, so a
+// tile never holds rows of two segments: a workgroup owns rows [r0, rend) of ITS segment, and rows behind rend read the segment's
+// last row (never a neighbour's), their results dropped.  Entries behind nseg are zero.
+struct AfSegTable {
+    int nseg;
+    int first[PEVIT_MAX_SEGMENTS], end[PEVIT_MAX_SEGMENTS], wg0[PEVIT_MAX_SEGMENTS];
+    const float* gamma[PEVIT_MAX_SEGMENTS]; const float* beta[PEVIT_MAX_SEGMENTS]; const bf16* wd[PEVIT_MAX_SEGMENTS];
+    const float* b_down[PEVIT_MAX_SEGMENTS]; const bf16* wu[PEVIT_MAX_SEGMENTS]; const float* b_up[PEVIT_MAX_SEGMENTS];
+};
+
+// adapter_fwd_kernel<ACT, NV> on the rows of the workgroup's segment, operation for operation (the same helpers, the same
+// expressions in the same order), as the first INFERENCE form of this kernel: the launcher passes z, mean_a, rstd_a, act and apre as
+// NULL and nothing that only a backward reads is stored.  The five pointers and their guarded stores stay in the source so that the
+// compiler meets the basic blocks of adapter_fwd_kernel: without them it paired the lanes of the LayerNorm arithmetic differently
+// (at NV = 3 one float4 per row batch as multiply + add instead of a fused multiply-add), and about one row in 2000 of a ViT-B/32
+// walk came out with other bits of x_out than adapter_fwd_kernel gives.
+template <int ACT, int NV>
+__global__ __launch_bounds__(64 * AF_WAVES, AF_MINW) void adapter_fwd_seg_kernel(const float* __restrict__ hraw, const float* __restrict__ bpr,
+                                                                        const float* __restrict__ x_mid, float* __restrict__ x_out,
+                                                                        bf16* __restrict__ z, float* __restrict__ mean_a,
+                                                                        float* __restrict__ rstd_a, bf16* __restrict__ act,
+                                                                        bf16* __restrict__ apre, int E_rt, AfSegTable tab) {
+#ifdef AF_E_RUNTIME
+    const int E = E_rt;
+#else
+    constexpr int E = 256 * NV;
+    (void)E_rt;
+#endif
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const AfLds L = af_layout(E);
+    bf16* Zs = reinterpret_cast<bf16*>(smem + L.zs);
+    float* red = reinterpret_cast<float*>(smem + L.red);
+    bf16* As = reinterpret_cast<bf16*>(smem + L.as);
+    float* U = reinterpret_cast<float*>(smem + L.u);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    // the workgroup's segment: a uniform scan of the first-workgroup column, then ONE entry read from the table where the kernel
+    // arguments lie (scalar loads at a uniform index; selecting all nine columns through the scan spilled scalar registers)
+    const int blk = blockIdx.x;
+    int sg = 0;
+#pragma unroll
+    for (int s = 1; s < PEVIT_MAX_SEGMENTS; ++s) sg = (s < tab.nseg && blk >= tab.wg0[s]) ? s : sg;
+    const int end = tab.end[sg];
+    const float* __restrict__ gamma = tab.gamma[sg]; const float* __restrict__ beta = tab.beta[sg]; const bf16* __restrict__ wd = tab.wd[sg];
+    const float* __restrict__ b_down = tab.b_down[sg]; const bf16* __restrict__ wu = tab.wu[sg]; const float* __restrict__ b_up = tab.b_up[sg];
+    const int r0 = tab.first[sg] + AF_ROWS * (blk - tab.wg0[sg]), rend = min(r0 + AF_ROWS, end), last = end - 1;
+    const int ldz = E + 8;
+    int cc[NV];
+    float4 gm[NV], bt[NV], bp[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane * 4 + i * 256;
+        cc[i] = c;
+        gm[i] = *reinterpret_cast<const float4*>(gamma + cc[i]);
+        bt[i] = *reinterpret_cast<const float4*>(beta + cc[i]);
+        bp[i] = *reinterpret_cast<const float4*>(bpr + cc[i]);
+    }
+    // ---- phase 1: h = acc + b, statistics, z (LDS only), s = x_mid + h
+    constexpr int RB = NV == 4 ? 1 : AF_RB;
+    float4 s[AF_RPW][NV];
+#pragma unroll
+    for (int half = 0; half < AF_RPW / RB; ++half) {
+        float4 hv[RB][NV], xv[RB][NV];
+#pragma unroll
+        for (int k = 0; k < RB; ++k) {
+            const int row = min(r0 + wid * AF_RPW + half * RB + k, last);
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                hv[k][i] = *reinterpret_cast<const float4*>(hraw + (size_t)row * E + cc[i]);
+                xv[k][i] = *reinterpret_cast<const float4*>(x_mid + (size_t)row * E + cc[i]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < RB; ++k) {
+            const int lr = wid * AF_RPW + half * RB + k, row = r0 + lr;
+            float sum = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                hv[k][i].x += bp[i].x; hv[k][i].y += bp[i].y; hv[k][i].z += bp[i].z; hv[k][i].w += bp[i].w;
+                sum += hv[k][i].x + hv[k][i].y + hv[k][i].z + hv[k][i].w;
+            }
+            const float mean = wave_sum(sum) / (float)E;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const float a = hv[k][i].x - mean, b = hv[k][i].y - mean, c = hv[k][i].z - mean, d = hv[k][i].w - mean;
+                q += a * a + b * b + c * c + d * d;
+            }
+            const float rstd = rsqrtf(wave_sum(q) / (float)E + 1e-5f);
+            if (mean_a && lane == 0 && row < rend) { mean_a[row] = mean; rstd_a[row] = rstd; }
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const float4 h4 = hv[k][i];
+                bf16x4 o;
+                o[0] = f2bf((h4.x - mean) * rstd * gm[i].x + bt[i].x); o[1] = f2bf((h4.y - mean) * rstd * gm[i].y + bt[i].y);
+                o[2] = f2bf((h4.z - mean) * rstd * gm[i].z + bt[i].z); o[3] = f2bf((h4.w - mean) * rstd * gm[i].w + bt[i].w);
+                {
+                    *reinterpret_cast<bf16x4*>(Zs + lr * ldz + cc[i]) = o;
+                    if (z && row < rend) *reinterpret_cast<bf16x4*>(z + (size_t)row * E + cc[i]) = o;
+                }
+                s[half * RB + k][i] = make_float4(h4.x + xv[k][i].x, h4.y + xv[k][i].y, h4.z + xv[k][i].z, h4.w + xv[k][i].w);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: pre = z Wd^T + b_down, activation (LDS only)
+    {
+        float v[AF_CPT];
+        af_first_product(Zs, ldz, wd, E, red, wid, lane, tid, v);
+        constexpr int TPR = 64 / AF_CPT;
+        const int lr = tid / TPR, c0 = (tid % TPR) * AF_CPT, row = r0 + lr;
+        bf16 o[AF_CPT], pre8[AF_CPT];
+#pragma unroll
+        for (int i = 0; i < AF_CPT; ++i) {
+            const float pv = v[i] + b_down[c0 + i];
+            if constexpr (ACT == 0) { o[i] = f2bf(fmaxf(pv, 0.0f)); pre8[i] = o[i]; }
+            else { pre8[i] = f2bf(pv); o[i] = f2bf(gelu_new_f(bf2f(pre8[i]))); }
+        }
+        af_store_mid(As + lr * 72 + c0, act + (size_t)min(row, last) * 64 + c0, act && row < rend, o);
+        if constexpr (ACT == 1) {
+            if (apre && row < rend) {
+                af_put_mid(apre + (size_t)row * 64 + c0, pre8);
+            }
+        }
+    }
+    __syncthreads();                                            // As complete; Zs / red are dead: U may overwrite them
+    // ---- phase 3: U = act Wu^T
+    af_second_product(As, wu, E, U, wid, lane);
+    __syncthreads();
+    // ---- phase 4: x_out = (x_mid + h) + U + b_up
+#pragma unroll
+    for (int k = 0; k < AF_RPW; ++k) {
+        const int lr = wid * AF_RPW + k, row = r0 + lr;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            if (row < rend) {
+                const float4 u = *reinterpret_cast<const float4*>(U + lr * (E + 4) + cc[i]);
+                const float4 b = *reinterpret_cast<const float4*>(b_up + cc[i]);
+                float4 o;
+                o.x = s[k][i].x + (u.x + b.x); o.y = s[k][i].y + (u.y + b.y); o.z = s[k][i].z + (u.z + b.z); o.w = s[k][i].w + (u.w + b.w);
+                *reinterpret_cast<float4*>(x_out + (size_t)row * E + cc[i]) = o;
+            }
+        }
+    }
+}
+
 // ---- the token-contracted weight gradients in the shadow of the backward workgroups -------------------------------------------
 // adapter_bwd_kernel keeps ONE workgroup on 200 of the 256 CUs for ~27 us (T = 6400; its LDS block admits no second one); the two
 // G[e][j] = sum_r X[r][e] Y[r][j] products of an adapter (d W_up = dx_out^T act, d W_down = z^T d pre: tn_gemm64_kernel, 8.5 us
@@ -635,6 +782,15 @@ int af_launch_fwd(const AdapterFwdArgs& a, int rb, int lds, hipStream_t s) {
     return 0;
 }
 template <auto KERN>
+int af_launch_fwd_seg(const AdapterFwdSegArgs& a, const AfSegTable& tab, int grid, int lds, hipStream_t s) {
+    if (reserve_lds<KERN, 160 * 1024>("adapter_fwd_seg")) return -1;
+    // (z, mean_a, rstd_a, act, apre: null -- the inference form stores none of them)
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(64 * AF_WAVES), lds, s, a.hraw, a.bpr, a.x_mid, a.x_out, (bf16*)nullptr, (float*)nullptr,
+                       (float*)nullptr, (bf16*)nullptr, (bf16*)nullptr, a.E, tab);
+    LAUNCH_OK("adapter_fwd_seg_kernel");
+    return 0;
+}
+template <auto KERN>
 int af_launch_bwd(const AdapterBwdArgs& a, int rb, int nb, int ntn, const AfTn& tn, int lds, hipStream_t s) {
     if (reserve_lds<KERN, 160 * 1024>("adapter_bwd")) return -1;
     hipLaunchKernelGGL(KERN, dim3(nb + ntn), dim3(64 * AF_WAVES), lds, s, a.dyb, a.dres, a.wuT, a.saved, a.wdT, a.hraw, a.bpr, a.mean_a, a.rstd_a,
@@ -668,6 +824,35 @@ int pevit_launch_adapter_fwd(const AdapterFwdArgs& a, hipStream_t s) {
         case 6: return af_launch_fwd<adapter_fwd_kernel<1, 3>>(a, rb, lds, s);
         case 7: return af_launch_fwd<adapter_fwd_kernel<1, 4>>(a, rb, lds, s);
     }
+    return -1;
+}
+
+// one launch for all segments: the grid is the sum of the segments' tiles
+int pevit_launch_adapter_fwd_seg(const AdapterFwdSegArgs& a, hipStream_t s) {
+    const char* who = "adapter_fwd_seg";
+    const int E = a.E;
+    if (!pevit_adapter_fused_ok(E)) { pevit_set_error("%s: unsupported width E=%d (E a multiple of 256, <= 1024)", who, E); return -1; }
+    if (a.nseg < 1 || a.nseg > PEVIT_MAX_SEGMENTS) { pevit_set_error("%s: %d segments outside [1,%d]", who, a.nseg, PEVIT_MAX_SEGMENTS); return -1; }
+    if (!a.hraw || !a.bpr || !a.x_mid || !a.x_out) { pevit_set_error("%s: null argument", who); return -1; }
+    AfSegTable tab{};
+    tab.nseg = a.nseg;
+    long grid = 0;
+    for (int i = 0; i < a.nseg; ++i) {
+        const AdapterSegment& g = a.seg[i];
+        if (g.first < 0 || g.end <= g.first) { pevit_set_error("%s: segment %d is rows [%d, %d): empty", who, i, g.first, g.end); return -1; }
+        if (!g.gamma || !g.beta || !g.wd || !g.b_down || !g.wu || !g.b_up) { pevit_set_error("%s: segment %d: null argument", who, i); return -1; }
+        tab.first[i] = g.first; tab.end[i] = g.end; tab.wg0[i] = (int)grid;
+        tab.gamma[i] = g.gamma; tab.beta[i] = g.beta; tab.wd[i] = g.wd; tab.b_down[i] = g.b_down; tab.wu[i] = g.wu; tab.b_up[i] = g.b_up;
+        grid += ceil_div(g.end - g.first, AF_ROWS);
+    }
+    if (grid > 0x7fffffffL) { pevit_set_error("%s: %ld workgroups", who, grid); return -1; }
+    const int lds = af_layout(E).colred;
+#define AF_SEG_CASE(A, N) case 4 * A + N - 1: return af_launch_fwd_seg<adapter_fwd_seg_kernel<A, N>>(a, tab, (int)grid, lds, s);
+    switch (4 * (a.act_kind != 0) + E / 256 - 1) {
+        AF_SEG_CASE(0, 1) AF_SEG_CASE(0, 2) AF_SEG_CASE(0, 3) AF_SEG_CASE(0, 4)
+        AF_SEG_CASE(1, 1) AF_SEG_CASE(1, 2) AF_SEG_CASE(1, 3) AF_SEG_CASE(1, 4)
+    }
+#undef AF_SEG_CASE
     return -1;
 }
 

@@ -72,7 +72,7 @@ WsLayout layout_workspace(const pevit_ctx* c, int B, bool infer) {
         }
         s.xn1 = cv.take(T * E * es);
         s.qkv = cv.take(3 * T * E * es);
-        s.t = cv.take(T * 64 * 4 * (c->slots ? c->slots + 1 : 1));      // (multi-slot context: the columns of every slot + the single-adapter calls')
+        s.t = cv.take(T * 64 * 4 * (site_slots(c) ? site_slots(c) + 1 : 1));      // (multi-slot context: the columns of every slot + the single-adapter calls')
         s.lse = cv.take((size_t)B * c->H * c->N * 4);
         s.attn_out = cv.take(T * E * es);
         if (!infer) s.h = cv.take(T * 4 * E * es);
@@ -204,8 +204,14 @@ static void carve_block_arena(pevit_ctx* c, Carver& cv) {
         b.bqkv = cv.take(3 * E * 4); b.bo = cv.take(E * 4); b.bfc = cv.take(4 * E * 4); b.bpr = cv.take(E * 4);
         b.ln1w = cv.take(E * 4); b.ln1b = cv.take(E * 4); b.ln2w = cv.take(E * 4); b.ln2b = cv.take(E * 4);
         b.q32 = cv.take(E * 64 * 4); b.qT = cv.take(64 * E * c->es); b.q16 = cv.take(E * 64 * 2);
-        b.q16s = c->slots ? cv.take(c->slots * q16_slot_bytes(c)) : 0;
-        if (c->infer_only) { b.wd = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); continue; }
+        b.q16s = site_slots(c) ? cv.take(site_slots(c) * q16_slot_bytes(c)) : 0;
+        b.wds = b.wus = 0;
+        if (c->infer_only) {
+            b.wd = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es);
+            // post-MLP slot context: the panels of every slot behind those of the single-adapter calls
+            if (post_mlp(c) && c->slots) { b.wds = cv.take(c->slots * pm_slot_bytes(c)); b.wus = cv.take(c->slots * pm_slot_bytes(c)); }
+            continue;
+        }
         b.wd = cv.take(64 * E * c->es); b.wdT = cv.take(64 * E * c->es); b.wu = cv.take(64 * E * c->es); b.wuT = cv.take(64 * E * c->es);
     }
 }
@@ -292,7 +298,7 @@ static int create_image_ctx(const pevit_dims* dims, pevit_ctx** out, bool infer_
     c->G2 = grid * grid; c->N = c->G2 + 1; c->D = d.out_dim; c->C = d.num_classes;
     c->Kpatch = (int)align_up((size_t)3 * d.patch * d.patch, 64);
     c->slots = slots;
-    c->NQ = 3 * c->E + 64 * (slots + 1); c->NQpad = (int)align_up((size_t)c->NQ, 128);
+    c->NQ = 3 * c->E + 64 * (site_slots(c) + 1); c->NQpad = (int)align_up((size_t)c->NQ, 128);
     c->ascale = d.method == PEVIT_LORA ? 128.0f / (float)d.lora_rank : 160.0f;
     c->fp8act = d.weight_format == PEVIT_W_FP8_ACT;
     c->fp8 = d.weight_format == PEVIT_W_FP8_E4M3 || c->fp8act;
@@ -373,6 +379,10 @@ extern "C" int pevit_infer_create_slots(const pevit_dims* dims, int slots, pevit
 extern "C" int pevit_load_adapter_slot(pevit_ctx* c, void* stream, int slot, const float* params, int num_classes) {
     if (!c || !params) { pevit_set_error("load_adapter_slot: null argument"); return -1; }
     if (!c->slots) { pevit_set_error("load_adapter_slot: this context has no adapter slots (pevit_infer_create_slots)"); return -1; }
+    if (c->d.method == PEVIT_COMPACTER) {
+        pevit_set_error("load_adapter_slot: a Compacter slot needs the adapter's frozen phm_rule: pevit_load_adapter_slot_rule takes it");
+        return -1;
+    }
     if (!c->arena) { pevit_set_error("load_adapter_slot: context not bound"); return -1; }
     if (slot < 0 || slot >= c->slots) { pevit_set_error("load_adapter_slot: slot %d outside [0,%d)", slot, c->slots); return -1; }
     if (num_classes < 1 || num_classes > c->d.num_classes) {
@@ -380,6 +390,45 @@ extern "C" int pevit_load_adapter_slot(pevit_ctx* c, void* stream, int slot, con
     }
     c->slot_params[slot] = nullptr;
     CHECK(prep_adapters(c, (hipStream_t)stream, slot, params));
+    c->slot_params[slot] = params; c->slot_classes[slot] = num_classes;
+    return 0;
+}
+
+// Slot contexts for all four methods (include/pevit_segments_all.h).  The attention-site methods: pevit_infer_create_slots itself.
+// The post-MLP methods: per layer and slot one down and one up panel in the arena (carve_block_arena: wds, wus); the workspace is
+// that of pevit_infer_create.
+extern "C" int pevit_infer_create_slots_all(const pevit_dims* dims, int slots, pevit_ctx** out) {
+    const char* who = "infer_create_slots_all";
+    if (!dims || !out) { pevit_set_error("%s: null argument", who); return -1; }
+    if (dims->method == PEVIT_KADAPTATION || dims->method == PEVIT_LORA) return pevit_infer_create_slots(dims, slots, out);
+    if (slots < 1 || slots > PEVIT_MAX_SLOTS) { pevit_set_error("%s: %d slots outside [1,%d]", who, slots, PEVIT_MAX_SLOTS); return -1; }
+    const char* why = nullptr;
+    if (dims->method == PEVIT_NONE) why = "method none has no adapter to keep in a slot";
+    else if (dims->weight_format == PEVIT_W_FP8_E4M3 || dims->weight_format == PEVIT_W_FP8_ACT)
+        why = "the fp8 weight formats are not served by segments; slots are built for bf16";
+    else if (dims->weight_format == PEVIT_W_F32_VERIFY) why = "the f32 verification mode has no segmented kernels";
+    if (why && slots > 1) { pevit_set_error("%s: %d slots: %s", who, slots, why); return -1; }
+    return create_image_ctx(dims, out, true, who, (why || slots == 1) ? 0 : slots);
+}
+
+// pevit_load_adapter_slot with Compacter's frozen rule: read from the caller's buffer while the panels are built, never through
+// the arena's a_phm (which belongs to the adapter the single-adapter calls selected).
+extern "C" int pevit_load_adapter_slot_rule(pevit_ctx* c, void* stream, int slot, const float* params, int num_classes, const float* phm_rule) {
+    const char* who = "load_adapter_slot_rule";
+    if (!c || !params) { pevit_set_error("%s: null argument", who); return -1; }
+    if (!c->slots) { pevit_set_error("%s: this context has no adapter slots (pevit_infer_create_slots_all)", who); return -1; }
+    if (c->d.method == PEVIT_COMPACTER) {
+        if (!phm_rule) { pevit_set_error("%s: a Compacter slot needs the adapter's frozen phm_rule", who); return -1; }
+    } else if (phm_rule) {
+        pevit_set_error("%s: only Compacter has a phm_rule; this context takes NULL (or pevit_load_adapter_slot)", who); return -1;
+    }
+    if (!c->arena) { pevit_set_error("%s: context not bound", who); return -1; }
+    if (slot < 0 || slot >= c->slots) { pevit_set_error("%s: slot %d outside [0,%d)", who, slot, c->slots); return -1; }
+    if (num_classes < 1 || num_classes > c->d.num_classes) {
+        pevit_set_error("%s: num_classes %d outside [1,%d] of the context", who, num_classes, c->d.num_classes); return -1;
+    }
+    c->slot_params[slot] = nullptr;
+    CHECK(prep_adapters(c, (hipStream_t)stream, slot, params, phm_rule));
     c->slot_params[slot] = params; c->slot_classes[slot] = num_classes;
     return 0;
 }

@@ -40,6 +40,7 @@ struct BlockArena {        // byte offsets inside the weight arena, one per laye
     size_t sqkv, so, sfc, spr;    // fp8 weights only: per-output-channel scales (f32, powers of two)
     size_t tsink;                 // inference-only contexts: [E][64] write-only panel that takes the transposed stores of the prep kernels
     size_t q16s;                  // multi-slot contexts: the [E][64] bf16 Q panels of the slots, q16_slot_bytes apart (q16: the single-adapter calls')
+    size_t wds, wus;              // post-MLP slot contexts: the [64][E] down / [E][64] up bf16 panels of the slots, pm_slot_bytes apart (wd, wu: the single-adapter calls')
 };
 
 struct LayerSaved {        // byte offsets inside the workspace, one per layer (kept for backward)
@@ -107,7 +108,9 @@ struct pevit_ctx {
     bool infer_only = false;  // pevit_infer_create: no transposed weight copies, the third workspace layout, no gradients; runs the inference walk only
     // multi-slot context (pevit_infer_create_slots; 0: none).  Rows [3E + 64 s, + 64) of wqkv hold slot s's P rows, the rows behind
     // the last slot those of the single-adapter calls, which prep_adapters rebuilds per call: NQ = 3E + 64 (slots + 1) covers them,
-    // a segmented call's product stops at 3E + 64 slots
+    // a segmented call's product stops at 3E + 64 slots.
+    // Post-MLP methods (pevit_infer_create_slots_all): `slots` counts the same, but nothing of the above grows (site_slots() is 0):
+    // a slot is two panels per layer (BlockArena::wds, wus), and the workspace is that of pevit_infer_create
     int slots = 0;
     const float* slot_params[PEVIT_MAX_SLOTS] = {};     // pevit_load_adapter_slot: the flat buffer of each slot (null: not loaded) ...
     int slot_classes[PEVIT_MAX_SLOTS] = {};             // ... and its class count
@@ -175,6 +178,10 @@ inline bool attention_site(const pevit_ctx* c) {
 // bytes between the Q panels of two slots of a layer
 inline size_t q16_slot_bytes(const pevit_ctx* c) { return align_up((size_t)c->E * 64 * 2, 256); }
 inline bool post_mlp(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER || c->d.method == PEVIT_COMPACTER; }
+// slots of the attention site (rows of wqkv, Q panels, columns of t): those of a multi-slot context of an attention-site method
+inline int site_slots(const pevit_ctx* c) { return post_mlp(c) ? 0 : c->slots; }
+// bytes between the down (or up) panels of two slots of a layer of a post-MLP slot context
+inline size_t pm_slot_bytes(const pevit_ctx* c) { return align_up((size_t)c->E * 64 * c->es, 256); }
 // activation of the post-MLP bottleneck as the fused kernels take it: 0 = ReLU (Adapter), 1 = gelu_new (Compacter)
 inline int act_kind(const pevit_ctx* c) { return c->d.method == PEVIT_ADAPTER ? 0 : 1; }
 
@@ -199,7 +206,7 @@ void prof_close(pevit_ctx* c, hipStream_t s, int slot, double flops, double byte
 int gemm(pevit_ctx* c, int epi, const GemmParams& p_in, hipStream_t s);
 
 // ---- walk.hip ----
-int prep_adapters(pevit_ctx* c, hipStream_t s, int slot = -1, const float* params = nullptr);
+int prep_adapters(pevit_ctx* c, hipStream_t s, int slot = -1, const float* params = nullptr, const float* phm_rule = nullptr);
 int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, unsigned char* a8, unsigned char* attn8);
 int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool cls_only, int l_lo = 0, int l_hi = -1);
 int attn_core_bwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, bool cls, AttnGradWalk& w);

@@ -373,6 +373,20 @@ struct AdapterFwdArgs {
     float* x_out = nullptr; int T = 0, E = 0;
 };
 int pevit_launch_adapter_fwd(const AdapterFwdArgs& a, hipStream_t s);
+// The segmented inference form (pevit_predict_segments on a post-MLP slot context): rows [first, end) of hraw / x_mid / x_out belong
+// to a segment with its own LayerNorm affine, panels and biases.  A workgroup never crosses a segment end, and nothing that only a
+// backward reads is stored.  x_out of a segment = pevit_launch_adapter_fwd on that segment's rows alone, bit for bit.
+struct AdapterSegment {
+    int first = 0, end = 0;             // rows [first, end) of the [T][E] buffers
+    const float* gamma = nullptr; const float* beta = nullptr; const bf16* wd = nullptr; const float* b_down = nullptr;
+    const bf16* wu = nullptr; const float* b_up = nullptr;
+};
+struct AdapterFwdSegArgs {
+    int act_kind = 0;
+    const float* hraw = nullptr; const float* bpr = nullptr; const float* x_mid = nullptr; float* x_out = nullptr; int E = 0;
+    int nseg = 0; AdapterSegment seg[PEVIT_MAX_SEGMENTS];
+};
+int pevit_launch_adapter_fwd_seg(const AdapterFwdSegArgs& a, hipStream_t s);
 // saved = act (ReLU) / apre (gelu_new); partial: [pevit_lna_blocks(T)][3][E] like ln_bwd_affine
 struct AdapterBwdArgs {
     int act_kind = 0;

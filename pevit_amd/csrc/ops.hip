@@ -159,6 +159,21 @@ extern "C" int pevit_op_attn_fwd_delta_seg(void* stream, const void* q, const vo
     if (seg_args(a, "attn_fwd_delta_seg", nseg, segs)) return -1;
     return pevit_launch_attn_fwd_delta_seg(a, (hipStream_t)stream);
 }
+// the segmented inference launch of the fused post-MLP adapter forward (adapter_fused.hip): AdapterFwdSegArgs by name
+extern "C" int pevit_op_adapter_fwd_seg(void* stream, const pevit_adapter_fwd_seg_args* a) {
+    const char* who = "adapter_fwd_seg";
+    if (!a) { pevit_set_error("%s: null argument struct", who); return -1; }
+    if (!a->segs || a->nseg < 1 || a->nseg > PEVIT_MAX_SEGMENTS) { pevit_set_error("%s: %d segments outside [1,%d]", who, a->nseg, PEVIT_MAX_SEGMENTS); return -1; }
+    AdapterFwdSegArgs p;
+    p.act_kind = a->act_kind; p.E = a->E; p.hraw = a->hraw; p.bpr = a->bpr; p.x_mid = a->x_mid; p.x_out = a->x_out; p.nseg = a->nseg;
+    for (int i = 0; i < a->nseg; ++i) {
+        const pevit_adapter_seg& g = a->segs[i];
+        AdapterSegment& o = p.seg[i];
+        o.first = g.first; o.end = g.end; o.gamma = g.gamma; o.beta = g.beta; o.wd = (const bf16*)g.wd; o.b_down = g.b_down;
+        o.wu = (const bf16*)g.wu; o.b_up = g.b_up;
+    }
+    return pevit_launch_adapter_fwd_seg(p, (hipStream_t)stream);
+}
 extern "C" int pevit_debug_occupy(void* stream, int workgroups, int lds_bytes, double microseconds) {
     return pevit_launch_occupy(workgroups, lds_bytes, microseconds, (hipStream_t)stream);
 }

@@ -23,7 +23,8 @@ static AdapterPanels panels(pevit_ctx* c, int l, int slot = -1) {
 
 // rebuild the bf16 adapter panels of every layer from the f32 master parameters (one launch).  slot >= 0 (pevit_load_adapter_slot):
 // the panels of that slot of a multi-slot context from `params`; otherwise those of the single-adapter calls from c->params
-int prep_adapters(pevit_ctx* c, hipStream_t s, int slot, const float* params) {
+// phm_rule (Compacter, slot >= 0): the slot's frozen rule, read from the caller's buffer; the single-adapter calls read the arena's
+int prep_adapters(pevit_ctx* c, hipStream_t s, int slot, const float* params, const float* phm_rule) {
     const size_t E = c->E;
     LayerStrides st;
     st.arena_bytes = c->L > 1 ? c->blk[1].wqkv - c->blk[0].wqkv : 0;
@@ -47,11 +48,15 @@ int prep_adapters(pevit_ctx* c, hipStream_t s, int slot, const float* params) {
         // (an inference-only context has neither wdT nor wuT: both transposed stores go to its write-only panel, nobody reads them)
         BottleneckPanels bp{at<bf16>(c->arena, b0.wd), at<bf16>(c->arena, c->infer_only ? b0.tsink : b0.wdT), at<bf16>(c->arena, b0.wu),
                             at<bf16>(c->arena, c->infer_only ? b0.tsink : b0.wuT)};
+        if (slot >= 0) {        // a slot of a post-MLP slot context (inference-only): its own down and up panels, the same write-only sink
+            bp.wd = at<bf16>(c->arena, b0.wds + (size_t)slot * pm_slot_bytes(c));
+            bp.wu = at<bf16>(c->arena, b0.wus + (size_t)slot * pm_slot_bytes(c));
+        }
         if (c->d.method == PEVIT_ADAPTER) {
             CHECK(pevit_launch_prep_adapter(lp + c->o_dw, lp + c->o_uw, bp, c->E, c->L, st, s, c->f32));
         } else {
             PrepCompacterArgs a;
-            a.rule = at<float>(c->arena, c->a_phm); a.dWl = lp + c->o_dWl; a.dWr = lp + c->o_dWr; a.uWl = lp + c->o_uWl; a.uWr = lp + c->o_uWr;
+            a.rule = slot >= 0 ? phm_rule : at<float>(c->arena, c->a_phm); a.dWl = lp + c->o_dWl; a.dWr = lp + c->o_dWr; a.uWl = lp + c->o_uWl; a.uWr = lp + c->o_uWr;
             a.pan = bp; a.E = c->E; a.layers = c->L; a.st = st; a.f32 = c->f32;
             CHECK(pevit_launch_prep_compacter(a, s));
         }
@@ -119,7 +124,7 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
     const LayerSaved& v = c->lay.sav[l];
     bf16* qkv = at<bf16>(W, v.qkv);
     const size_t plane = (size_t)T * E;
-    if (c->slots) return attn_core_fwd_slots(c, s, B, pl, l);
+    if (site_slots(c)) return attn_core_fwd_slots(c, s, B, pl, l);
     if (!c->fp8) {
         GemmParams p = gp(at<bf16>(W, v.xn1), E, at<bf16>(A, b.wqkv), E, c->NQpad, T, site ? c->NQ : 3 * E, E);
         p.bias = at<float>(A, b.bqkv); p.outb = qkv; p.head_stride = plane; p.outf = at<float>(W, v.t); p.ldo = 64;
@@ -173,6 +178,74 @@ int attn_core_fwd(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l,
         } else {
             if (pl.infer) a.lse = nullptr;
             PROF(c, s, PEVIT_PROF_ATTN_FWD, T, (double)T * E * 4 * 2 + (pl.infer ? 0.0 : (double)B * H * N * 4), pevit_launch_attn_fwd(a, s));
+        }
+    }
+    return 0;
+}
+
+// The post-MLP adapter of block l in a segmented call (pevit_predict_segments on a post-MLP slot context): c_proj runs once on all
+// rows, the adapter per segment on the panels of the segment's slot and the f32 vectors of the slot's flat buffer.
+//   fused route:   ONE adapter_fwd_seg launch, whose workgroups never cross a segment end;
+//   unfused route: LayerNorm, down and up product per segment on its row range -- the launches pevit_predict makes for those rows alone.
+static int post_mlp_fwd_segments(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, int l, const float* x_mid, float* x_out) {
+    const int E = c->E, N = c->N, T = B * N;
+    char* W = c->ws; char* A = c->arena;
+    const BlockArena& b = c->blk[l];
+    const LayerSaved& v = c->lay.sav[l];
+    const size_t poff = c->p_layer0 + c->p_layer_stride * l;           // layer l's parameters in a flat buffer
+    auto wd_of = [&](int slot) { return at<bf16>(A, b.wds + (size_t)slot * pm_slot_bytes(c)); };
+    auto wu_of = [&](int slot) { return at<bf16>(A, b.wus + (size_t)slot * pm_slot_bytes(c)); };
+    if (pl.adapter_fused) {
+        GemmParams p = gp(at<bf16>(W, c->lay.w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
+        p.outf = at<float>(W, v.hf32); p.ldo = E;
+        CHECK(gemm(c, EPI_F32, p, s));
+        AdapterFwdSegArgs a;
+        a.act_kind = act_kind(c); a.hraw = at<float>(W, v.hf32); a.bpr = at<float>(A, b.bpr); a.x_mid = x_mid; a.x_out = x_out; a.E = E;
+        a.nseg = c->nseg;
+        for (int i = 0; i < c->nseg; ++i) {
+            const pevit_segment& g = c->segs[i];
+            const float* lp = c->slot_params[g.slot] + poff;
+            AdapterSegment& o = a.seg[i];
+            o.first = g.first * N; o.end = (g.first + g.count) * N;
+            o.gamma = lp + c->o_nw; o.beta = lp + c->o_nb; o.wd = wd_of(g.slot); o.b_down = lp + c->o_db; o.wu = wu_of(g.slot); o.b_up = lp + c->o_ub;
+        }
+        PROF(c, s, PEVIT_PROF_ADAPTER_FWD, T, (double)T * E * (4 + 4 + 4) + (double)c->nseg * 2 * 64 * E * 2, pevit_launch_adapter_fwd_seg(a, s));
+        return 0;
+    }
+    float* ytmp = at<float>(W, c->lay.w_dxn);           // x_mid + h
+    {
+        GemmParams p = gp(at<bf16>(W, c->lay.w_g), 4 * E, at<bf16>(A, b.wpr), 4 * E, E, T, E, 4 * E);
+        p.bias = at<float>(A, b.bpr); p.resid = x_mid; p.ldr = E; p.outf = ytmp; p.ldo = E;
+        p.outf2 = at<float>(W, v.hf32); p.ldo2 = E;
+        CHECK(gemm(c, EPI_BIAS_RESID_KEEP, p, s));
+    }
+    for (int i = 0; i < c->nseg; ++i) {
+        const pevit_segment& g = c->segs[i];
+        const float* lp = c->slot_params[g.slot] + poff;
+        const size_t r0 = (size_t)g.first * N;
+        const int Ts = g.count * N;
+        bf16* z = at<bf16>(W, v.z) + r0 * E;
+        bf16* act = at<bf16>(W, v.act) + r0 * 64;
+        {
+            LnFwdArgs a;
+            a.x = at<float>(W, v.hf32) + r0 * E; a.gamma = lp + c->o_nw; a.beta = lp + c->o_nb; a.rows = Ts; a.E = E; a.y_bf16 = z;
+            CHECK(pevit_launch_ln_fwd(a, s));
+        }
+        {
+            GemmParams p = gp(z, E, wd_of(g.slot), E, 64, Ts, 64, E);
+            p.bias = lp + c->o_db;
+            if (c->d.method == PEVIT_ADAPTER) {
+                p.outb = act; p.ldob = 64;
+                CHECK(gemm(c, EPI_BIAS_RELU_BF16, p, s));
+            } else {
+                p.outb = at<bf16>(W, v.apre) + r0 * 64; p.ldob = 64; p.outb2 = act; p.ldob2 = 64;
+                CHECK(gemm(c, EPI_BIAS_GELUNEW, p, s));
+            }
+        }
+        {
+            GemmParams p = gp(act, 64, wu_of(g.slot), 64, E, Ts, E, 64);
+            p.bias = lp + c->o_ub; p.resid = ytmp + r0 * E; p.ldr = E; p.outf = x_out + r0 * E; p.ldo = E;
+            CHECK(gemm(c, EPI_BIAS_RESID_F32, p, s));
         }
     }
     return 0;
@@ -243,6 +316,10 @@ int blocks_forward(pevit_ctx* c, hipStream_t s, int B, const StepPlan& pl, bool 
             continue;
         }
         // x = x + [h + up(act(down(LN_a(h))))]         adapter_model.py:330-336 / compacter_model.py:497-503
+        if (pl.segments) {          // (no adapter need be selected: every operand comes from the segments' slots)
+            CHECK(post_mlp_fwd_segments(c, s, B, pl, l, x_mid, x_out));
+            continue;
+        }
         const float* lp = c->params + c->p_layer0 + c->p_layer_stride * l;
         if (pl.adapter_fused) {
             // two launches (adapter_fused.hip): c_proj writes its accumulators once (the bias joins in the adapter kernel), then

@@ -11,7 +11,8 @@ is ``HipEngine.predict`` / ``encode_image`` / ``zeroshot`` bit for bit -- the sa
     eng.use("cifar100")
     logits = eng.predict(images)            # any number of images, in chunks of max_batch
 
-With ``slots=2..8`` (``pevit_infer_create_slots``, include/pevit_segments.h; KAdaptation and LoRA in bf16) requests for different
+With ``slots=2..8`` (``pevit_infer_create_slots`` / ``pevit_infer_create_slots_all``, include/pevit_segments.h and
+pevit_segments_all.h; all four methods, in bf16) requests for different
 resident adapters are answered in ONE walk of the tower, each as ``use(name); predict(images)`` would answer it alone::
 
     eng = InferenceEngine(arch, "kadaptation", max_classes=100, max_batch=128, slots=8)
@@ -129,8 +130,10 @@ class InferenceEngine(EngineContext, InputMixin):
         self._resize_buf, self._resize_cache = None, {}  # resize_u8: its staging (on first use), (h, w, crop) -> device tables
 
     def _create_slots(self, dims):
-        """``EngineContext._create`` through the entry that takes a slot count."""
-        _lib.check(self.lib.pevit_infer_create_slots(C.byref(dims), self.slots, C.byref(self._ctx)), "pevit_infer_create_slots")
+        """``EngineContext._create`` through the entry that takes a slot count: the post-MLP methods through
+        ``pevit_infer_create_slots_all`` (include/pevit_segments_all.h), the attention-site methods through the entry they always used."""
+        entry = "pevit_infer_create_slots_all" if self.method in ("adapter", "compacter") else "pevit_infer_create_slots"
+        _lib.check(getattr(self.lib, entry)(C.byref(dims), self.slots, C.byref(self._ctx)), entry)
         self.arena = torch.zeros(self.lib.pevit_arena_bytes(self._ctx), dtype=torch.uint8, device=self.device)
         self._bind(self.max_batch)
 
@@ -275,6 +278,10 @@ class InferenceEngine(EngineContext, InputMixin):
     # ------------------------------------------------------------------ requests for several adapters in one walk
     def _load_slot(self, slot, name):
         a = self._adapters[name]
+        if a["phm_rule"] is not None:       # Compacter: the slot's frozen rule, read while its panels are built
+            _lib.check(self.lib.pevit_load_adapter_slot_rule(self._ctx, _lib.stream_ptr(), slot, _lib.ptr(a["params"]), a["num_classes"],
+                                                             _lib.ptr(a["phm_rule"])), "pevit_load_adapter_slot_rule")
+            return
         _lib.check(self.lib.pevit_load_adapter_slot(self._ctx, _lib.stream_ptr(), slot, _lib.ptr(a["params"]), a["num_classes"]),
                    "pevit_load_adapter_slot")
 
@@ -356,7 +363,9 @@ class InferenceEngine(EngineContext, InputMixin):
         and run through ``predict_segments``, then scattered back into the order they came in.
         EACH NAME'S ROWS FORM ONE BATCH for the raw reshape of the adapter delta: a row's logits are those of ``use(name);
         predict(all rows of that name, in their order)`` -- they depend on the other rows of the SAME name in this call, as an
-        image's logits depend on its batch in ``predict``, and on no row of another name."""
+        image's logits depend on its batch in ``predict``, and on no row of another name.  That is the attention-site methods
+        (KAdaptation, LoRA); the post-MLP methods (Adapter, Compacter) are row-wise and have no raw reshape: there a row's logits
+        depend on no other row."""
         names = list(names)
         if not torch.is_tensor(images):
             raise _lib.PevitError(f"predict_mixed takes one tensor of images; a ragged batch ({type(images).__name__}) is served by use + predict")

@@ -20,6 +20,8 @@ route alone is built and timed (a process per round, to alternate two builds of 
 --segments: instead of the above, the segmented leg (profiles/serving.md; ``segments_leg`` below): eight requests of 16 images for
 eight resident adapters as a loop of ``use`` + ``predict`` against ONE ``predict_segments`` call, and the cost of a ``slots = 8``
 context.  --segments-one-pass ROUTE: nothing but STEPS calls of that route (the process to put under rocprofv3).
+--method kadaptation|lora|adapter|compacter: the method of the --serving and --segments legs (default kadaptation; the post-MLP
+methods: profiles/serving_segments.md).
 Prints one JSON object.  usage: python scripts/predict_rate.py [--steps 20] [--reps 3] [--profile] [--serving] [--out FILE]"""
 import argparse
 import dataclasses
@@ -127,7 +129,12 @@ def profile(model, bs):
     return out
 
 
-def serving_sizes(lib):
+def rule_of(method, seed=11):
+    """Compacter's frozen (4,4,4) rule, which the synthetic state dict leaves zero; None for the other methods"""
+    return torch.rand((4, 4, 4), generator=torch.Generator().manual_seed(seed)) * 2 - 1 if method == "compacter" else None
+
+
+def serving_sizes(lib, method="kadaptation"):
     """arena / workspace bytes of the training and the inference-only context, from the size queries (no allocation)"""
     import ctypes as C
     from pevit_amd import _lib
@@ -135,7 +142,7 @@ def serving_sizes(lib):
     out = {}
     for name in ("ViT-B/32", "ViT-B/16", "ViT-L/14"):
         a = ARCHS[name]
-        d = _lib.PevitDims(a.width, a.layers, a.patch, a.resolution, a.embed_dim, _lib.METHOD_IDS["kadaptation"], 4, 100, _lib.WEIGHT_FORMATS["bf16"])
+        d = _lib.PevitDims(a.width, a.layers, a.patch, a.resolution, a.embed_dim, _lib.METHOD_IDS[method], 4, 100, _lib.WEIGHT_FORMATS["bf16"])
         row = {}
         for kind, creator in (("train", "pevit_ctx_create"), ("serving", "pevit_infer_create")):
             if not hasattr(lib, creator):
@@ -149,28 +156,31 @@ def serving_sizes(lib):
     return out
 
 
-def serving_leg(steps, reps, route):
+def serving_leg(steps, reps, route, method="kadaptation"):
     from pevit_amd import _lib
     from pevit_amd.engine import HipEngine, adapter_param_spec
     from pevit_amd.synth import ARCHS, randomize_adapters, synth_state_dict
     dev = torch.device("cuda", 0)
-    arch, method, classes = ARCHS["ViT-B/32"], "kadaptation", 100
+    arch, classes = ARCHS["ViT-B/32"], 100
     sd = {k: v for k, v in synth_state_dict(arch, seed=2, text_tower=False).items() if k.startswith("visual.")}
     ad = [(n, torch.zeros(s)) for n, s, _ in adapter_param_spec(method, arch.width, arch.layers)]
     randomize_adapters(ad, seed=3)
     sd.update(dict(ad))
     eng = HipEngine(arch, method, classes, 128)
     eng.load_state_dict(sd)
+    rule = rule_of(method)
+    if rule is not None:
+        eng.load_phm_rule(rule)
     g = torch.Generator().manual_seed(5)
     v = eng.param_views()
     with torch.no_grad():
         v["layers.0.weight"].copy_(((torch.rand((classes, 512), generator=g) * 2 - 1) / 512 ** 0.5).cuda())
         eng.running_var.copy_((0.5 + torch.rand(512, generator=g)).cuda())
-    routes, out = {}, {"sizes": serving_sizes(eng.lib)}
+    routes, out = {}, {"method": method, "sizes": serving_sizes(eng.lib, method)}
     if route in ("both", "serving"):
         from pevit_amd import adapter_io
         from pevit_amd.serving import InferenceEngine
-        ckpt = adapter_io.engine_adapter_state(eng, sd)
+        ckpt = adapter_io.engine_adapter_state(eng, sd, phm_rule=rule)
         inf = InferenceEngine(arch, method, classes, 128)
         inf.load_backbone(sd)
         for name in ("a", "b"):
@@ -209,18 +219,19 @@ def serving_leg(steps, reps, route):
     return out
 
 
-def segments_leg(steps, reps, one_pass=None):
-    """ViT-B/32 + KAdaptation, 8 resident adapters, 8 requests of 16 images for 8 different adapters: the loop ``use(name);
+def segments_leg(steps, reps, one_pass=None, method="kadaptation"):
+    """ViT-B/32 + ``method``, 8 resident adapters, 8 requests of 16 images for 8 different adapters: the loop ``use(name);
     predict(images)`` per request on a plain context ("loop": the route before segments, unchanged code) against one
     ``predict_segments`` call on a ``slots = 8`` context ("segments"), same images, passes in alternation as the other legs.  Next
     to it what a ``slots = 8`` context costs: ``predict`` at batch 128 on it against the plain context (its QKV product is 512
-    columns wider than 3 E + 64 for the single-adapter calls), and the arena / workspace bytes of both."""
+    columns wider than 3 E + 64 for the single-adapter calls; a post-MLP slot context runs the very launches of the plain one), and
+    the arena / workspace bytes of both."""
     from pevit_amd import adapter_io
     from pevit_amd.engine import HipEngine, adapter_param_spec
     from pevit_amd.serving import InferenceEngine
     from pevit_amd.synth import ARCHS, randomize_adapters, synth_state_dict
     dev = torch.device("cuda", 0)
-    arch, method, classes, n_req, req = ARCHS["ViT-B/32"], "kadaptation", 100, 8, 16
+    arch, classes, n_req, req = ARCHS["ViT-B/32"], 100, 8, 16
     sd = {k: v for k, v in synth_state_dict(arch, seed=2, text_tower=False).items() if k.startswith("visual.")}
     ckpts = []
     for i in range(n_req):                                # eight different adapters and heads
@@ -228,11 +239,14 @@ def segments_leg(steps, reps, one_pass=None):
         randomize_adapters(ad, seed=3 + i)
         eng = HipEngine(arch, method, classes, 16)
         eng.load_state_dict(dict(sd, **dict(ad)))
+        rule = rule_of(method, seed=11 + i)                 # (Compacter: eight different frozen rules too)
+        if rule is not None:
+            eng.load_phm_rule(rule)
         g = torch.Generator().manual_seed(5 + i)
         with torch.no_grad():
             eng.param_views()["layers.0.weight"].copy_(((torch.rand((classes, 512), generator=g) * 2 - 1) / 512 ** 0.5).cuda())
             eng.running_var.copy_((0.5 + torch.rand(512, generator=g)).cuda())
-        ckpts.append(adapter_io.engine_adapter_state(eng, sd))
+        ckpts.append(adapter_io.engine_adapter_state(eng, sd, phm_rule=rule))
         del eng
     torch.cuda.empty_cache()
     names = [f"task{i}" for i in range(n_req)]
@@ -244,7 +258,7 @@ def segments_leg(steps, reps, one_pass=None):
             e.add_adapter(n, ck)
         engines[kind] = e
     plain, multi = engines["plain"], engines["slots8"]
-    out = {"sizes": {k: {"arena_bytes": e.arena_bytes, "workspace_bytes_max_batch_128": e.workspace_bytes} for k, e in engines.items()}}
+    out = {"method": method, "sizes": {k: {"arena_bytes": e.arena_bytes, "workspace_bytes_max_batch_128": e.workspace_bytes} for k, e in engines.items()}}
     x = torch.randn((steps, n_req * req, 3, 224, 224), generator=torch.Generator().manual_seed(0)).to(dev)
 
     def loop(batch):
@@ -325,16 +339,17 @@ def main():
     ap.add_argument("--serving-route", choices=["both", "train", "serving"], default="both")
     ap.add_argument("--segments", action="store_true")
     ap.add_argument("--segments-one-pass", choices=["loop", "segments"], default=None)
+    ap.add_argument("--method", choices=["kadaptation", "lora", "adapter", "compacter"], default="kadaptation")
     args = ap.parse_args()
     if args.segments or args.segments_one_pass:
-        s = json.dumps(segments_leg(args.steps, args.reps, args.segments_one_pass), indent=1)
+        s = json.dumps(segments_leg(args.steps, args.reps, args.segments_one_pass, args.method), indent=1)
         print(s)
         if args.out:
             with open(args.out, "w") as f:
                 f.write(s + "\n")
         return
     if args.serving:
-        s = json.dumps(serving_leg(args.steps, args.reps, args.serving_route), indent=1)
+        s = json.dumps(serving_leg(args.steps, args.reps, args.serving_route, args.method), indent=1)
         print(s)
         if args.out:
             with open(args.out, "w") as f:
